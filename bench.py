@@ -3,7 +3,13 @@
 Whitted raytrace (librtg.so HIP kernel) on BASELINE.json's configs[2] workload.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...        (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(value, ms_per_step, kernel_ms and what else falls out of the timed steps).
+--dump-outputs DIR also writes the frame of the last timed step (dump_outputs
+below).  Everything that takes runs of its own is behind --full.
 
 A step renders ONE full frame (3840x2160, 16 spheres, 3 lights, depth 5 =
 RTSTACK_MAXSIZE 6, 3x3 supersampling = 74.6 M primary rays) of the seeded
@@ -13,8 +19,8 @@ and rank 0 gathers them with one RCCL gather over xGMI and restores row order
 on the device, so the step ends with the whole frame in rank 0's HBM (strong
 scaling: fixed frame).  Rank 0 prints one JSON line.
 
-Also reported: the kernel roofline (VALU issue; work = the VALU operations the
-kernel EXECUTES, counted per wave by the counting build of the same kernel,
+With --full also reported: the launches of a fresh frame geometry on the warm
+GPU, the kernel roofline (VALU issue; work = the VALU operations the kernel EXECUTES, counted per wave by the counting build of the same kernel,
 rtg_amd/work.py; the reference's brute-force test count x 25 flops beside it
 as `reference_work`), end-to-end frame times (scene preparation + upload,
 render, read-back, PPM bytes), the reference CPU path timed on a bounded
@@ -68,6 +74,32 @@ def canon_md5(fb: np.ndarray) -> str:
     b = fb.view(np.uint32).copy()
     b[np.isnan(fb)] = 0xFFC00000
     return hashlib.md5(b.tobytes()).hexdigest()
+
+
+DUMP_MAX_BYTES = 48 << 20  # of .npy data per --dump-outputs, both arrays together
+
+
+def dump_outputs(out_dir: str, frame: torch.Tensor) -> None:
+    """--dump-outputs: the frame the last timed step left in rank 0's HBM (what
+    a caller of the timed path receives), for comparing two builds output for
+    output.  Two float32 arrays of one shape: frame.npy, the colours with every
+    NaN written as 0, and frame_isnan.npy, 1 where the colour is NaN and 0
+    elsewhere (the reference's total internal reflection yields NaNs, 0.7 %
+    of C3's values; NaN != NaN under plain array arithmetic and its payload is
+    implementation-defined, so the positions are stored beside the values).
+    A frame within DUMP_MAX_BYTES is written whole as (H, W, 3); of a larger
+    one a uniform sample of pixels, drawn without replacement by a generator
+    seeded with 7 and kept in frame order, as (pixels, 3)."""
+    H, W, _ = frame.shape
+    px = DUMP_MAX_BYTES // (2 * 12)
+    if H * W > px:
+        idx = np.sort(np.random.default_rng(7).choice(H * W, size=px, replace=False))
+        frame = frame.reshape(-1, 3)[torch.from_numpy(idx).to(frame.device)]
+    fb = frame.cpu().numpy()
+    nan = np.isnan(fb)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), np.where(nan, np.float32(0), fb))
+    np.save(os.path.join(out_dir, "frame_isnan.npy"), nan.astype(np.float32))
 
 
 def cpu_threads() -> int:
@@ -199,6 +231,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: fresh-geometry launch timings, "
+                         "parity against the goldens, the CPU baseline, the executed-work "
+                         "roofline and the end-to-end frame times")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's frame to DIR/frame.npy and "
+                         "DIR/frame_isnan.npy (float32; see dump_outputs)")
     ap.add_argument("--row-block", type=int, default=8,
                     help="rows per block of the row-cyclic deal (8: <1 %% imbalance at 8 ranks on C3)")
     ap.add_argument("--variant", type=int, default=0)
@@ -233,6 +272,8 @@ def main():
     if args.cpu_only:
         cpu_only(args)
         return
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed region)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -378,6 +419,14 @@ def main():
     # the process's very first launch (code objects loaded, launch scratch
     # allocated: first_launch_process_ms), then set_scene again (a new scene
     # generation, so no feedback) and its first launch (first_launch_ms).
+    # Every run makes these two launches, a plain one too: they load the code
+    # objects, and the timed region starts at a fixed launch of the process
+    # and of this frame geometry (launch-order feedback holds from a
+    # geometry's third launch on).  The timed steps run before the GPU has
+    # reached its steady clocks (the fresh-geometry launches after them are
+    # faster), so the figure moves with what precedes them: with one untimed
+    # launch in their place ms_per_step came out 1.6 % higher (medians of 6
+    # interleaved runs, C3, --steps 20 --warmup 3).
     first_ms = first_proc_ms = None
     if world == 1:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -450,6 +499,9 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     mpx = W * H / (elapsed / args.steps) / 1e6
 
+    if args.dump_outputs and rank == 0:  # before anything renders into the frame again
+        dump_outputs(args.dump_outputs, frame)
+
     # The first launches of a fresh frame geometry on a WARM GPU (after the
     # timed region; set_scene starts a new scene generation, so the launch-
     # order feedback starts empty).  first_launch_ms above is the same launch
@@ -459,7 +511,7 @@ def main():
     # so the two figures separate the launch path's own cold cost from the
     # GPU's power-state ramp.
     fresh_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         fresh_ms = []
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ctx.set_scene(sph, lg)
@@ -513,6 +565,36 @@ def main():
 
     if rank != 0:
         dist.destroy_process_group()
+        return
+
+    # ---------------- the result line of the timed steps
+    out = {
+        "metric": METRIC, "value": round(mpx, 2), "unit": "Mpixels/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic: seeded scene generator (SURVEY.md §8d, seed 42), resident in HBM",
+        "config": {"workload": f"{args.config}: {W}x{H}, {n} spheres, {m} lights, depth {depth} "
+                               f"(RTSTACK_MAXSIZE {S}), 3x3 supersampling",
+                   "width": W, "height": H, "spheres": n, "lights": m, "depth": depth,
+                   "alias_factor": 3, "row_block": B, "variant": args.variant,
+                   "parallelism": f"row-cyclic x{world}" + (
+                       ((f" + RCCL gather ({K} pipelined chunks)") if args.dist_backend == "nccl"
+                        else " + gloo gather") if world > 1 else "")},
+        "mrays_per_s": round(mpx * 9, 1),
+        "kernel_ms": round(kern_ms, 4), "kernel_ms_max_rank": round(kern_max_ms, 4),
+        "first_launch_ms": round(first_ms, 4) if first_ms is not None else None,
+        "first_launch_process_ms": round(first_proc_ms, 4) if first_proc_ms is not None else None,
+        "timed_launches": {"first": 2 + args.warmup if world == 1 else None,
+                           "count": args.steps,
+                           "note": "trace-kernel dispatches [first, first + count) of this "
+                                   "process are the timed region's (tools/timed_stats.py)"},
+        "multi_gpu": multi, "ab": ab, "diag": diag, "full": args.full,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
         return
 
     # ---------------- parity of the produced frame vs the reference goldens
@@ -709,34 +791,13 @@ def main():
                 roof["traffic_note"] = ("PMC FETCH_SIZE x2 + WRITE_SIZE per launch "
                                         f"({os.path.relpath(pmc, ROOT)})")
 
-    out = {
-        "metric": METRIC, "value": round(mpx, 2), "unit": "Mpixels/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic: seeded scene generator (SURVEY.md §8d, seed 42), resident in HBM",
-        "config": {"workload": f"{args.config}: {W}x{H}, {n} spheres, {m} lights, depth {depth} "
-                               f"(RTSTACK_MAXSIZE {S}), 3x3 supersampling",
-                   "width": W, "height": H, "spheres": n, "lights": m, "depth": depth,
-                   "alias_factor": 3, "row_block": B, "variant": args.variant,
-                   "parallelism": f"row-cyclic x{world}" + (
-                       ((f" + RCCL gather ({K} pipelined chunks)") if args.dist_backend == "nccl"
-                        else " + gloo gather") if world > 1 else "")},
-        "mrays_per_s": round(mpx * 9, 1),
-        "kernel_ms": round(kern_ms, 4), "kernel_ms_max_rank": round(kern_max_ms, 4),
-        "first_launch_ms": round(first_ms, 4) if first_ms is not None else None,
-        "first_launch_process_ms": round(first_proc_ms, 4) if first_proc_ms is not None else None,
+    out.update({
         "first_launch_warm_gpu_ms": fresh_ms[0] if fresh_ms else None,
         "fresh_geometry_launches_warm_ms": fresh_ms,
-        "timed_launches": {"first": 2 + args.warmup if world == 1 else None,
-                           "count": args.steps,
-                           "note": "trace-kernel dispatches [first, first + count) of this "
-                                   "process are the timed region's (tools/timed_stats.py)"},
-        "roofline": roof, "cpu_baseline": cpu, "e2e": e2e, "multi_gpu": multi,
+        "roofline": roof, "cpu_baseline": cpu, "e2e": e2e,
         "gpu_vs_cpu": round(mpx / cpu["value"], 1) if cpu else None,
         "parity": parity,
-        "ab": ab,
-        "diag": diag,
-    }
+    })
     print(json.dumps(out), flush=True)
     ctx.close()
     if world > 1:

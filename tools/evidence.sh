@@ -33,7 +33,7 @@ for c in ${CONFIGS:-c3 c2 c4 c5 c1cpu}; do
     tail -c 300 $OUT/bench_c1_cpu.json; echo
     continue
   fi
-  timeout -k 10 600 python bench.py --config $c --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
+  timeout -k 10 600 python bench.py --config $c --steps ${STEPS:-20} --warmup 3 --full ${BENCH_ARGS:-} > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
   python -c "import json;d=json.loads(open('$OUT/bench_$c.json').read().strip().splitlines()[-1]);r=d['roofline'] or {};print('$c', d['value'], d['unit'], d['ms_per_step'], 'first', d.get('first_launch_ms'), 'warm-first', d.get('first_launch_warm_gpu_ms'), 'frac', r.get('frac'), 'frac_pmc', r.get('frac_pmc'), 'model/pmc', r.get('model_vs_pmc_valu'), 'traffic', r.get('traffic'), 'cpu', (d['cpu_baseline'] or {}).get('value'), 'bit_exact', d['parity'].get('bit_exact'), 'fb', d['parity'].get('fb_md5_match'), 'ppm', d['parity'].get('ppm_md5_match'))"
 done
 [ -n "$NO_PROFILES" ] && exit 0

@@ -37,7 +37,7 @@ for step in "$@"; do
       lib=""; [ -n "$b" ] && lib=$(lib_path "$b")
       d=$O/sqc_${a}_${b:-shipped}
       ( cd /tmp && export TMPDIR=/tmp && RTG_LIB=$lib timeout -s KILL 240 rocprofv3 --pmc SQC_DCACHE_HITS SQC_DCACHE_MISSES SQ_INSTS_SMEM SQ_INSTS_VMEM \
-          --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --config "$a" --steps 1 --warmup 1 \
+          --output-format csv -d "$d" -o run -- python3 "$ROOT/bench.py" --config "$a" --steps 1 --warmup 1 --full \
           --no-cpu-baseline --no-work-count --no-e2e > "$d.json" 2> "$d.err" ) || { tail -5 "$d.err"; exit 1; }
       python3 tools/pmc_kernel_avg.py "$d" "$d.json" | tee "$d.txt" ;;
     calib)
@@ -55,11 +55,11 @@ for step in "$@"; do
         > "$O/pytest_gpu.log" 2>&1 || { tail -40 "$O/pytest_gpu.log"; exit 1; }
       tail -5 "$O/pytest_gpu.log" ;;
     bench)
-      timeout -k 10 600 python bench.py --config "$a" ${b:-} > "$O/bench_$a.json" 2> "$O/bench_$a.err" || { tail -20 "$O/bench_$a.err"; exit 1; }
+      timeout -k 10 600 python bench.py --config "$a" --full ${b:-} > "$O/bench_$a.json" 2> "$O/bench_$a.err" || { tail -20 "$O/bench_$a.err"; exit 1; }
       cat "$O/bench_$a.json" ;;
     prof)
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d "$O/prof_$a" -o run -- python3 "$ROOT/bench.py" --config "$a" > "$O/prof_bench_$a.json" 2> "$O/prof_bench_$a.err" ) \
+          -d "$O/prof_$a" -o run -- python3 "$ROOT/bench.py" --config "$a" --full > "$O/prof_bench_$a.json" 2> "$O/prof_bench_$a.err" ) \
         || { tail -20 "$O/prof_bench_$a.err"; exit 1; }
       python3 tools/timed_stats.py "$O/prof_$a" "$O/prof_bench_$a.json" "$O/timed_stats_$a" > "$O/timed_stats_$a.txt" 2>&1 || true
       cat "$O/timed_stats_$a.txt" ;;
