@@ -18,6 +18,8 @@
  *   savePPM  main.cpp:43-91                            rtg_save_ppm / rtg_ppm_bytes
  *   rayTrace(...)  raytracer.h:410-636 (CPU entry)     (inside the HIP kernel)
  *   (8-GPU node, SURVEY.md §8e: none in the reference) rtg_render_multi (RCCL gather)
+ *   (primary visibility per pixel: none in the reference) rtg_gbuffer / rtg_gbuffer_device /
+ *                                                      rtg_gbuffer_host
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
  *   output_device_info  device_info.cpp:30             rtg_device_info
  *   parseArguments --list/--device  device_picker.h:70 rtg_device_count / device index args
@@ -193,6 +195,50 @@ int rtg_render_rows(int device, const rtg_sphere* spheres, unsigned sphNum,
                     const rtg_light* lights, unsigned lgtNum, unsigned width, unsigned height,
                     float zoom, float aliasFactor, int stackSize, const unsigned* rows,
                     unsigned nRows, rtg_vec* dstHost);
+
+/* ---- primary-hit G-buffer: id, depth, normal and coverage per pixel ----
+ * What the primary rays of a pixel see, before any shading (picking, object
+ * masks and alpha, denoiser guides, edge detection, "why is this pixel
+ * black?").  Per sample (i, j) of the pixel, in the reference's loop order
+ * (main.cpp:411-452), the ray starts at o = (0,0,0) with the direction the
+ * render uses, and its hit is calcIntersection's (raytracer.h:145-194) in the
+ * same float operations: the raySphere root test with the 1e-5 / 10000
+ * window, minT starting at 1000, strict <, the first index winning ties.
+ * The pixel's winning sample is the one with the smallest t among those that
+ * hit, the lowest sample index on a tie.
+ *   hits * (id + 1) != idSum marks a mixed pixel: its samples hit more than
+ *   one sphere (an edge between spheres); 0 < hits < nAA*nAA is a silhouette
+ *   against the background (hits / nAA^2 is its coverage).  hits == 0 is a
+ *   pixel the render leaves +0 in every channel.
+ * NaN or degenerate inputs follow the comparisons as written (a comparison
+ * with NaN is false: a miss); a NaN normal component is written as
+ * 0xFFC00000, like the frame's NaNs.  The G-buffer does not depend on
+ * stackSize, lights or rtg_context_set_semantics. */
+typedef struct rtg_gbuf_px { /* 32 bytes */
+  int id;          /* sphere index of the winning sample's closest hit; -1: no sample hit */
+  float t;         /* that hit's t (calcIntersection's minT); 1000.f when id == -1 */
+  unsigned hits;   /* samples of the pixel whose primary ray hit a sphere, 0..nAA*nAA */
+  unsigned sample; /* winning sample's index i*nAA + j (reference loop order); 0 when none */
+  rtg_vec normal;  /* vnorm(P - c) at the winning hit, P = o + t*d; (0,0,0) when none */
+  unsigned idSum;  /* sum over the pixel's samples of (id_sample + 1), mod 2^32; a miss adds 0 */
+} rtg_gbuf_px;
+/* Asynchronous G-buffer of shard `shard` of a W x H frame of the context's
+ * scene into device memory dstDevice (rtg_shard_rows(...) * W records, 16-byte
+ * aligned) on `stream`; shard rows packed as rtg_render_device packs them.
+ * Uses none of the context's render scratch: it may be mixed freely with
+ * rtg_render_device calls on the same context. */
+int rtg_gbuffer_device(rtg_context* ctx, unsigned width, unsigned height, float zoom,
+                       float aliasFactor, unsigned rowBlock, unsigned shard, unsigned nShards,
+                       rtg_gbuf_px* dstDevice, void* stream);
+/* One-shot: uploads the scene, runs on `device`, downloads W*H records. */
+int rtg_gbuffer(int device, const rtg_sphere* spheres, unsigned sphNum, unsigned width,
+                unsigned height, float zoom, float aliasFactor, rtg_gbuf_px* dstHost);
+/* The same records computed on the host with plain loops over every pixel,
+ * sample and sphere (no GPU call; the device kernel's yardstick, and usable
+ * on a machine without a GPU).  nthreads <= 0: 1. */
+int rtg_gbuffer_host(const rtg_sphere* spheres, unsigned sphNum, unsigned width,
+                     unsigned height, float zoom, float aliasFactor, rtg_gbuf_px* dstHost,
+                     int nthreads);
 
 /* Semantics of a context's renders.  RTG_SEMANTICS_CPU (default) is the
  * reference CPU path (raytracer.h), bit for bit.  RTG_SEMANTICS_OPENCL is the

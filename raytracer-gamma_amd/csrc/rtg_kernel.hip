@@ -107,46 +107,8 @@ __global__ __launch_bounds__(256) void ppm_kernel(const float* __restrict__ c, s
 // background matte is 0), and the pixel sum of +0 * inv is +0 in every
 // channel.  The other groups are appended to groupList (one atomic per wave)
 // for the trace kernel.  n <= 64 spheres.
-// The spheres pixel group g can reach (the cull of trace_group): bit i set
-// when primary_possible keeps sphere i for the group's bundle.
-__device__ __forceinline__ uint64_t group_sel(const KernelArgs& a, size_t g, unsigned PPW,
-                                              size_t total) {
-  const size_t p0 = g * PPW;
-  const unsigned nv = (unsigned)((total - p0 < PPW) ? (total - p0) : PPW);
-  unsigned col, lr;
-  divmod_u64(p0, a.W, a.invW, lr, col);
-  float x0 = 3.0e38f, x1 = -3.0e38f, y0 = 3.0e38f, y1 = -3.0e38f;
-  // one row: the first and last pixels bound the group (monotone float
-  // steps, see trace_group); otherwise every pixel
-  const bool oneRow = col + nv - 1 < a.W;
-  for (unsigned k = 0; k < nv; ++k) {
-    if (!oneRow || k == 0 || k == nv - 1) {
-      const unsigned gy =
-          a.rowList ? a.rowList[lr]
-                    : shard_global_row_fast(lr, a.rowBlock, a.invRowBlock, a.shard, a.nShards);
-      float bx0, bx1, by0, by1;
-      primary_bounds(a.cam, col, gy, bx0, bx1, by0, by1);
-      x0 = fminf(x0, bx0);
-      x1 = fmaxf(x1, bx1);
-      y0 = fminf(y0, by0);
-      y1 = fmaxf(y1, by1);
-    }
-    if (++col == a.W) {
-      col = 0;
-      ++lr;
-    }
-  }
-  const PrimBundle pb = primary_bundle(x0, x1, y0, y1, a.cam.zoom);
-  const RTG_CONST float* geom = (const RTG_CONST float*)a.geom;
-  const RTG_CONST float* pc = (const RTG_CONST float*)a.prim;
-  uint64_t sel = 0;
-  for (unsigned i = 0; i < a.n; ++i) {  // wave-uniform: scalar sphere records
-    const RTG_CONST float* r = geom + 4 * i;
-    const RTG_CONST float* k = pc + 4 * i;
-    if (primary_possible(pb, v3(r[0], r[1], r[2]), k[0], k[1], k[2])) sel |= 1ull << i;
-  }
-  return sel;
-}
+// (group_sel, the group's sphere mask, is in rtg_trace_kernels.h: the G-buffer
+// kernel takes the same cull.)
 
 // Launches of at most this many pixel groups list them in eight runs
 // (KernelArgs::nRuns): a 1/8 or 1/4 C3 shard's chunks (~60 k, ~125 k), not a
@@ -422,6 +384,34 @@ static void free_scene(rtg_context* c) {
   c->mats = nullptr;
   c->lights = nullptr;
   c->hasScene = false;
+}
+
+// The resident scene's tables as kernel arguments.
+static void scene_args(const rtg_context* ctx, KernelArgs* a) {
+  a->geom = ctx->geom;
+  a->crad2 = ctx->crad2;
+  a->mats = ctx->mats;
+  a->lights = ctx->lights;
+  a->smask = ctx->smask;
+  a->cone = ctx->cone;
+  a->prim = ctx->prim;
+  a->bvhNodes = ctx->bvhNodes;
+  a->capRec = ctx->capRec;
+  a->capOff = ctx->capOff;
+  a->ovRec = ctx->ovRec;
+  a->ovOff = ctx->ovOff;
+  a->n = ctx->n;
+  a->m = ctx->m;
+  a->n4 = ctx->n4;
+}
+
+// A context's device and resident scene for the launchers of other
+// translation units (rtg_gbuffer.hip); false when it has no scene.
+bool rtg_context_scene(const rtg_context* ctx, KernelArgs* a, int* device) {
+  if (!ctx || !ctx->hasScene) return false;
+  scene_args(ctx, a);
+  *device = ctx->device;
+  return true;
 }
 
 // Argument checks shared by the one-shot entry points (no HIP call made).
@@ -893,21 +883,7 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
     rtg_set_error("render: null destination");
     return RTG_ERR_INVALID;
   }
-  a.geom = ctx->geom;
-  a.crad2 = ctx->crad2;
-  a.mats = ctx->mats;
-  a.lights = ctx->lights;
-  a.smask = ctx->smask;
-  a.cone = ctx->cone;
-  a.prim = ctx->prim;
-  a.bvhNodes = ctx->bvhNodes;
-  a.capRec = ctx->capRec;
-  a.capOff = ctx->capOff;
-  a.ovRec = ctx->ovRec;
-  a.ovOff = ctx->ovOff;
-  a.n = ctx->n;
-  a.m = ctx->m;
-  a.n4 = ctx->n4;
+  scene_args(ctx, &a);
   a.W = width;
   a.rowsLocal = rows;
   a.rowBlock = rowBlock ? rowBlock : 1;

@@ -600,6 +600,47 @@ __device__ __forceinline__ unsigned shard_global_row_fast(unsigned localRow, uns
   return (lb * G + g) * B + rem;
 }
 
+// The spheres pixel group g can reach (the cull of trace_group): bit i set
+// when primary_possible keeps sphere i for the group's bundle.
+__device__ __forceinline__ uint64_t group_sel(const KernelArgs& a, size_t g, unsigned PPW,
+                                              size_t total) {
+  const size_t p0 = g * PPW;
+  const unsigned nv = (unsigned)((total - p0 < PPW) ? (total - p0) : PPW);
+  unsigned col, lr;
+  divmod_u64(p0, a.W, a.invW, lr, col);
+  float x0 = 3.0e38f, x1 = -3.0e38f, y0 = 3.0e38f, y1 = -3.0e38f;
+  // one row: the first and last pixels bound the group (monotone float
+  // steps, see trace_group); otherwise every pixel
+  const bool oneRow = col + nv - 1 < a.W;
+  for (unsigned k = 0; k < nv; ++k) {
+    if (!oneRow || k == 0 || k == nv - 1) {
+      const unsigned gy =
+          a.rowList ? a.rowList[lr]
+                    : shard_global_row_fast(lr, a.rowBlock, a.invRowBlock, a.shard, a.nShards);
+      float bx0, bx1, by0, by1;
+      primary_bounds(a.cam, col, gy, bx0, bx1, by0, by1);
+      x0 = fminf(x0, bx0);
+      x1 = fmaxf(x1, bx1);
+      y0 = fminf(y0, by0);
+      y1 = fmaxf(y1, by1);
+    }
+    if (++col == a.W) {
+      col = 0;
+      ++lr;
+    }
+  }
+  const PrimBundle pb = primary_bundle(x0, x1, y0, y1, a.cam.zoom);
+  const RTG_CONST float* geom = (const RTG_CONST float*)a.geom;
+  const RTG_CONST float* pc = (const RTG_CONST float*)a.prim;
+  uint64_t sel = 0;
+  for (unsigned i = 0; i < a.n; ++i) {  // wave-uniform: scalar sphere records
+    const RTG_CONST float* r = geom + 4 * i;
+    const RTG_CONST float* k = pc + 4 * i;
+    if (primary_possible(pb, v3(r[0], r[1], r[2]), k[0], k[1], k[2])) sel |= 1ull << i;
+  }
+  return sel;
+}
+
 __device__ __forceinline__ float canon_nan(float v) {
   // x86 default NaN, what the reference CPU path writes (see rtg.h).
   return (v != v) ? __uint_as_float(0xFFC00000u) : v;
@@ -1301,3 +1342,7 @@ RTG_DECL(14) RTG_DECL(15) RTG_DECL(16)
 #undef RTG_DECL
 
 }  // namespace rtg
+
+// rtg_kernel.hip: a context's device and the scene tables of its KernelArgs
+// (geom .. n4); false when the context is null or has no scene.
+bool rtg_context_scene(const rtg_context* ctx, rtg::KernelArgs* a, int* device);

@@ -39,6 +39,8 @@ static void usage() {
   printf("      --zoom       Z       Zoom factor (default -4)\n");
   printf("      --seed       S       Scene generator seed (default 42)\n");
   printf("      --out        FILE    Output PPM (default testPPM.ppm)\n");
+  printf("      --gbuffer    FILE    Also write the primary-hit G-buffer: W*H raw little-endian\n");
+  printf("                           rtg_gbuf_px records (id, t, hits, sample, normal, idSum)\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -60,7 +62,7 @@ int main(int argc, char** argv) {
   unsigned device = 0, W = 800, H = 600, nSph = 3, nLgt = 2, depth = 5, repeat = 1;
   unsigned long long seed = 42;
   float aa = 3.f, zoom = -4.f;
-  std::string out = "testPPM.ppm", sceneIn, sceneOut;
+  std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut;
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   for (int i = 1; i < argc; ++i) {
@@ -109,6 +111,8 @@ int main(int argc, char** argv) {
       seed = strtoull(need(a), nullptr, 10);
     } else if (!strcmp(a, "--out")) {
       out = need(a);
+    } else if (!strcmp(a, "--gbuffer")) {
+      gbufOut = need(a);
     } else if (!strcmp(a, "--scene")) {
       sceneIn = need(a);
     } else if (!strcmp(a, "--save-scene")) {
@@ -203,5 +207,19 @@ int main(int argc, char** argv) {
   check(rtg_save_ppm(pixels.data(), out.c_str(), (int)W, (int)H, mx), "rtg_save_ppm");
   printf("Wrote %s (%ux%u, %u spheres, %u lights, depth %u, max colour %.8g)\n", out.c_str(), W,
          H, nSph, nLgt, depth, (double)mx);
+
+  if (!gbufOut.empty()) {  // the records as they lie in memory (the GPU hosts are little-endian)
+    std::vector<rtg_gbuf_px> gbuf((size_t)W * H);
+    check(rtg_gbuffer((int)device, spheres.data(), nSph, W, H, zoom, aa, gbuf.data()),
+          "rtg_gbuffer");
+    FILE* f = fopen(gbufOut.c_str(), "wb");
+    if (!f || fwrite(gbuf.data(), sizeof(rtg_gbuf_px), gbuf.size(), f) != gbuf.size() ||
+        fclose(f) != 0) {
+      fprintf(stderr, "Error: can't write %s\n", gbufOut.c_str());
+      exit(EXIT_FAILURE);
+    }
+    printf("Wrote %s (%zu G-buffer records of %zu bytes)\n", gbufOut.c_str(), gbuf.size(),
+           sizeof(rtg_gbuf_px));
+  }
   return 0;
 }

@@ -44,6 +44,10 @@ SPHERE_DTYPE = np.dtype([("pos", "<f4", 3), ("radius", "<f4"), ("material", MATE
 LIGHT_DTYPE = np.dtype([("pos", "<f4", 3), ("col", "<f4", 3)])
 assert VEC_DTYPE.itemsize == 12 and MATERIAL_DTYPE.itemsize == 32
 assert SPHERE_DTYPE.itemsize == 48 and LIGHT_DTYPE.itemsize == 24
+# rtg_gbuf_px (include/rtg.h): the primary-hit G-buffer's record
+GBUF_DTYPE = np.dtype([("id", "<i4"), ("t", "<f4"), ("hits", "<u4"), ("sample", "<u4"),
+                       ("normal", "<f4", 3), ("idSum", "<u4")])
+assert GBUF_DTYPE.itemsize == 32
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -62,6 +66,7 @@ EXPORTED = [
     "rtg_render_multi", "rtg_scene_load", "rtg_scene_save", "rtg_context_set_semantics",
     "rtg_multi_create", "rtg_multi_set_scene", "rtg_multi_render", "rtg_multi_destroy",
     "rtg_multi_set_gather", "rtg_place_shard_device",
+    "rtg_gbuffer_device", "rtg_gbuffer", "rtg_gbuffer_host",
 ]
 
 
@@ -140,6 +145,9 @@ def lib() -> ctypes.CDLL:
         L.rtg_multi_set_scene.argtypes = [vp, vp, u, vp, u]
         L.rtg_multi_render.argtypes = [vp, u, u, f, f, i, u, vp, vp]
         L.rtg_multi_destroy.argtypes = [vp]
+        L.rtg_gbuffer_device.argtypes = [vp, u, u, f, f, u, u, u, vp, vp]
+        L.rtg_gbuffer.argtypes = [i, vp, u, u, u, f, f, vp]
+        L.rtg_gbuffer_host.argtypes = [vp, u, u, u, f, f, vp, i]
 
         pu = ctypes.POINTER(u)
         L.rtg_scene_load.argtypes = [ctypes.c_char_p, vp, u, pu, vp, u, pu]
@@ -288,6 +296,28 @@ def render_multi(spheres, lights, width: int, height: int, devices=(0,), zoom: f
                                   float(alias_factor), stack_size, row_block, _ptr(out),
                                   _ptr(tm)), "rtg_render_multi")
     return out, [float(v) for v in tm]
+
+
+def gbuffer(spheres, width: int, height: int, zoom: float = -4.0, alias_factor: float = 3.0,
+            device: int = 0) -> np.ndarray:
+    """Primary-hit G-buffer of a scene on the GPU (rtg_gbuffer): an (H, W) array
+    of GBUF_DTYPE records (closest sphere id, t, normal, sample coverage)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    out = np.empty((height, width), GBUF_DTYPE)
+    _check(lib().rtg_gbuffer(device, _ptr(spheres), len(spheres), width, height, float(zoom),
+                             float(alias_factor), _ptr(out)), "rtg_gbuffer")
+    return out
+
+
+def gbuffer_host(spheres, width: int, height: int, zoom: float = -4.0,
+                 alias_factor: float = 3.0, threads: int = 1) -> np.ndarray:
+    """The same records computed on the host with plain loops (rtg_gbuffer_host;
+    no GPU needed)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    out = np.empty((height, width), GBUF_DTYPE)
+    _check(lib().rtg_gbuffer_host(_ptr(spheres), len(spheres), width, height, float(zoom),
+                                  float(alias_factor), _ptr(out), threads), "rtg_gbuffer_host")
+    return out
 
 
 class MultiContext:
@@ -451,6 +481,16 @@ class Context:
                                        n_shards, ctypes.c_void_p(dst_ptr),
                                        ctypes.c_void_p(stream) if stream else None),
                "rtg_render_device")
+
+    def gbuffer_device(self, width, height, dst_ptr: int, zoom=-4.0, alias_factor=3.0,
+                       row_block=16, shard=0, n_shards=1, stream: int = 0):
+        """Primary-hit G-buffer of the resident scene into device memory
+        (GBUF_DTYPE records, the shard's rows packed as render_device packs them)."""
+        _check(lib().rtg_gbuffer_device(self._h, width, height, float(zoom),
+                                        float(alias_factor), row_block, shard, n_shards,
+                                        ctypes.c_void_p(dst_ptr),
+                                        ctypes.c_void_p(stream) if stream else None),
+               "rtg_gbuffer_device")
 
     def render_rows_device(self, width, height, rows_ptr: int, n_rows: int, dst_ptr: int,
                            zoom=-4.0, alias_factor=3.0, stack_size=6, stream: int = 0):
