@@ -253,7 +253,7 @@ int rtg_context_set_semantics(rtg_context* ctx, int semantics);
 
 /* Launch-configuration knobs (performance only; results never change). */
 typedef struct rtg_launch_opts {
-  int variant;        /* 0 = default kernel; other values select A/B variants */
+  int variant;        /* 0 = default kernel; 9 tile kernel; 100, 110, 120 diagnostic builds */
   int flags;          /* RTG_LAUNCH_* bits */
   int reserved[6];
 } rtg_launch_opts;

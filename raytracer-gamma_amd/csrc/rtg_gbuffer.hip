@@ -135,7 +135,7 @@ static void gbuffer_host_rows(const HostSpheres& sc, const Camera& cam, unsigned
 // loads for wave-uniform indices), without frames; `stk`: the wave's BVH
 // traversal stack in LDS.
 template <bool kBvh>
-using GbufScene = DevScene<cfloat_p, false, 64, kBvh, kFusePrim>;
+using GbufScene = DevScene<false, 64, kBvh, kFusePrim>;
 
 template <bool kBvh>
 __device__ __forceinline__ void gbuf_scene(const KernelArgs& a, GbufScene<kBvh>& sc, int* stk) {

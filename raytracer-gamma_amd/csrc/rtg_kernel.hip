@@ -256,9 +256,9 @@ __global__ __launch_bounds__(256) void cull_groups_kernel(const KernelArgs a, si
   }
 }
 
-static TraceFn pick_trace(int S, bool lds, int variant, bool bvh, int list) {
+static TraceFn pick_trace(int S, int variant, bool bvh, int list) {
   switch (S) {
-#define RTG_CASE(k) case k: return trace_fn_s##k(lds, variant, bvh, list);
+#define RTG_CASE(k) case k: return trace_fn_s##k(variant, bvh, list);
     RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
     RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
     RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
@@ -836,7 +836,6 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
     rtg_set_error("render: no context/scene");
     return RTG_ERR_INVALID;
   }
-  bool ldsMats = ctx->n + 1 <= kLdsMatMax;
   if (stackSize < 1 || stackSize > RTG_MAX_STACK) {  // before anything is launched
     rtg_set_error("no kernel for stackSize %d (valid: 1..%d)", stackSize, RTG_MAX_STACK);
     return RTG_ERR_INVALID;
@@ -858,12 +857,6 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
     vi = variant_info(variant);
   }
   const bool sampleKernel = vi->kind == kVariantSample;
-  // the default sample kernel reads materials/geometry from global memory
-  // (L1/L2-resident), not from a per-workgroup LDS copy (as do the shipped
-  // tile kernels 9, 59, 100); only the A/B variants below stage it
-  if (!(variant == 1 || variant == 2 || variant == 3 || variant == 4 || variant == 5 ||
-        variant == 6 || variant == 8 || variant == 14 || variant == 104 || variant == 108))
-    ldsMats = false;
   unsigned rows;
   if (rowList) {
     rows = nRowList;
@@ -930,22 +923,17 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
   size_t cullGroups = 0;                   // pixel groups of the cull pass
   if (sampleKernel) {
     const unsigned ppw = 64u / (unsigned)(a.cam.nAA * a.cam.nAA);  // >= 1: nAA <= 8 here
-    const size_t groupsPerWave = variant == 21 ? 4 : 1;
+    // one-wave workgroups, one pixel group per wave
     const size_t groups = ((size_t)width * rows + ppw - 1) / ppw;
-    const size_t waves = (groups + groupsPerWave - 1) / groupsPerWave;
-    const unsigned tpb = variant == 14 ? 256u : 64u;
-    const size_t blocks = (waves + tpb / 64 - 1) / (tpb / 64);
-    threads = tpb;
-    if (blocks > 0x7FFFFFFFu) {
-      rtg_set_error("render: frame too large (%zu workgroups)", blocks);
+    threads = 64u;
+    if (groups > 0x7FFFFFFFu) {
+      rtg_set_error("render: frame too large (%zu workgroups)", groups);
       return RTG_ERR_INVALID;
     }
-    grid = dim3((unsigned)blocks, 1);
-    // Compacted launch (the default; variant 22 and the multi-wave-workgroup
-    // variants launch one wave per group instead): a cull pass writes the
+    grid = dim3((unsigned)groups, 1);
+    // Compacted launch (scenes of <= 64 spheres): a cull pass writes the
     // groups no primary ray can leave (+0) and lists the others; a grid of
     // one-wave workgroups traces the listed groups round-robin.
-    const bool compact = tpb == 64 && variant != 21 && variant != 22;
     // each list partition's capacity: the groups of its cull-pass blocks
     const size_t cullBlocks = (groups + 255) / 256;
     const size_t partCap = (cullBlocks + kListParts - 1) / kListParts * 256;
@@ -953,7 +941,7 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
     // eight longest-first runs, whole frames in four
     const unsigned nRuns = groups <= kRuns8MaxGroups ? 8u : 4u;
     const size_t listCap = (nRuns / 2) * kListParts * partCap;  // list entries (KernelArgs::groupCap)
-    if (compact && ctx->n <= 64 && listCap < 0xFFFFFFFFull) {
+    if (ctx->n <= 64 && listCap < 0xFFFFFFFFull) {
       listed = true;
       const hipStream_t st = (hipStream_t)stream;
       slotIdx = ctx->nextSlot;  // the ring advances at the commit below
@@ -1055,7 +1043,7 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
   // the compacted default kernel of a scene with shadow/overlap and cone masks
   // takes them as compile-time facts (kMasks)
   const int listKind = !listed ? 0 : (ctx->smask && ctx->cone) ? 2 : 1;
-  TraceFn fn = pick_trace(stackSize, ldsMats, variant, ctx->bvhNodes != nullptr, listKind);
+  TraceFn fn = pick_trace(stackSize, variant, ctx->bvhNodes != nullptr, listKind);
   if (!fn) {
     rtg_set_error("no kernel for stackSize %d (valid: 1..%d), variant %d", stackSize,
                   RTG_MAX_STACK, variant);
@@ -1065,10 +1053,7 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
   // keeps one fewer, LdsFramesTop)
   const bool bvhKernel = ctx->bvhNodes != nullptr && has_bvh_kernel(variant);
   const size_t frameLds = (size_t)frame_lds_levels(stackSize, bvhKernel) * threads * 16;
-  const size_t lds = frameLds +
-                     (ldsMats ? ((size_t)(ctx->n + 1) * 8 * sizeof(float) + (size_t)ctx->n4 * 16)
-                              : 0) +
-                     (ctx->bvhNodes ? (size_t)(threads / 64) * 64 * sizeof(int) : 0);
+  const size_t lds = frameLds + (ctx->bvhNodes ? (size_t)(threads / 64) * 64 * sizeof(int) : 0);
   if (ctx->opts.flags & RTG_LAUNCH_TIMELINE) {
     const size_t waves = (size_t)grid.x * grid.y * (threads / 64);
     if (ctx->timelineCap < waves) {

@@ -180,7 +180,11 @@ struct Mat { V3 matte, gloss; float opacity, refr; };
 // Fused query forms (Scene::fuse bits; results identical, speed differs):
 // screen and exact root test in ONE wave-uniform loop over a sphere subset,
 // with scalar record loads, instead of a screen pass plus a per-lane
-// candidate loop with per-lane record gathers.
+// candidate loop with per-lane record gathers.  The sample kernels set every
+// bit and the tile kernels run only closest_hit_sel's two-pass form; the other
+// two-pass forms, like query strategies 0, 1 and 3 and the persistent and node
+// pixel loops below, run only in the host build that tests/test_oracle.py
+// checks against the oracle (tests/hostsim).
 enum : int { kFusePrim = 1, kFuseCone = 2, kFuseShadow = 4, kFuseEnter = 8 };
 
 // Diagnostic probe slots (scenes without probes implement them as no-ops).
@@ -240,15 +244,6 @@ enum : int { kCntSamples = 0, kCntPrimQ, kCntPrimSel, kCntPrimCand, kCntEnterQ, 
 enum : int { kProbeClosest = 0, kProbeShadow = 1, kProbeRefraction = 2, kProbeTotal = 3,
              kProbeMatte = 4, kProbePush = 5, kProbeUnwind = 6, kProbeShade = 7,
              kProbeSlots = 8 };
-// Finer regions, recorded only by RTG_DIAG_SPLIT builds (in slots 1, 4, 5, 6
-// instead of shadow, matte, push, unwind): the shading set-up after the
-// closest-hit query (hit record, P, N, material, guard test), the refraction
-// target's containment search, the Fresnel factor, and sinA1.
-#ifndef RTG_DIAG_SPLIT
-#define RTG_DIAG_SPLIT 0
-#endif
-enum : int { kProbeSplitBase = 100, kProbeSplitSetup = 101, kProbeSplitContain = 104,
-             kProbeSplitFresnel = 105, kProbeSplitSin = 106 };
 
 // Split frame used by trace_sample: the part every unwind step touches
 // (colour, stage flags, refractive material) is 16 bytes and can live in LDS;
@@ -657,7 +652,6 @@ RTG_HD V3 matte_light(const Scene& sc, V3 P, V3 N, int hit = -1, bool guardOK = 
     V3 Lpos, Lcol;
     sc.light(l, Lpos, Lcol);
     V3 dist = vsub(Lpos, P);
-#if !defined(RTG_NO_FACING_TEST)
     // (Not in the BVH kernels: measured slower there, C5 141.1 vs 139.4 ms.)
     // Facing-away test ahead of the light direction: the reference's
     // incidence (raytracer.h:337-349) is inv (N.dist) with relative
@@ -672,7 +666,6 @@ RTG_HD V3 matte_light(const Scene& sc, V3 P, V3 N, int hit = -1, bool guardOK = 
                             fmaf(fabsf(N.y), fabsf(dist.y), fabsf(N.z * dist.z)));
       if (sc.all(fm >= 0x1p-100f && fmaf(fm, 0x1p-20f, fe) < 0.f)) continue;
     }
-#endif
     sc.count(kULightDir, 1);
     const float gap = vdot(dist, dist);
     const V3 dir = vsmul(rcp_sqrt_rn(gap), dist);  // vnorm(dist)
@@ -808,13 +801,8 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
   float sinA1 = 0.f;
   if (cosA1 <= -1.0f) { cosA1 = -1.f; sinA1 = 0.f; }
   else if (cosA1 >= 1.f) { cosA1 = 1.f; sinA1 = 0.f; }
-  else {
-    sc.probe_begin(kProbeSplitSin);
-    sinA1 = (float)sqrt_d_unit(1.0 - (double)(cosA1 * cosA1));
-    sc.probe_end(kProbeSplitSin);
-  }
+  else sinA1 = (float)sqrt_d_unit(1.0 - (double)(cosA1 * cosA1));
 
-  sc.probe_begin(kProbeSplitContain);
   const V3 testPt = vadd(vsmul(0.01f, D), P);
   int tgt;
   float nTgt;
@@ -845,7 +833,6 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
     }
     if (tgt < 0) tgt = (int)sc.n;  // background material
   }
-  sc.probe_end(kProbeSplitContain);
   const float ratio = nSrc / nTgt;
   const float sinA2 = ratio * sinA1;
 
@@ -881,7 +868,6 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
     }
     dirOut = dir;
   }
-  sc.probe_begin(kProbeSplitFresnel);
   float cosA2 = rtg_sqrtf(1.f - (sinA2 * sinA2));
   if (cosA1 < 0.f) cosA2 = -cosA2;
   const float Rs = polarised_reflection<kCL>(nSrc, nTgt, cosA1, cosA2);
@@ -889,7 +875,6 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
   // (float)((double)(Rs + Rp) * 0.5) (raytracer.h:801): the f64 product is
   // exact, so its rounding to float is the float product's.
   R = (Rs + Rp) * 0.5f;
-  sc.probe_end(kProbeSplitFresnel);
   return tgt;
 }
 
@@ -934,15 +919,6 @@ RTG_HD FrameR load_frame_r(const FrameR& src) {
   return src;
 }
 
-// Internal reflections of BVH scenes traced as entering rays (the sphere in
-// the frame record, scenes below 2048 spheres): C5 -3.3 %, DESIGN.md §4
-// item 63.  0 in A/B builds only.
-#ifndef RTG_BVH_INSIDE
-#define RTG_BVH_INSIDE 1
-#endif
-#ifndef RTG_SELF_SKIP  // the masked scenes' shadow self test (blocked_sel); 0: A/B builds
-#define RTG_SELF_SKIP 1
-#endif
 // One primary sample: rayTrace(spheres, ..., ray, bgMaterial, 0),
 // raytracer.h:410-636, for stack capacity S (RTSTACK_MAXSIZE).
 // kCL: the reference OpenCL kernel's semantics (raytrace_kernel.cl:641-867):
@@ -1005,7 +981,6 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
         uint64_t cm = sc.cone_union(originH, (unsigned)tier, (unsigned)cone_cell(U));
         const RayQ q = make_query(o, d);
         int skip = -1;
-#if RTG_SELF_SKIP
         {
           // the origin sphere (in every cone mask of its own): a ray leaving
           // its surface (refraction out of it) or starting 0.01 off it
@@ -1019,7 +994,6 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
           const int h0 = sc.first_lane_i(originH);
           if (sc.all(skip == h0)) cm &= ~(1ull << h0);
         }
-#endif
         sc.count(kCntConeQ, 1);
         sc.count(kCntConeSel, __builtin_popcountll(cm));
         sc.count(kUQuery, 1);
@@ -1074,7 +1048,6 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
       ret = vmul(I, sc.mat(rm).matte);                       // :544
     } else if (significant(I)) {                             // :460
       sc.count(kUShade, 1);
-      sc.probe_begin(kProbeSplitSetup);
       V3 c;
       float g2, r2h;
       Mat mh;
@@ -1091,7 +1064,6 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
         guardOK = vdot(e, e) <= g2;
         if (sc.has_lists() && guardOK) cell = cap_cell(e, r2h);
       }
-      sc.probe_end(kProbeSplitSetup);
       if (op > 0.f) {
         V3 tmp = vmul(I, mh.matte);
         tmp = vsmul(op, tmp);
@@ -1133,16 +1105,16 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
           const bool inside = Q == 4 && origin && vdot(d, N) > 0.f;
           f.meta = ((unsigned)rm << 10) | (inside ? 0x200u : 0u) |
                    ((unsigned)(origin ? hit + 1 : 0) << 2) | (sigR ? 2u : 0u);
-#if RTG_BVH_INSIDE
           if constexpr (Q == 4 && IsBvhScene<Scene>::value) {
             // BVH scenes below 2048 spheres: the same for the sphere lists
             // (closest_enter_list), the sphere in bits 10..20 and rm in 21..31
+            // (internal reflections traced as entering rays: C5 -3.3 %,
+            // DESIGN.md §4 item 63)
             const bool in = sc.n < 2048u && guardOK && vdot(d, N) > 0.f;
             if (sc.n < 2048u)
               f.meta = ((unsigned)rm << 21) | ((unsigned)(in ? hit + 1 : 0) << 10) |
                        (in ? 0x200u : 0u) | (sigR ? 2u : 0u);
           }
-#endif
           fc.set(lv, f);
           if (sigR) {
             sc.count(kCntReflPush, 1);
@@ -1198,7 +1170,6 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
         o = r.ro; d = r.rd; I = r.rI; rm = (int)(f.meta >> 10);
         originH = (int)((f.meta >> 2) & 0x7Fu) - 1;
         if (Q == 4 && (f.meta & 0x200u)) enterH = originH;  // reflection back into it
-#if RTG_BVH_INSIDE
         if constexpr (Q == 4 && IsBvhScene<Scene>::value) {
           if (sc.n < 2048u) {
             rm = (int)(f.meta >> 21);
@@ -1206,7 +1177,6 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
             enterH = (f.meta & 0x200u) ? (int)((f.meta >> 10) & 0x7FFu) - 1 : -1;
           }
         }
-#endif
         if constexpr (kCL) ret = v3(0.f, 0.f, 0.f);           // raytrace_kernel.cl:845
         descend = true;
         break;
@@ -2053,7 +2023,6 @@ RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, in
     // one sphere and all show it drops the sphere from the loop (DESIGN.md §4
     // item 64).
     int skip = -1;
-#if RTG_SELF_SKIP
     if (hit >= 0) {
       const V3 e = vsub(q.o, hc);
       const float b = 2.0f * vdot(q.d, e);
@@ -2062,9 +2031,6 @@ RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, in
       const int h0 = sc.first_lane_i(hit);
       if (sc.all(skip == h0)) sel &= ~(1ull << h0);
     }
-#else
-    (void)hit; (void)hc; (void)hr2;
-#endif
     if (sc.all(q.fast)) return blocked_sel_fused<true>(sc, q, gap, sel, skip);
     return blocked_sel_fused<false>(sc, q, gap, sel, skip);
   }
@@ -2374,6 +2340,12 @@ RTG_HD bool primary_possible(const PrimBundle& b, V3 c, float iL, float sa, floa
   return cosPhi >= cosLim - 2.0e-3f;
 }
 
+// ---------------------------------------------------------------------------
+// From here to primary_bounds: forms that no kernel instantiates any more
+// (the tuned two-pass query, the query strategy selectors' values 0, 1 and 3,
+// the persistent and node pixel loops).  They run only in the host build,
+// where tests/test_oracle.py checks each against the oracle.
+//
 // Two-pass query for scenes of at most 64 spheres (the common case), tuned:
 //  * the geometry array is padded with NaN spheres to a multiple of 4 plus one
 //    extra group (PackedScene), so pass 1 has no remainder loop and can load
@@ -2797,6 +2769,7 @@ RTG_HD V3 shade_pixel_nodes(const Scene& sc, const Camera& cam, unsigned x, unsi
   return pix;
 }
 
+// ---------------------------------------------------------------------------
 // Bounds of the primary-ray directions of pixel (x, y) (all its samples):
 // X = (pxX + j*st)*asp, Y = pxY + i*st for i, j in [0, nAA).
 RTG_HD void primary_bounds(const Camera& cam, unsigned x, unsigned y, float& x0, float& x1,

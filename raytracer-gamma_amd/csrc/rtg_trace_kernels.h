@@ -13,8 +13,6 @@
 
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "rtg.h"
 #include "rtg_internal.h"
 #include "rtg_trace.h"
@@ -22,9 +20,6 @@
 namespace rtg {
 
 constexpr int kBlock = 256;
-
-// Materials staged in LDS when the table fits (n+1 records of 32 B).
-constexpr unsigned kLdsMatMax = 1024 + 1;  // => <= 48 KiB of LDS per workgroup
 
 // Device scene: geometry SoA-ish float4 {x, y, z, r*r}, (r + 1e-6f)^2, the
 // material table (n+1 x 8 floats; [n] = background), lights (m x 6 floats).
@@ -48,9 +43,6 @@ __device__ __forceinline__ cfloat_p fidx(cfloat_p p, unsigned i) {
 __device__ __forceinline__ cuint_p uidx(cuint_p p, unsigned i) {
   return (cuint_p)((const RTG_CONST char*)p + i * 4u);
 }
-#if defined(__HIP_DEVICE_COMPILE__)  // (one type on the host pass, where RTG_CONST is empty)
-__device__ __forceinline__ const float* fidx(const float* p, unsigned i) { return p + i; }
-#endif
 
 // Per-lane frame colours in LDS: level lv of thread t at lfr[lv * kBlock + t]
 // (16-byte records, so a wave's ds_read_b128 covers 1 KiB contiguously and is
@@ -66,30 +58,24 @@ struct LdsFrames {
 // limits their occupancy (7 frame levels + the traversal stack at S = 8: 5
 // waves per SIMD; 6 with this).  Level `top` holds a frame only while a node
 // of depth S - 1 (a leaf) is being shaded below it.
-// RTG_BVH_REG_LEVELS = 2 (A/B builds): the two deepest levels in VGPRs.
-#ifndef RTG_BVH_REG_LEVELS
-#define RTG_BVH_REG_LEVELS 1
-#endif
 template <int kThreads>
 struct LdsFramesTop {
   FrameC* base;  // already offset by threadIdx.x; levels 0 .. top-1
   int top;
-  mutable FrameC reg[RTG_BVH_REG_LEVELS];
+  mutable FrameC reg;
   __device__ __forceinline__ FrameC get(int lv) const {
     const FrameC l = base[(lv < top ? lv : top - 1) * kThreads];
-    if constexpr (RTG_BVH_REG_LEVELS == 1) return lv < top ? l : reg[0];
-    else return lv < top ? l : lv == top ? reg[0] : reg[1];
+    return lv < top ? l : reg;
   }
   __device__ __forceinline__ void set(int lv, const FrameC& v) const {
     if (lv < top) base[lv * kThreads] = v;
-    else if (RTG_BVH_REG_LEVELS == 1 || lv == top) reg[0] = v;
-    else reg[RTG_BVH_REG_LEVELS - 1] = v;
+    else reg = v;
   }
 };
 
 // kBvh: the kernel instantiation for BVH scenes (n > 64); without it the BVH
 // branches compile away, so small scenes keep the smaller, faster kernel.
-// kFuse: Scene::fuse bits (kFusePrim / kFuseCone / kFuseShadow, rtg_trace.h).
+// kFuse: Scene::fuse bits (kFusePrim / kFuseCone / kFuseShadow / kFuseEnter, rtg_trace.h).
 // kMasks: the scene has shadow/overlap and cone masks (every finite scene of
 // <= 64 spheres, rtg_scene_pack.h), so has_smask() / has_cone() are
 // compile-time true and the kernel keeps no run-time flags for them.
@@ -98,8 +84,8 @@ struct LdsFramesTop {
 // wave-level execution, on the wave's first active lane; flush_counts() adds
 // the wave's sums to KernelArgs::counts.  Control flow is the default
 // kernel's, so the counts are the default kernel's executed work.
-template <class MatPtr, bool kDiag = false, int kThreads = kBlock, bool kBvh = false,
-          int kFuse = 0, bool kMasks = false, bool kCount = false>
+template <bool kDiag = false, int kThreads = kBlock, bool kBvh = false, int kFuse = 0,
+          bool kMasks = false, bool kCount = false>
 struct DevScene {
   static constexpr int fuse = kFuse;
   static constexpr bool kIsBvh = kBvh;
@@ -117,28 +103,14 @@ struct DevScene {
   // probe slot, summed per wave and added to KernelArgs::diag at exit.
   mutable unsigned long long acc[kProbeSlots];
   mutable unsigned long long t0[kProbeSlots];
-  // RTG_DIAG_SPLIT builds (diagnostic A/B libraries only) re-assign slots 1
-  // and 4-6 to the finer regions kProbeSplit* (rtg_trace.h).
-  __device__ __forceinline__ static int probe_slot(int slot) {
-    if (RTG_DIAG_SPLIT) {
-      if (slot >= kProbeSplitBase) return slot - kProbeSplitBase;
-      if (slot == kProbeShadow || (slot >= kProbeMatte && slot <= kProbeUnwind)) return -1;
-      return slot;
-    }
-    return slot >= kProbeSplitBase ? -1 : slot;
-  }
-  __device__ __forceinline__ void probe_begin(int slot0) const {
-    const int slot = probe_slot(slot0);
-    if (slot < 0) return;
+  __device__ __forceinline__ void probe_begin(int slot) const {
     if constexpr (kDiag) {
       __builtin_amdgcn_sched_barrier(0);
       t0[slot] = __builtin_amdgcn_s_memtime();
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  __device__ __forceinline__ void probe_end(int slot0) const {
-    const int slot = probe_slot(slot0);
-    if (slot < 0) return;
+  __device__ __forceinline__ void probe_end(int slot) const {
     if constexpr (kDiag) {
       __builtin_amdgcn_sched_barrier(0);
       acc[slot] += __builtin_amdgcn_s_memtime() - t0[slot];
@@ -183,8 +155,8 @@ struct DevScene {
   }
   cfloat_p geom;      // n x {x, y, z, r*r}
   cfloat_p crad2;
-  MatPtr mats;        // LDS copy (float*) or the global table (cfloat_p)
-  const float4* lgeom;  // LDS copy of geom (or the global array when it does not fit)
+  cfloat_p mats;
+  const float4* lgeom;  // geom through a plain pointer, for per-lane (divergent) records
   cfloat_p lights;
   cuint_p smask;  // m x n x {lo, hi} shadow masks, or null
   cuint_p cone;   // n x kConeCells x {lo, hi} secondary-ray cone masks, or null
@@ -216,12 +188,12 @@ struct DevScene {
   __device__ __forceinline__ void sphere4_screen(unsigned i, V3* c, float* rs) const {
     sphere4(n4 + 4 + i, c, rs);
   }
+  __device__ __forceinline__ V3 sphere_screen(unsigned i, float& rs) const {
+    return sphere(n4 + 4 + i, rs);
+  }
   // ... and with the containment radius^2 (third part of geom).
   __device__ __forceinline__ void sphere4_contain(unsigned i, V3* c, float* cr) const {
     sphere4(2 * (n4 + 4) + i, c, cr);
-  }
-  __device__ __forceinline__ V3 sphere_screen(unsigned i, float& rs) const {
-    return sphere(n4 + 4 + i, rs);
   }
   // Fused record of sphere i (geom's fourth part, 32 bytes: one
   // s_load_dwordx8): centre, pass-1 screen radius^2, r^2 and the primary
@@ -429,7 +401,7 @@ struct DevScene {
   __device__ __forceinline__ uint64_t contain_union(int hit, bool ok) const {
     return mask_union(m, hit, ok);
   }
-  // Per-lane sphere record (divergent index): from the LDS copy.
+  // Per-lane sphere record (divergent index).
   __device__ __forceinline__ V3 sphere_lane(unsigned i, float& r2) const {
     const float4 g = lgeom[i];
     r2 = g.w;
@@ -443,7 +415,7 @@ struct DevScene {
   }
   // |0 - c_i|^2 - r_i^2: the c term of a ray from the origin (primary rays)
   __device__ __forceinline__ float origin_c(unsigned i) const { return *fidx(crad2, n + i); }
-  __device__ __forceinline__ Mat mat_at(decltype(mats) p) const {
+  __device__ __forceinline__ Mat mat_at(cfloat_p p) const {
     Mat r;
     r.matte = v3(p[0], p[1], p[2]);
     r.gloss = v3(p[3], p[4], p[5]);
@@ -453,9 +425,13 @@ struct DevScene {
   }
   // Material record i; when every active lane asks for the same record (the
   // background for primary misses, one sphere for a coherent wave) it comes
-  // through scalar loads instead of a per-lane gather.
+  // through scalar loads instead of a per-lane gather.  (i0 lives in a scope
+  // of its own: with it at function scope the compiler merges the two paths
+  // into one gather at a selected index, and the scalar loads are gone from
+  // every trace kernel.  After touching this, look for the s_load_dwordx2 of
+  // the record's words 6-7 in the kernels' assembly (`make asm`).)
   __device__ __forceinline__ Mat mat(int i) const {
-    if constexpr (std::is_same<MatPtr, cfloat_p>::value) {
+    {
       const int i0 = __builtin_amdgcn_readfirstlane(i);
       if (__ballot(i != i0) == 0ull) return mat_at(fidx(mats, 8u * (unsigned)i0));
     }
@@ -660,10 +636,9 @@ template <int S, int kVariant, bool kBvh = false>
 struct MinWaves {
   static constexpr int value =
       (kVariant == 120) ? 1  // counting build: its counters take registers
-      : (kBvh && (kVariant == 0 || kVariant == 50) && S > 6) ? 5 + RTG_BVH_REG_LEVELS
-      : (kVariant == 18 && S <= 6) ? 8
+      : (kBvh && (kVariant == 0 || kVariant == 50) && S > 6) ? 6
       : (kVariant == 0 && S <= 6) ? RTG_DEFAULT_MIN_WAVES
-      : ((kVariant % 100 == 0 || kVariant % 100 == 9 || kVariant >= 14) && S <= 6) ? 7 : 1;
+      : S <= 6 ? 7 : 1;
 };
 
 // Frame levels in LDS per lane: S - 1 ancestors (at least 1: the pixel sum
@@ -671,32 +646,19 @@ struct MinWaves {
 // (LdsFramesTop keeps the deepest in VGPRs).  launch_trace sizes the LDS with
 // the same rule.
 constexpr int frame_lds_levels(int S, bool bvh) {
-  return (S > 1 ? S - 1 : 1) -
-         (!bvh || S < 3 ? 0 : S < 4 ? 1 : RTG_BVH_REG_LEVELS);
+  return (S > 1 ? S - 1 : 1) - (!bvh || S < 3 ? 0 : 1);
 }
 
-// Workgroup prologue: the frame area and (kLds) the scene tables staged in LDS.
-template <int S, bool kLds, int kThreads, class Sc>
+// Workgroup prologue: the frame area in LDS and the scene tables (read from
+// global memory through the scalar and vector caches).
+template <int S, int kThreads, class Sc>
 __device__ __forceinline__ void stage_scene(const KernelArgs& a, Sc& sc) {
   extern __shared__ float4 lds4[];
   constexpr int NFL = frame_lds_levels(S, Sc::kIsBvh);
   sc.lfr = reinterpret_cast<FrameC*>(lds4) + threadIdx.x;
   sc.nfl = NFL;
-  float4* sceneLds = lds4 + NFL * kThreads;
-  if constexpr (kLds) {
-    float* lmats = reinterpret_cast<float*>(sceneLds);
-    const unsigned nm = (a.n + 1) * 8;
-    for (unsigned i = threadIdx.x; i < nm; i += kThreads) lmats[i] = a.mats[i];
-    float4* lg = sceneLds + (a.n + 1) * 2;
-    for (unsigned i = threadIdx.x; i < a.n4; i += kThreads)
-      lg[i] = reinterpret_cast<const float4*>(a.geom)[i];
-    __syncthreads();
-    sc.mats = lmats;
-    sc.lgeom = lg;
-  } else {
-    sc.mats = (cfloat_p)a.mats;
-    sc.lgeom = reinterpret_cast<const float4*>(a.geom);
-  }
+  sc.mats = (cfloat_p)a.mats;
+  sc.lgeom = reinterpret_cast<const float4*>(a.geom);
   sc.geom = (cfloat_p)a.geom;
   sc.crad2 = (cfloat_p)a.crad2;
   sc.lights = (cfloat_p)a.lights;
@@ -708,10 +670,9 @@ __device__ __forceinline__ void stage_scene(const KernelArgs& a, Sc& sc) {
   sc.capOff = (cuint_p)a.capOff;
   sc.ovRec = (cfloat_p)a.ovRec;
   sc.ovOff = (cuint_p)a.ovOff;
-  // BVH scenes: 64 stack entries per wave after the frames and scene tables
-  // (the launcher adds them to the LDS size).
-  sc.bvhStk = reinterpret_cast<int*>(sceneLds + (kLds ? (a.n + 1) * 2 + a.n4 : 0)) +
-              (threadIdx.x >> 6) * 64;
+  // BVH scenes: 64 stack entries per wave after the frames (the launcher adds
+  // them to the LDS size).
+  sc.bvhStk = reinterpret_cast<int*>(lds4 + NFL * kThreads) + (threadIdx.x >> 6) * 64;
   sc.n = a.n;
   sc.m = a.m;
   sc.n4 = a.n4;
@@ -723,7 +684,6 @@ template <int S, int kVariant, class Sc>
 __device__ __forceinline__ void trace_tile(const KernelArgs& a, Sc& sc, unsigned tx,
                                            unsigned ty) {
   constexpr bool kDiag = kVariant >= 100;
-  constexpr int kBase = kDiag ? kVariant - 100 : kVariant;
   const unsigned lane = threadIdx.x & 63u;
   const unsigned x = tx * 8u + (lane & 7u);
   const unsigned lr = ty * 8u + (lane >> 3);
@@ -737,25 +697,23 @@ __device__ __forceinline__ void trace_tile(const KernelArgs& a, Sc& sc, unsigned
   // per lane against that bundle, then a ballot (see primary_possible).
   uint64_t primSel = ~0ull;
   bool usePrim = false;
-  if constexpr (kBase == 0 || kBase == 8 || kBase == 9 || kBase == 59) {
-    if (a.n <= 64) {
-      float x0 = 3.0e38f, x1 = -3.0e38f, y0 = 3.0e38f, y1 = -3.0e38f;
-      if (valid) primary_bounds(a.cam, x, gy, x0, x1, y0, y1);
-      for (int off = 32; off > 0; off >>= 1) {
-        x0 = fminf(x0, __shfl_xor(x0, off));
-        x1 = fmaxf(x1, __shfl_xor(x1, off));
-        y0 = fminf(y0, __shfl_xor(y0, off));
-        y1 = fmaxf(y1, __shfl_xor(y1, off));
-      }
-      const PrimBundle pb = primary_bundle(x0, x1, y0, y1, a.cam.zoom);
-      bool possible = false;
-      if (lane < a.n) {
-        const float4 g = sc.lgeom[lane];
-        possible = sc.prim_possible(pb, lane, v3(g.x, g.y, g.z));
-      }
-      primSel = __ballot(possible);
-      usePrim = true;
+  if (a.n <= 64) {
+    float x0 = 3.0e38f, x1 = -3.0e38f, y0 = 3.0e38f, y1 = -3.0e38f;
+    if (valid) primary_bounds(a.cam, x, gy, x0, x1, y0, y1);
+    for (int off = 32; off > 0; off >>= 1) {
+      x0 = fminf(x0, __shfl_xor(x0, off));
+      x1 = fmaxf(x1, __shfl_xor(x1, off));
+      y0 = fminf(y0, __shfl_xor(y0, off));
+      y1 = fmaxf(y1, __shfl_xor(y1, off));
     }
+    const PrimBundle pb = primary_bundle(x0, x1, y0, y1, a.cam.zoom);
+    bool possible = false;
+    if (lane < a.n) {
+      const float4 g = sc.lgeom[lane];
+      possible = sc.prim_possible(pb, lane, v3(g.x, g.y, g.z));
+    }
+    primSel = __ballot(possible);
+    usePrim = true;
   }
   if (!valid) return;
   V3 pix;
@@ -764,17 +722,8 @@ __device__ __forceinline__ void trace_tile(const KernelArgs& a, Sc& sc, unsigned
     for (int k = 0; k < kProbeSlots; ++k) sc.acc[k] = 0;
     tk0 = __builtin_amdgcn_s_memtime();
   }
-  if constexpr (kBase == 0 || kBase == 9)
-    pix = shade_pixel<S, 2, true>(sc, a.cam, x, gy, usePrim, primSel);
-  else if constexpr (kBase == 59)  // OpenCL semantics (rtg_context_set_semantics)
-    pix = shade_pixel<S, 2, true, true>(sc, a.cam, x, gy, usePrim, primSel);
-  else if constexpr (kBase == 6) pix = shade_pixel<S, 2, true>(sc, a.cam, x, gy);
-  else if constexpr (kBase == 8) pix = shade_pixel<S, 3, true>(sc, a.cam, x, gy, usePrim, primSel);
-  else if constexpr (kBase == 5) pix = shade_pixel<S, 2, false>(sc, a.cam, x, gy);
-  else if constexpr (kBase == 1) pix = shade_pixel<S, 0>(sc, a.cam, x, gy);
-  else if constexpr (kBase == 2) pix = shade_pixel_persistent<S, 2>(sc, a.cam, x, gy);
-  else if constexpr (kBase == 3) pix = shade_pixel_persistent<S, 1>(sc, a.cam, x, gy);
-  else pix = shade_pixel_nodes<S, 2>(sc, a.cam, x, gy);
+  // 59: the OpenCL kernel's semantics (rtg_context_set_semantics)
+  pix = shade_pixel<S, 2, true, kVariant == 59>(sc, a.cam, x, gy, usePrim, primSel);
   if constexpr (kDiag) {
     sc.acc[kProbeTotal] = __builtin_amdgcn_s_memtime() - tk0;
     // one wave-level add per slot (values are wave-uniform: s_memtime is scalar)
@@ -819,23 +768,22 @@ __device__ __forceinline__ void record_wave_end(const KernelArgs& a, size_t w, u
 
 // Tile kernels: one 8 x 8 pixel tile per wave, all samples of a pixel in its
 // lane; a workgroup is 2 x 2 tiles.
-template <int S, bool kLds, int kVariant, bool kBvh = false>
+template <int S, int kVariant, bool kBvh = false>
 __global__ __launch_bounds__(kBlock, (MinWaves<S, kVariant>::value))
 void trace_kernel(const KernelArgs a) {
-  // LDS image: per-lane frame colours ((S-1) x threads x 16 B), then, when
-  // kLds, the material table (n+1) x 8 floats and the geometry n x float4.
+  // LDS image: per-lane frame colours ((S-1) x threads x 16 B), then (BVH
+  // scenes) the waves' traversal stacks.
   constexpr int kThreads = kBlock;
   constexpr unsigned TW = 2u, TH = 2u;
-  typedef typename std::conditional<kLds, const float*, cfloat_p>::type MatPtr;
-  DevScene<MatPtr, (kVariant >= 100), kThreads, kBvh> sc;
-  stage_scene<S, kLds, kThreads>(a, sc);
+  DevScene<(kVariant >= 100), kThreads, kBvh> sc;
+  stage_scene<S, kThreads>(a, sc);
   const unsigned wave = threadIdx.x >> 6;
   const unsigned t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
   trace_tile<S, kVariant>(a, sc, blockIdx.x * TW + (wave % TW), blockIdx.y * TH + (wave / TW));
   record_wave(a, t0, ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (kThreads / 64) + wave);
 }
 
-// Sample-parallel form (variant 14): each lane traces ONE primary sample, so
+// Sample-parallel form: each lane traces ONE primary sample, so
 // a wave takes floor(64 / nAA^2) consecutive pixels (7 at 3 x 3) with their
 // samples in lane order, instead of 64 pixels x all their samples.  A heavy
 // region (deep refraction trees) is then spread over nAA^2 times as many
@@ -845,7 +793,7 @@ void trace_kernel(const KernelArgs a) {
 // Each pixel's sum is formed in the reference's sample order
 // (main.cpp:411-452: pix += c_s * inv for s = 0 .. nAA^2-1) by its first lane
 // from the other lanes' values (ds_bpermute moves the bits unchanged).
-// Requires nAA^2 <= 64; the host launches the default kernel otherwise.
+// Requires nAA^2 <= 64; the host launches the tile kernel otherwise.
 // Pixel group gw (floor(64 / nAA^2) consecutive pixels of the shard's local
 // rows, all their samples) traced by one wave, entered converged.
 // hasSel: the cull pass already gave the group's primary-ray sphere subset
@@ -862,7 +810,7 @@ __device__ __forceinline__ const RTG_CONST KernelArgs* kargs() {
   return p;
 }
 
-template <int S, int Q, bool kDiag, class Sc, bool kShfl = false, bool kCL = false>
+template <int S, bool kDiag, class Sc, bool kCL = false>
 __device__ __forceinline__ void trace_group(const KernelArgs& a0, Sc& sc, size_t gw,
                                             bool hasSel = false, uint64_t gsel = 0) {
   (void)a0;
@@ -909,7 +857,7 @@ __device__ __forceinline__ void trace_group(const KernelArgs& a0, Sc& sc, size_t
     // lane nAA(nAA-1)).  Otherwise reduce across the wave.
     const unsigned nv = (unsigned)((total - p0 < PPW) ? (total - p0) : PPW);  // >= 1
     const bool oneRow = col0 + nv - 1 < a.W;
-    if (oneRow && !kShfl) {
+    if (oneRow) {
       x0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rx), 0));
       x1 = __int_as_float(
           __builtin_amdgcn_readlane(__float_as_int(rx), (int)((nv - 1) * SP + nAA - 1)));
@@ -948,7 +896,7 @@ __device__ __forceinline__ void trace_group(const KernelArgs& a0, Sc& sc, size_t
 #else
   if (valid) {
     sc.count(kUSample, 1);
-    c = trace_sample<S, Q, kCL>(sc, dir, sc.frames(), usePrim, primSel);
+    c = trace_sample<S, 4, kCL>(sc, dir, sc.frames(), usePrim, primSel);
     c = vsmul(kargs()->cam.inv, c);
   }
 #endif
@@ -962,28 +910,19 @@ __device__ __forceinline__ void trace_group(const KernelArgs& a0, Sc& sc, size_t
   // and each pixel's first lane reads its nAA^2 samples back in order.
   const unsigned base = pl * SP;
   V3 pix = v3(0.f, 0.f, 0.f);
-  if constexpr (kShfl) {  // variant 19: cross-lane reads instead of LDS
+  FrameC* slot0 = sc.lfr - (threadIdx.x & 63u);  // this wave's level-0 slots
+  sc.lfr->cx = c.x;
+  sc.lfr->cy = c.y;
+  sc.lfr->cz = c.z;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (s == 0) {
     for (unsigned k = 0; k < SP; ++k) {
-      const int src = (int)((base + k) & 63u);
-      pix.x = pix.x + __shfl(c.x, src);
-      pix.y = pix.y + __shfl(c.y, src);
-      pix.z = pix.z + __shfl(c.z, src);
-    }
-  } else {
-    FrameC* slot0 = sc.lfr - (threadIdx.x & 63u);  // this wave's level-0 slots
-    sc.lfr->cx = c.x;
-    sc.lfr->cy = c.y;
-    sc.lfr->cz = c.z;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (s == 0) {
-      for (unsigned k = 0; k < SP; ++k) {
-        const FrameC& f = slot0[(base + k) & 63u];
-        pix.x = pix.x + f.cx;
-        pix.y = pix.y + f.cy;
-        pix.z = pix.z + f.cz;
-      }
+      const FrameC& f = slot0[(base + k) & 63u];
+      pix.x = pix.x + f.cx;
+      pix.y = pix.y + f.cy;
+      pix.z = pix.z + f.cz;
     }
   }
   if (valid && s == 0) {
@@ -1006,57 +945,32 @@ struct IsDiag {
   static constexpr bool value = V >= 100 && V != 120;
 };
 
-// Fused query forms per variant (Scene::fuse bits, rtg_trace.h): every
-// sample-kernel variant except 23 (the two-pass queries, for A/B).
-template <int kVariant>
-struct FuseOf {
-  static constexpr int value =
-      (kVariant == 23) ? 0 : (kFusePrim | kFuseCone | kFuseShadow | kFuseEnter);
-};
-
-template <int kVariant>
-struct GroupsPerWave {
-  static constexpr int value = (kVariant == 21) ? 4 : 1;
-};
-
-template <int kVariant>
-struct SampleThreads {
-  static constexpr int value = (kVariant == 14) ? kBlock : 64;
-};
-
-// One launch, one pixel group per wave: one-wave workgroups (default), or
-// four-wave ones (variant 14).  kList: the compacted launch (the launcher
-// guarantees a.groupList): the listed groups, dealt round-robin to the waves,
-// with the cull pass's sphere masks; otherwise K consecutive groups per wave.
-// Separate instantiations keep each loop's registers to itself.
+// One launch of one-wave workgroups.  kList: the compacted launch (the
+// launcher guarantees a.groupList): the listed groups, dealt round-robin to
+// the waves, with the cull pass's sphere masks; otherwise one pixel group per
+// wave.  Separate instantiations keep each loop's registers to itself.
 // kMasks (compacted default kernel only): the launcher guarantees the
 // scene's shadow/overlap and cone masks (DevScene).
 // The body of the sample kernels (one per launch kind below).
-template <int S, bool kLds, int kVariant, bool kBvh, bool kList, bool kMasks>
+template <int S, int kVariant, bool kBvh, bool kList, bool kMasks>
 __device__ __forceinline__ void trace_samples_body(const KernelArgs& a) {
-  constexpr int kThreads = SampleThreads<kVariant>::value;
-  typedef typename std::conditional<kLds, const float*, cfloat_p>::type MatPtr;
+  constexpr int kThreads = 64;
   constexpr bool kCount = IsCount<kVariant>::value;
-  DevScene<MatPtr, IsDiag<kVariant>::value, kThreads, kBvh, FuseOf<kVariant>::value, kMasks,
-           kCount>
-      sc;
+  // every sample kernel runs the fused query forms
+  constexpr int kFuse = kFusePrim | kFuseCone | kFuseShadow | kFuseEnter;
+  DevScene<IsDiag<kVariant>::value, kThreads, kBvh, kFuse, kMasks, kCount> sc;
   sc.count_reset();
   sc.count(kUWave, 1);  // every wave, those past the listed groups included
   const unsigned t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
-  stage_scene<S, kLds, kThreads>(a, sc);
-  if constexpr (kVariant == 20) sc.cone = nullptr;  // A/B: no secondary-ray cone cull
+  stage_scene<S, kThreads>(a, sc);
   // the wave's index, wave-uniform (readfirstlane: an SGPR, so the list and
   // mask reads below are scalar loads and the group set-up is scalar work)
   const size_t gw = (size_t)blockIdx.x * (kThreads / 64) +
                     (unsigned)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // variant 15: the previous default (shadow rays screening every sphere)
-  // variant 21: kGroupsPerWave consecutive pixel groups per wave, in turn
-  constexpr int Q = (kVariant == 15) ? 2 : 4;
   constexpr bool kDiag = IsDiag<kVariant>::value;
   unsigned tag = 0;  // timeline tag (record_wave)
   if constexpr (kList) {
     const RTG_CONST unsigned* list = (const RTG_CONST unsigned*)a.groupList;
-    // variant 24: the wave recomputes its primary cull (no cull-pass masks)
     const RTG_CONST unsigned long long* gsel = (const RTG_CONST unsigned long long*)a.groupSel;
     // List position of index idx: partition idx % kListParts (nPersist is a
     // multiple of kListParts, so a wave stays in one partition), its run-order
@@ -1102,8 +1016,7 @@ __device__ __forceinline__ void trace_samples_body(const KernelArgs& a) {
       const unsigned at = pos(idx);
       if (at == ~0u) break;
       const unsigned g = __builtin_amdgcn_readfirstlane(list[at]);
-      trace_group<S, Q, kDiag, decltype(sc), (kVariant == 19), (kVariant == 50)>(
-          a, sc, g, kVariant != 24, kVariant != 24 ? (uint64_t)gsel[at] : 0ull);
+      trace_group<S, kDiag, decltype(sc), (kVariant == 50)>(a, sc, g, true, (uint64_t)gsel[at]);
       const unsigned now = (unsigned)__builtin_amdgcn_s_memrealtime();
       const RTG_CONST KernelArgs* b = kargs();
       if (b->groupCost != nullptr && (threadIdx.x & 63u) == 0)
@@ -1117,21 +1030,17 @@ __device__ __forceinline__ void trace_samples_body(const KernelArgs& a) {
       tag = ((unsigned)__builtin_popcountll(gsel[at]) & 127u) | ((g < 0x1FFFFFu ? g : 0x1FFFFFu) << 7);
     }
   } else {
-    constexpr int K = GroupsPerWave<kVariant>::value;
-    for (int k = 0; k < K; ++k)
-      trace_group<S, Q, kDiag, decltype(sc), (kVariant == 19), (kVariant == 50)>(a, sc,
-                                                                                 gw * K + k);
+    trace_group<S, kDiag, decltype(sc), (kVariant == 50)>(a, sc, gw);
   }
   if constexpr (kCount) sc.flush_counts(kargs()->counts);
   if constexpr (kList) record_wave_end(a, gw, tag);
   else record_wave(a, t0, gw);
 }
 
-template <int S, bool kLds, int kVariant, bool kBvh = false, bool kList = false,
-          bool kMasks = false>
-__global__ __launch_bounds__(SampleThreads<kVariant>::value, (MinWaves<S, kVariant, kBvh>::value))
+template <int S, int kVariant, bool kBvh = false, bool kList = false, bool kMasks = false>
+__global__ __launch_bounds__(64, (MinWaves<S, kVariant, kBvh>::value))
 void trace_samples_kernel(const KernelArgs a) {
-  trace_samples_body<S, kLds, kVariant, kBvh, kList, kMasks>(a);
+  trace_samples_body<S, kVariant, kBvh, kList, kMasks>(a);
 }
 
 // The compacted default kernel of a masked scene with an SGPR budget
@@ -1148,51 +1057,28 @@ void trace_samples_kernel(const KernelArgs a) {
 template <int S>
 __global__ __launch_bounds__(64, 8) __attribute__((amdgpu_num_sgpr(RTG_NUM_SGPR)))
 void trace_samples_kernel_masked(const KernelArgs a) {
-  trace_samples_body<S, false, 0, false, true, true>(a);
+  trace_samples_body<S, 0, false, true, true>(a);
 }
 
 // Kernel variants (rtg_launch_opts.variant; results identical, speed differs):
 //   0 (default) sample-parallel: one primary sample per lane, one-wave
 //     workgroups, scene tables read from global memory (trace_samples_kernel),
-//     fused sphere queries (FuseOf);
+//     fused sphere queries (kFuse*, rtg_trace.h);
 //     compacted launch for scenes of <= 64 spheres (cull_groups_kernel,
 //     rtg_kernel.hip); falls back to 9 when nAA > 8
-//   1 per-sample recursion, one sphere per step (first kernel)
-//   2 one-query-per-iteration state machine + candidate masks
-//   3 one-query-per-iteration state machine, four spheres per step
-//   4 node-persistent: samples chained in one node loop + candidate masks
-//   5 as 9 but frame colours in private memory instead of LDS
-//   6 as 9 without the per-wave primary-ray sphere cull
-//   (7, a converged loop with per-query bundle culls, was removed: DESIGN.md)
-//   8 as 9 with the tuned two-pass query (prefetched groups, uniform quotient path)
 //   9 tile kernel: an 8 x 8 pixel tile per wave, each lane all samples of its
 //     pixel (per-sample recursion + two-pass candidate-mask queries + per-wave
 //     primary cull), 7 waves/SIMD; the default until the sample-parallel kernel
-//   14 as 0 with four-wave workgroups
-//   15 as 0 with shadow rays screening every sphere (no shadow masks)
-//   18 as 0 built for 8 waves per SIMD (<= 64 VGPRs)
-//   19 as 0 with shuffle reductions for the cull bounds and the pixel sum
-//   20 as 0 without the secondary-ray cone cull (cone_masks)
-//   21 as 0 with four consecutive pixel groups per wave
-//   22 as 0 without the compacted launch (one wave per pixel group, every
-//      group traced: the default before cull_groups_kernel)
-//   23 as 0 with the two-pass queries (a screen loop, then a per-lane
-//      candidate loop with per-lane record gathers) for primary, cone-culled,
-//      shadow and entering rays: the default before the fused queries (FuseOf)
-//   24 as 0 with each wave computing its primary-ray cull instead of taking
-//      the cull pass's per-group sphere mask
 //   50 / 59: 0 / 9 with the OpenCL kernel's semantics (RTG_SEMANTICS_OPENCL;
 //     chosen by rtg_context_set_semantics, not by the variant knob)
-//   (19-21, persistent sample kernels with static / atomic-queue dealing of
-//    pixel groups, were removed: register spills made them slower)
-//   (16, 17: as 0 with the materials/geometry staged in LDS per workgroup,
-//    two- and one-wave workgroups; measured slower than the scalar-cache
-//    reads in rounds 1-2 and removed in round 6: DESIGN.md §6)
-//   (10-12: work-queue and workgroup-size trials of the tile kernel, removed: DESIGN.md)
-//   100 + v: diagnostic build of v (s_memtime probes, rtg_diag_read); 100 = 9,
-//     110 = the default sample kernel (0)
+//   100, 110: diagnostic builds (s_memtime probes, rtg_diag_read) of 9 and of
+//     the compacted 0
 //   120 the default kernel's executed-work counting build (rtg_diag_counts):
 //     same control flow, unit counters per wave (DevScene kCount)
+// Retired after losing their measurements: 1-6, 8, 14, 15,
+// 18-24, 104 and 108, last held by revision f97a834; for a same-box comparison
+// `AB=1 tools/ab_build.sh f97a834 ab` builds a library with all of them.  (The
+// host build of tests/hostsim still runs the traversal forms of 1-5, 8, 15, 23.)
 // The one table of valid variants and their kernel kind; anything else is
 // rejected (rtg_set_launch_opts, RTG_VARIANT) and trace_fn returns nullptr.
 // kSemantic variants change results and are only chosen through
@@ -1203,27 +1089,10 @@ struct VariantInfo {
   int kind;
   bool semantic;
 };
-// The shipped library holds the default kernel (0), its tile fallback for
-// nAA > 8 (9), the OpenCL-semantics forms (50, 59), the diagnostic builds of
-// 9 and 0 (100, 110) and the counting build (120).  The A/B variants, each
-// measured and not adopted, are compiled only into A/B
-// libraries (`make AB=1`, -DRTG_AB_VARIANTS=1).
-#ifndef RTG_AB_VARIANTS
-#define RTG_AB_VARIANTS 0
-#endif
 constexpr VariantInfo kVariants[] = {
     {0, kVariantSample, false},  {9, kVariantTile, false},    {50, kVariantSample, true},
     {59, kVariantTile, true},    {100, kVariantTile, false},  {110, kVariantSample, false},
     {120, kVariantSample, false},
-#if RTG_AB_VARIANTS
-    {1, kVariantTile, false},    {2, kVariantTile, false},    {3, kVariantTile, false},
-    {4, kVariantTile, false},    {5, kVariantTile, false},    {6, kVariantTile, false},
-    {8, kVariantTile, false},    {14, kVariantSample, false}, {15, kVariantSample, false},
-    {18, kVariantSample, false},
-    {19, kVariantSample, false}, {20, kVariantSample, false}, {21, kVariantSample, false},
-    {22, kVariantSample, false}, {23, kVariantSample, false}, {24, kVariantSample, false},
-    {104, kVariantTile, false},  {108, kVariantTile, false},
-#endif
 };
 inline const VariantInfo* variant_info(int v) {
   for (const VariantInfo& i : kVariants)
@@ -1231,111 +1100,69 @@ inline const VariantInfo* variant_info(int v) {
   return nullptr;
 }
 
-// list: the compacted launch (kList instantiations exist for the one-wave
-// sample kernels that the launcher compacts, CompactVariant).
-// (launch_trace compacts every one-wave sample kernel but 21 and 22); a list
-// request for any other variant gets nullptr, an error, never a wrong frame.
-template <int V>
-struct CompactVariant {
-  static constexpr bool value = V == 0 || V == 15 || V == 18 || V == 19 || V == 20 ||
-                                V == 23 || V == 24 || V == 50 || V == 110 || V == 120;
-};
 // list: 0 the direct launch, 1 the compacted launch, 2 the compacted launch
-// of a scene with masks (kMasks instantiation of the default kernel).
+// of a scene with masks (kMasks instantiation of the default kernel).  Only
+// the sample kernels 0, 50, 110 and 120 have compacted forms; a list request
+// for any other variant gets nullptr, an error, never a wrong frame.
 template <int S, int V>
-static TraceFn trace_fn_v(bool lds, int list) {
-  if (list && !CompactVariant<V>::value) return nullptr;
+static TraceFn trace_fn_v(int list) {
   if constexpr (V == 0) {
     // S <= 6: the SGPR-budgeted 8-wave kernel; deeper stacks hold more LDS
     // per wave than 8 waves per SIMD admit anyway
     if (list == 2) {
       if constexpr (S <= 6) return trace_samples_kernel_masked<S>;
-      else return trace_samples_kernel<S, false, 0, false, true, true>;
+      else return trace_samples_kernel<S, 0, false, true, true>;
     }
-    return list ? trace_samples_kernel<S, false, 0, false, true> : trace_samples_kernel<S, false, 0>;
+    return list ? trace_samples_kernel<S, 0, false, true> : trace_samples_kernel<S, 0>;
   } else if constexpr (V == 120) {  // the counting build of exactly the masked kernel
-    return list == 2 ? trace_samples_kernel<S, false, 120, false, true, true> : nullptr;
+    return list == 2 ? trace_samples_kernel<S, 120, false, true, true> : nullptr;
   } else if constexpr (V == 110) {  // the probe build of the compacted default kernel
-    return list ? trace_samples_kernel<S, false, 110, false, true> : nullptr;
-  } else if constexpr (V == 14) {
-    return lds ? trace_samples_kernel<S, true, V> : trace_samples_kernel<S, false, V>;
-  } else if constexpr (CompactVariant<V>::value) {
-    return list ? trace_samples_kernel<S, false, V, false, true> : trace_samples_kernel<S, false, V>;
-  } else if constexpr (V == 21 || V == 22) {
-    return trace_samples_kernel<S, false, V>;
-  } else if constexpr (V == 9 || V == 59 || V == 100) {
-    (void)lds;  // the shipped tile kernels read the scene from global memory
-    return trace_kernel<S, false, V>;
-  } else {
-    return lds ? trace_kernel<S, true, V> : trace_kernel<S, false, V>;
+    return list ? trace_samples_kernel<S, 110, false, true> : nullptr;
+  } else if constexpr (V == 50) {
+    return list ? trace_samples_kernel<S, 50, false, true> : trace_samples_kernel<S, 50>;
+  } else {  // the tile kernels 9, 59, 100
+    return list ? nullptr : trace_kernel<S, V>;
   }
 }
-// BVH scenes: the default kernels (and their diagnostic and OpenCL-semantics
-// forms, the counting build) and the nAA > 8 tile fallback have kBvh
-// instantiations; 59, 100 and the A/B variants run BVH scenes through their
-// flat queries (same results, slower); the probe build 110 has none (an
-// error on BVH scenes).  The launcher sizes a kBvh
-// kernel's LDS by frame_lds_levels(S, true), so this list and
+// BVH scenes: the default kernels (and their OpenCL-semantics form, the
+// counting build) and the nAA > 8 tile fallback have kBvh instantiations; 59
+// and 100 run BVH scenes through their flat queries (same results, slower);
+// the probe build 110 has none (an error on BVH scenes).  The launcher sizes a
+// kBvh kernel's LDS by frame_lds_levels(S, true), so this list and
 // has_bvh_kernel() must agree.
 inline bool has_bvh_kernel(int variant) {
-  return variant == 0 || variant == 50 || variant == 120 || variant == 9 ||
-         (RTG_AB_VARIANTS && variant == 110);
+  return variant == 0 || variant == 50 || variant == 120 || variant == 9;
 }
 template <int S>
-static TraceFn trace_fn_bvh(bool lds, int variant) {
+static TraceFn trace_fn_bvh(int variant) {
   switch (variant) {
-    case 0: return trace_samples_kernel<S, false, 0, true>;
-    case 50: return trace_samples_kernel<S, false, 50, true>;
-    case 120: return trace_samples_kernel<S, false, 120, true>;
-    case 9: (void)lds; return trace_kernel<S, false, 9, true>;
-#if RTG_AB_VARIANTS
-    case 110: return trace_samples_kernel<S, false, 110, true>;  // probe build, A/B libraries
-#endif
+    case 0: return trace_samples_kernel<S, 0, true>;
+    case 50: return trace_samples_kernel<S, 50, true>;
+    case 120: return trace_samples_kernel<S, 120, true>;
+    case 9: return trace_kernel<S, 9, true>;
     default: return nullptr;
   }
 }
 template <int S>
-static TraceFn trace_fn(bool lds, int variant, bool bvh, int list) {
+static TraceFn trace_fn(int variant, bool bvh, int list) {
   if (bvh) {
     if (list) return nullptr;  // BVH scenes (n > 64) are never compacted
-    if (TraceFn f = trace_fn_bvh<S>(lds, variant)) return f;
+    if (TraceFn f = trace_fn_bvh<S>(variant)) return f;
   }
   switch (variant) {
-    case 0: return trace_fn_v<S, 0>(lds, list);
-    case 9: return trace_fn_v<S, 9>(lds, list);
-    case 50: return trace_fn_v<S, 50>(lds, list);
-    case 59: return trace_fn_v<S, 59>(lds, list);
-    case 100: return trace_fn_v<S, 100>(lds, list);
-    case 110: return trace_fn_v<S, 110>(lds, list);
-    case 120: return trace_fn_v<S, 120>(lds, list);
-#if RTG_AB_VARIANTS
-    case 1: return trace_fn_v<S, 1>(lds, list);
-    case 2: return trace_fn_v<S, 2>(lds, list);
-    case 3: return trace_fn_v<S, 3>(lds, list);
-    case 4: return trace_fn_v<S, 4>(lds, list);
-    case 5: return trace_fn_v<S, 5>(lds, list);
-    case 6: return trace_fn_v<S, 6>(lds, list);
-    case 8: return trace_fn_v<S, 8>(lds, list);
-    case 14: return trace_fn_v<S, 14>(lds, list);
-    case 15: return trace_fn_v<S, 15>(lds, list);
-    case 16: return trace_fn_v<S, 16>(lds, list);
-    case 17: return trace_fn_v<S, 17>(lds, list);
-    case 18: return trace_fn_v<S, 18>(lds, list);
-    case 19: return trace_fn_v<S, 19>(lds, list);
-    case 20: return trace_fn_v<S, 20>(lds, list);
-    case 21: return trace_fn_v<S, 21>(lds, list);
-    case 22: return trace_fn_v<S, 22>(lds, list);
-    case 23: return trace_fn_v<S, 23>(lds, list);
-    case 24: return trace_fn_v<S, 24>(lds, list);
-    case 104: return trace_fn_v<S, 104>(lds, list);
-    case 108: return trace_fn_v<S, 108>(lds, list);
-#endif
+    case 0: return trace_fn_v<S, 0>(list);
+    case 9: return trace_fn_v<S, 9>(list);
+    case 50: return trace_fn_v<S, 50>(list);
+    case 59: return trace_fn_v<S, 59>(list);
+    case 100: return trace_fn_v<S, 100>(list);
+    case 110: return trace_fn_v<S, 110>(list);
+    case 120: return trace_fn_v<S, 120>(list);
     default: return nullptr;  // not in kVariants
   }
 }
 
 // One per stack size, defined in rtg_trace_s<S>.hip.
-#define RTG_DECL(k) TraceFn trace_fn_s##k(bool lds, int variant, bool bvh, int list);
+#define RTG_DECL(k) TraceFn trace_fn_s##k(int variant, bool bvh, int list);
 RTG_DECL(1) RTG_DECL(2) RTG_DECL(3) RTG_DECL(4) RTG_DECL(5) RTG_DECL(6) RTG_DECL(7)
 RTG_DECL(8) RTG_DECL(9) RTG_DECL(10) RTG_DECL(11) RTG_DECL(12) RTG_DECL(13)
 RTG_DECL(14) RTG_DECL(15) RTG_DECL(16)

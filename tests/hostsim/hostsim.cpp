@@ -275,7 +275,8 @@ extern "C" int hostsim_render_rows(const rtg_sphere* spheres, unsigned n,
   sc.smask = ps.smask.empty() ? nullptr : ps.smask.data();
   sc.cone = ps.cone.empty() ? nullptr : ps.cone.data();
   sc.prim = ps.prim.data();
-  // the kernel's FuseOf (rtg_trace_kernels.h): sample-kernel variants but 23
+  // the sample kernels' fused queries (trace_samples_body, rtg_trace_kernels.h);
+  // 23 and the tile forms run the two-pass queries
   sc.fuse = (g_variant == 0 || g_variant == 15 || g_variant == 50)
                 ? (rtg::kFusePrim | rtg::kFuseCone | rtg::kFuseShadow | rtg::kFuseEnter)
                 : 0;

@@ -4,6 +4,9 @@
 # for same-box A/B runs:   RTG_LIB=$PWD/ab/librtg_NAME.so python bench.py ...
 # Compiler-setting trials: EXTRA="-O2" tools/ab_build.sh HEAD o2 (EXTRA is
 # appended to the Makefile's HIPFLAGS).
+# AB=1 is passed on for revisions up to f97a834, whose Makefile builds the
+# since-retired A/B kernel variants with it (AB=1 tools/ab_build.sh f97a834 ab);
+# later Makefiles ignore it.
 set -euo pipefail
 REV=${1:?revision}
 NAME=${2:-$REV}
