@@ -20,6 +20,8 @@
  *   (8-GPU node, SURVEY.md §8e: none in the reference) rtg_render_multi (RCCL gather)
  *   (primary visibility per pixel: none in the reference) rtg_gbuffer / rtg_gbuffer_device /
  *                                                      rtg_gbuffer_host
+ *   calcIntersection / hasClearLineOfSight for a       rtg_intersect[_device|_host] /
+ *     caller's own rays  raytracer.h:145-194, 272-309  rtg_visible[_device|_host]
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
  *   output_device_info  device_info.cpp:30             rtg_device_info
  *   parseArguments --list/--device  device_picker.h:70 rtg_device_count / device index args
@@ -239,6 +241,75 @@ int rtg_gbuffer(int device, const rtg_sphere* spheres, unsigned sphNum, unsigned
 int rtg_gbuffer_host(const rtg_sphere* spheres, unsigned sphNum, unsigned width,
                      unsigned height, float zoom, float aliasFactor, rtg_gbuf_px* dstHost,
                      int nthreads);
+
+/* ---- batch ray queries: closest hit and line of sight for arbitrary rays ----
+ * The two scene queries of the reference, calcIntersection (raytracer.h:
+ * 145-194) and hasClearLineOfSight (raytracer.h:272-309), for a buffer of the
+ * caller's own rays against the resident scene: picking from another camera,
+ * ambient occlusion, light baking, collision and visibility tests, or one
+ * secondary ray of a bad pixel.  A buffer of rays goes in, a buffer of
+ * results comes out, bit for bit what the reference's functions return.
+ *
+ * rtg_intersect: ray k gets calcIntersection(spheres, n, &ray) in the same
+ * float operations: the raySphere root test with the 1e-5 / 10000 window,
+ * minT starting at 1000, strict <, the first index winning ties.  `dir` is
+ * used as given: it is not normalised, and any length is legal.  `point` and
+ * `normal` are computed for the final winner only (the reference recomputes
+ * them at each improvement, so its last values are these).
+ *
+ * rtg_visible: out[k] = hasClearLineOfSight(a, b) ? 1 : 0, with dir =
+ * vnorm(b - a), gap = dot(b - a, b - a) taken before normalising, blocked iff
+ * the closest hit's |t dir|^2 < gap.
+ *
+ * NaN, infinite and degenerate inputs (a zero dir, a == b, NaN or infinite
+ * components) follow the comparisons as written: a comparison with NaN is
+ * false, so no hit and visible.  NaN words of point and normal are written
+ * as 0xFFC00000, as the frame and the G-buffer do.
+ *
+ * The results do not depend on lights, stackSize or
+ * rtg_context_set_semantics.  Rays are independent; the order of a batch
+ * affects speed only: the 64 rays of a wave walk the scene's BVH together,
+ * so coherent neighbours (a pixel grid, a sorted batch) are faster than a
+ * shuffled one.  Origins may lie anywhere: far outside the scene the BVH's
+ * boxes are widened per ray (by 2^-8 of the distance to the scene), so very
+ * distant origins are exact but slower.
+ *
+ * The device calls are asynchronous on `stream`, use none of the context's
+ * render scratch and may be mixed freely with rtg_render_device and
+ * rtg_gbuffer_device on one context.  n == 0 is RTG_OK with no launch.
+ * RTG_ERR_INVALID with a message, before any GPU call, for a null buffer,
+ * hits not 16-byte aligned, a context without a scene, or a batch of more
+ * than 2^31-1 workgroups (64 rays each). */
+typedef struct rtg_ray     { rtg_vec origin, dir; } rtg_ray;      /* 24 B */
+typedef struct rtg_segment { rtg_vec a, b; }        rtg_segment;  /* 24 B */
+typedef struct rtg_hit {                                           /* 32 B */
+  int id;          /* calcIntersection's sphere index; -1: no hit */
+  float t;         /* its minT; 1000.f when id == -1 */
+  rtg_vec point;   /* origin + t*dir, as raytracer.h:172-173; (0,0,0) when none */
+  rtg_vec normal;  /* vnorm(point - c), :176-177; (0,0,0) when none */
+} rtg_hit;
+
+int rtg_intersect_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
+                         rtg_hit* hitsDevice /* 16-byte aligned */, void* stream);
+/* One-shot: uploads the scene and the rays, runs on `device`, downloads n hits. */
+int rtg_intersect(int device, const rtg_sphere* spheres, unsigned sphNum,
+                  const rtg_ray* rays, size_t n, rtg_hit* hitsHost);
+/* The same on the host, no GPU call.  walk 0: plain loops over every ray and
+ * sphere (the yardstick).  walk 1: the device kernel's own query path compiled
+ * for the host, one ray per "wave": the scene tables built as
+ * rtg_context_set_scene builds them, then the branch the kernel takes (the
+ * BVH with the outside-origin treatment, the 64-sphere two-pass query, or
+ * the flat loop), so the culls can be checked without a GPU.  Any other walk
+ * is RTG_ERR_INVALID.  nthreads <= 0: 1. */
+int rtg_intersect_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_ray* rays,
+                       size_t n, rtg_hit* hitsHost, int walk, int nthreads);
+
+int rtg_visible_device(rtg_context* ctx, const rtg_segment* segsDevice, size_t n,
+                       unsigned char* outDevice, void* stream);
+int rtg_visible(int device, const rtg_sphere* spheres, unsigned sphNum,
+                const rtg_segment* segs, size_t n, unsigned char* outHost);
+int rtg_visible_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_segment* segs,
+                     size_t n, unsigned char* outHost, int walk, int nthreads);
 
 /* Semantics of a context's renders.  RTG_SEMANTICS_CPU (default) is the
  * reference CPU path (raytracer.h), bit for bit.  RTG_SEMANTICS_OPENCL is the

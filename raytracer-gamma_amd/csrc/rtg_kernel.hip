@@ -24,6 +24,7 @@
 #include "rtg.h"
 #include "rtg_internal.h"
 #include "rtg_trace_kernels.h"
+#include "rtg_rays.h"
 #include "rtg_scene_pack.h"
 
 #define HIP_TRY(expr)                                                              \
@@ -280,6 +281,7 @@ struct rtg_context {
   unsigned* cone = nullptr;   // secondary-ray cone masks (null when none)
   float* prim = nullptr;      // primary-cull sphere constants
   float* bvhNodes = nullptr;  // BVH node records (null when the scene has none)
+  rtg::RayBox rayBox{};       // the BVH's origin box, for the batch ray queries (rtg_rays.hip)
   float* capRec = nullptr;    // sphere lists of BVH scenes (null when none)
   unsigned* capOff = nullptr;
   float* ovRec = nullptr;
@@ -411,6 +413,12 @@ bool rtg_context_scene(const rtg_context* ctx, KernelArgs* a, int* device) {
   if (!ctx || !ctx->hasScene) return false;
   scene_args(ctx, a);
   *device = ctx->device;
+  return true;
+}
+// The same with the BVH's origin box (rtg_rays.hip).
+bool rtg_context_ray_scene(const rtg_context* ctx, KernelArgs* a, RayBox* box, int* device) {
+  if (!rtg_context_scene(ctx, a, device)) return false;
+  *box = ctx->rayBox;
   return true;
 }
 
@@ -785,6 +793,7 @@ int rtg_context_set_scene(rtg_context* ctx, const rtg_sphere* spheres, unsigned 
   ctx->n = sphNum;
   ctx->m = lgtNum;
   ctx->n4 = ps.n4;
+  ctx->rayBox = ray_box(ps.originBox);
   ctx->hasScene = true;
   ++ctx->sceneGen;  // new geometry keys: no launch-order feedback from the old scene
   const auto tEnd = clk::now();

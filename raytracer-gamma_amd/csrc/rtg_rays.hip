@@ -1,0 +1,719 @@
+// rtg_rays.hip — batch ray queries of librtg.so (rtg_intersect*, rtg_visible*,
+// rtg.h): calcIntersection (raytracer.h:145-194) and hasClearLineOfSight
+// (raytracer.h:272-309) for a caller's own rays against the resident scene,
+// bit for bit.  One lane per ray, one-wave workgroups, the wave's 64-entry BVH
+// stack in LDS (the G-buffer kernel's mapping, rtg_gbuffer.hip); a ray is 24
+// bytes in, a hit two 16-byte stores out, a visibility one byte.  Lanes past
+// the end of the batch stay in the wave as inactive queries (they load the
+// batch's last ray, store nothing): the BVH walk is wave-uniform, no lane
+// returns early from it.  One translation unit, no instantiation per stack
+// size; the launches take none of rtg_context's render scratch.
+//
+// Query per scene kind, all with the device functions of rtg_trace.h:
+//   BVH scene (KernelArgs::bvhNodes)  the walk below (closest_wide / blocked_wide)
+//   n4 <= 64                          closest_hit64 / blocked64
+//   anything else                     closest_hit4 / blocked (every sphere)
+// The primary-ray masks (group_sel), the shadow, overlap and cone masks and
+// the capsule lists are keyed to the renderer's own rays and are not used.
+//
+// ORIGINS OUTSIDE B*: the path taken is INFLATION (no flat fallback for finite
+// origins).  The BVH's boxes (build_bvh, bvh_grow, rtg_scene_pack.h) keep every
+// sphere the reference accepts only for ray origins inside the scene's origin
+// box B* (rtg_trace.h, "Why a box keeps every sphere"): sphere i's box has the
+// half-width
+//   w_i = r_i + 2^-8 (P_i + r_i) + 2^-18 (|c_i|_inf + r_i + omax) + 2^-20,
+// P_i = the distance from c_i to B*'s farthest corner >= |p_i| = |o - c_i|.
+// The first margin is mu_i = 2^-8 (|p_i| + r_i), the bound of an accepted
+// root's exact point X = o + t* d around the sphere, a statement about the
+// ray's own p_i and d whatever they are (it comes from the radicand's
+// relative rounding error, <= ~60 eps a (|p_i|^2 + r_i^2)); the second is the
+// slab test's rounding, 3 eps (|plane| + |o|) per axis.  For an origin o
+// anywhere, with
+//   D >= dist(o, B*)  (0 inside),   M = |o|_inf,
+// the nearest point q of B* to o has |q - c_i| <= P_i (q in B*, a box is
+// convex and the farthest corner maximises the distance), so
+//   |p_i| <= P_i + D,   mu_i <= 2^-8 (P_i + r_i) + 2^-8 D,
+// and the slab rounding is at most 3 eps (|plane| + M), of which the builder's
+// term covers 3 eps (|plane| + omax).  Every sphere box therefore needs at
+// most
+//   delta = 2^-8 D + 2^-18 [M > omax] M
+// more half-width (ray_delta rounds it up by 1 + 2^-10), and the walk tests
+// every child box as [lo - delta, hi + delta].  A child box is the union of
+// its spheres' grown boxes; the union inflated by delta contains each member
+// inflated by delta, so inner nodes need nothing else.  Roundings on the way:
+//  * D is taken to RayBox, B* rounded inward, so it can only grow; its
+//    subtractions, squares, sum and v_sqrt_f32 are each within 2^-23
+//    relative, and the factor 1 + 2^-10 on delta covers them;
+//  * lo - delta and hi + delta round by 2^-24 (|plane| + delta): the plane
+//    part is a third of the slab's own 3 eps |plane| allowance, for which the
+//    builder's 2^-18 = 64 eps term leaves a factor 20; the delta part (and
+//    the slab rounding 3 eps delta of the moved plane) is inside 2^-10 delta;
+//  * for M > omax the whole 2^-18 M is added, 64 eps M against the 3 eps M
+//    needed.
+// delta is exactly 0 for an origin inside B* (the renderer's own kind: D = 0,
+// M <= omax), so such rays walk the tree the render kernels walk.
+// tests/test_rays_host.py (walk 1 against walk 0) checks it on near-tangent
+// rays from 1e2 .. 1e5 scene units away.
+//
+// Lanes outside the range arguments take the flat loop (closest_hit4 /
+// blocked) in a second pass that the wave skips when it has none (`odd`):
+//  * an origin with a non-finite component or M > 2^56: the slab products
+//    o / d stay finite only below 2^57 (build_bvh);
+//  * a direction with 2 a = 2 d.d outside [2^-60, 2^60] (RayQ::fast false;
+//    NaN, infinite, zero and a == b segments are among them): every
+//    threshold below that multiplies a (75 a, 2^20 a, a (1 - K), sqrt(gap /
+//    a)) is then free of overflow and underflow, and 1 / d_k is normal.
+//
+// The sphere-slot prunes are stated for the ray's own p = o - c (the
+// reference's float subtraction) and d, and need nothing of where o is:
+//  * pass-1 screen (pass1_rad): a slack of K = 2^-16 relative to a (|p|^2 +
+//    r^2) against ~40 ulps of rounding of both evaluations: relative in p and
+//    d, any origin, any |d| in the range above.  Where x^2 or a cs overflow
+//    (|p| up to 2^58): x^2 = inf gives +inf or NaN, kept; a cs = +inf with
+//    x^2 finite gives -inf, and the reference's a4 cc >= a (1 - K) cs is +inf
+//    too, its radicand -inf or NaN, rejected as well;
+//  * behind: proves b > 0, cc >= 0 and b < 150 a in the reference's own
+//    values from the fused x and cs; the dot products' error bounds are
+//    AM-GM bounds in a + |p|^2, any p and d;
+//  * beyond: an accepted root has t |d| = |X - o| >= |p| - |X - c| >= |p| (1 -
+//    2^-8) - r (1 + 2^-8), with mu_i in terms of the ray's own p; the reach is
+//    minT |d| rounded up (closest) or sqrt(gap) rounded up (shadow), any o;
+//  * the box reach: tn <= t* needs t* > 0 (the 1e-5 window) and t* <= minT,
+//    or |t* d|^2 < gap, so t* < sqrt(gap / a) (1 + 2^-18), at most 1000.
+// The 64-sphere path has no origin precondition at all: candidate_masks64
+// evaluates the reference's own radicand (same operations, same value), and
+// pass2's Markstein quotient (ray_sphere_k<true>) is chosen by all(q.fast), a
+// condition on 2 a alone; the quotient's proof (tests/fpcheck/
+// markstein_check.c) is about the float pair (x, den), any numerator: a
+// quotient in the (1e-5, 10000) window has x >= 2^-77, far from underflow,
+// and one whose product overflows is rejected by both forms (inf or NaN).
+//
+// FP contract: the Makefile's FPFLAGS; fused multiply-adds only inside the
+// culls of rtg_trace.h (slab_pass, the screen); the root test is the shared
+// ray_sphere*.
+//
+// rtg_intersect_host / rtg_visible_host: walk 0 = plain loops (closest_hit /
+// blocked over the caller's array), the yardstick; walk 1 = the functions the
+// kernels call (ray_closest / ray_blocked) over the packed scene tables,
+// one ray per "wave".
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <functional>
+#include <thread>
+#include <vector>
+
+#include "rtg.h"
+#include "rtg_internal.h"
+#include "rtg_trace_kernels.h"
+#include "rtg_rays.h"
+#include "rtg_scene_pack.h"
+
+static_assert(sizeof(rtg_ray) == 24 && sizeof(rtg_segment) == 24, "rays are 24 B");
+static_assert(sizeof(rtg_hit) == 32 && offsetof(rtg_hit, t) == 4 && offsetof(rtg_hit, point) == 8 &&
+                  offsetof(rtg_hit, normal) == 20,
+              "rtg_hit layout (two 16-byte halves)");
+
+#define HIP_TRY(expr)                                                              \
+  do {                                                                             \
+    hipError_t e_ = (expr);                                                        \
+    if (e_ != hipSuccess) {                                                        \
+      rtg_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
+                    __LINE__);                                                     \
+      return RTG_ERR_HIP;                                                          \
+    }                                                                              \
+  } while (0)
+
+namespace rtg {
+
+// The extra half-width every BVH box gets for a ray from o (header); `odd`:
+// the origin is outside the slab arithmetic's range.
+RTG_HD float ray_delta(const RayBox& B, V3 o, bool& odd) {
+  const float ax = fabsf(o.x), ay = fabsf(o.y), az = fabsf(o.z);
+  odd = !(ax <= 0x1p56f && ay <= 0x1p56f && az <= 0x1p56f);  // NaN: odd
+  const float M = fmaxf(ax, fmaxf(ay, az));
+  const float ex = fmaxf(fmaxf(B.lo[0] - o.x, o.x - B.hi[0]), 0.f);
+  const float ey = fmaxf(fmaxf(B.lo[1] - o.y, o.y - B.hi[1]), 0.f);
+  const float ez = fmaxf(fmaxf(B.lo[2] - o.z, o.z - B.hi[2]), 0.f);
+  const float D = sqrt_hw(ex * ex + ey * ey + ez * ez);
+  const float Mo = M > B.omax ? M : 0.f;
+  return (0x1p-8f * D + 0x1p-18f * Mo) * (1.0f + 0x1p-10f);
+}
+
+// One node of a widened walk: bvh_ray_node (rtg_trace.h) with every child box
+// taken as [lo - delta, hi + delta] and a per-lane `active`.  kShadow: the
+// shadow query (reach reachT / reachD, lanes leave when `blk`), else the
+// closest-hit query (the reach is the live minT).
+template <bool kShadow, class Scene>
+RTG_HD int ray_node(const Scene& sc, const RayQ& q, const BoxQ& b, float delta, unsigned nd,
+                    unsigned oct, bool active, float dn, float reachT, float reachD, float gap,
+                    float& minT, int& best, bool& blk, BvhStack& st) {
+  BvhRec r;
+  sc.bvh_rec(nd * kBvhCopies + oct, r);
+  int pc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) pc[k] = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (r.ch[k] < 0) {  // wave-uniform: a sphere slot
+      const float* g = &r.s[6 * k];
+      const V3 c = v3(g[0], g[1], g[2]);
+      const V3 p = vsub(q.o, c);
+      const float xd = fmaf(q.d.x, p.x, fmaf(q.d.y, p.y, q.d.z * p.z));
+      const float p2 = fmaf(p.x, p.x, fmaf(p.y, p.y, p.z * p.z));
+      const float cs = p2 - g[3];
+      const float v = fmaf(xd, xd, fmaf(-q.ap, cs, 0x1p-100f));  // pass1_rad
+      const float rD = kShadow ? reachD : minT * dn;
+      const bool act = kShadow ? (active && !blk) : active;
+      if (act && !beyond(p2, g[5], rD) && !(v < 0.f) && !behind(0.5f * q.den, xd, cs, g[3])) {
+        bool res;
+        const float t = ray_sphere_leaf(q, c, g[4], res);
+        if constexpr (kShadow) take_blocker(t, q.d, gap, blk);
+        else take_closer(t, ~r.ch[k], minT, best);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (r.ch[k] > 0) {  // a child node: its box widened by the lane's delta
+      const float* g = &r.s[6 * k];
+      float tn;
+      const float rT = kShadow ? reachT : minT;
+      const bool act = kShadow ? (active && !blk) : active;
+      const bool pass =
+          act && slab_pass(b, v3(g[0] - delta, g[1] - delta, g[2] - delta),
+                           v3(g[3] + delta, g[4] + delta, g[5] + delta), rT, tn);
+      if (sc.any(pass)) pc[k] = r.ch[k];
+    }
+  }
+  int nxt = 0;  // slots already front to back: the nearest next, the others pushed far first
+#pragma unroll
+  for (int k = 3; k >= 0; --k) {
+    if (pc[k] > 0) {
+      if (nxt > 0) st.push(nxt);
+      nxt = pc[k];
+    }
+  }
+  return nxt;
+}
+
+// closest_bvh (rtg_trace.h) over the widened boxes; the whole wave enters,
+// `active` lanes query.
+template <class Scene>
+RTG_HD int closest_wide(const Scene& sc, const RayQ& q, float delta, bool active, float& tOut) {
+  float minT = 1000.f;
+  int best = -1;
+  bool blk = false;
+  tOut = minT;
+  if (!sc.any(active)) return best;
+  const float dn = norm_up(q.den * 0.5f);
+  const BoxQ b = make_boxq(q);
+  BvhStack st(sc.bvh_stack());
+  const unsigned oct = query_octant(sc, q);
+  unsigned nd = 0;  // the root
+  for (;;) {        // wave-uniform
+    const int nx = ray_node<false>(sc, q, b, delta, nd, oct, active, dn, 0.f, 0.f, 0.f, minT, best,
+                                   blk, st);
+    if (nx > 0) {
+      nd = (unsigned)nx;
+    } else {
+      if (st.empty()) break;
+      nd = (unsigned)st.pop();
+    }
+  }
+  tOut = minT;
+  return best;
+}
+
+// blocked_bvh (rtg_trace.h) over the widened boxes.  Active lanes have 2 a in
+// the Markstein range, so the reach in ray units is sqrt(gap / a) rounded up.
+template <class Scene>
+RTG_HD bool blocked_wide(const Scene& sc, const RayQ& q, float gap, float delta, bool active) {
+  bool blk = false;
+  float minT = 0.f;
+  int best = 0;
+  if (!sc.any(active)) return blk;
+  const float reachD = norm_up(gap);
+  const float reachT = fminf(sqrt_hw(gap * rcp_hw(q.den * 0.5f)) * (1.0f + 0x1p-18f), 1000.f);
+  const BoxQ b = make_boxq(q);
+  BvhStack st(sc.bvh_stack());
+  const unsigned oct = query_octant(sc, q);
+  unsigned nd = 0;  // the root
+  for (;;) {        // wave-uniform
+    const int nx = ray_node<true>(sc, q, b, delta, nd, oct, active, 0.f, reachT, reachD, gap, minT,
+                                  best, blk, st);
+    if (sc.all(blk || !active)) break;
+    if (nx > 0) {
+      nd = (unsigned)nx;
+    } else {
+      if (st.empty()) break;
+      nd = (unsigned)st.pop();
+    }
+  }
+  return blk;
+}
+
+// calcIntersection for ray (o, d) of an `active` lane; the whole wave enters
+// (kBvh: the walk is wave-uniform).  Inactive lanes get a miss.
+template <bool kBvh, class Scene>
+RTG_HD int ray_closest(const Scene& sc, const RayBox& box, V3 o, V3 d, bool active, float& t) {
+  if constexpr (kBvh) {
+    const RayQ q = make_query(o, d);
+    bool odd;
+    const float delta = ray_delta(box, o, odd);
+    odd = active && (odd || !q.fast);
+    int id = closest_wide(sc, q, delta, active && !odd, t);
+    if (sc.any(odd)) {
+      if (odd) id = closest_hit4(sc, o, d, t);
+    }
+    return id;
+  } else {
+    t = 1000.f;
+    if (!active) return -1;
+    if (sc.n4 <= 64) return closest_hit64(sc, o, d, t);
+    return closest_hit4(sc, o, d, t);
+  }
+}
+
+// hasClearLineOfSight's blocker search for the ray (o, d) with gap |b - a|^2.
+template <bool kBvh, class Scene>
+RTG_HD bool ray_blocked(const Scene& sc, const RayBox& box, V3 o, V3 d, float gap, bool active) {
+  if constexpr (kBvh) {
+    const RayQ q = make_query(o, d);
+    bool odd;
+    const float delta = ray_delta(box, o, odd);
+    odd = active && (odd || !q.fast);
+    bool blk = blocked_wide(sc, q, gap, delta, active && !odd);
+    if (sc.any(odd)) {
+      if (odd) blk = blocked(sc, o, d, gap);
+    }
+    return blk;
+  } else {
+    if (!active) return false;
+    if (sc.n4 <= 64) return blocked64(sc, o, d, gap);
+    return blocked(sc, o, d, gap);
+  }
+}
+
+RTG_HD unsigned ray_bits(float v) {  // NaN as the frame's NaNs (rtg.h)
+  unsigned u;
+  memcpy(&u, &v, 4);
+  return (v != v) ? 0xFFC00000u : u;
+}
+
+// The hit record of ray (o, d) with closest hit (id, t) as two 16-byte
+// halves; point and normal of the winner (raytracer.h:172-177), c its centre.
+RTG_HD void hit_record(V3 o, V3 d, int id, float t, V3 c, unsigned* w) {
+  V3 P = v3(0.f, 0.f, 0.f), N = v3(0.f, 0.f, 0.f);
+  if (id >= 0) {
+    P = vadd(o, vsmul(t, d));
+    N = vnorm(vsub(P, c));
+  }
+  w[0] = (unsigned)id;
+  w[1] = ray_bits(t);
+  w[2] = ray_bits(P.x);
+  w[3] = ray_bits(P.y);
+  w[4] = ray_bits(P.z);
+  w[5] = ray_bits(N.x);
+  w[6] = ray_bits(N.y);
+  w[7] = ray_bits(N.z);
+}
+
+// A segment's shadow ray (raytracer.h:279-286): gap before normalising.
+RTG_HD V3 segment_ray(V3 a, V3 b, float& gap) {
+  const V3 dist = vsub(b, a);
+  gap = vdot(dist, dist);
+  return vnorm(dist);
+}
+
+// ---- host forms ----
+
+// The caller's sphere array as a Scene of closest_hit / blocked: r*r as
+// raySphere forms it (raytracer.h:100).
+struct RaySpheres {
+  const rtg_sphere* s;
+  unsigned n;
+  V3 sphere(unsigned i, float& r2) const {
+    r2 = s[i].radius * s[i].radius;
+    return v3(s[i].pos.x, s[i].pos.y, s[i].pos.z);
+  }
+};
+
+// The packed tables (pack_scene) as a one-lane Scene of the kernels' queries.
+struct PackedRayScene {
+  const float* geom;
+  const float* bvhNodes;
+  unsigned n, n4;
+  bool all(bool b) const { return b; }
+  bool any(bool b) const { return b; }
+  V3 first_lane(V3 v) const { return v; }
+  int* bvh_stack() const { return nullptr; }
+  void bvh_rec(unsigned nd, BvhRec& r) const {
+    const float* g = bvhNodes + (size_t)kBvhWords * nd;
+    memcpy(r.s, g, 24 * 4);
+    memcpy(r.ch, g + 24, 4 * 4);
+    memcpy(r.cr, g + 28, 4 * 4);
+  }
+  V3 sphere(unsigned i, float& r2) const {
+    const float* g = geom + 4 * (size_t)i;
+    r2 = g[3];
+    return v3(g[0], g[1], g[2]);
+  }
+  V3 sphere_lane(unsigned i, float& r2) const { return sphere(i, r2); }
+  void sphere4(unsigned i, V3* c, float* r2) const {
+    for (int k = 0; k < 4; ++k) c[k] = sphere(i + k, r2[k]);
+  }
+};
+
+struct HostRayJob {
+  const rtg_sphere* spheres;
+  unsigned n;
+  const PackedScene* ps;  // walk 1
+  RayBox box;
+};
+
+static V3 host_centre(const HostRayJob& j, int id) {
+  if (id < 0) return v3(0.f, 0.f, 0.f);
+  return v3(j.spheres[id].pos.x, j.spheres[id].pos.y, j.spheres[id].pos.z);
+}
+
+static void intersect_host_range(const HostRayJob& j, const rtg_ray* rays, size_t k0, size_t k1,
+                                 rtg_hit* hits) {
+  const RaySpheres plain{j.spheres, j.n};
+  PackedRayScene sc{nullptr, nullptr, 0, 0};
+  bool bvh = false;
+  if (j.ps) {
+    sc = PackedRayScene{j.ps->geom.data(), j.ps->bvhNodes.data(), j.ps->n, j.ps->n4};
+    bvh = !j.ps->bvhNodes.empty();
+  }
+  for (size_t k = k0; k < k1; ++k) {
+    const V3 o = v3(rays[k].origin.x, rays[k].origin.y, rays[k].origin.z);
+    const V3 d = v3(rays[k].dir.x, rays[k].dir.y, rays[k].dir.z);
+    float t;
+    int id;
+    if (!j.ps) id = closest_hit(plain, o, d, t);
+    else if (bvh) id = ray_closest<true>(sc, j.box, o, d, true, t);
+    else id = ray_closest<false>(sc, j.box, o, d, true, t);
+    unsigned w[8];
+    hit_record(o, d, id, t, host_centre(j, id), w);
+    memcpy(&hits[k], w, sizeof w);
+  }
+}
+
+static void visible_host_range(const HostRayJob& j, const rtg_segment* segs, size_t k0, size_t k1,
+                               unsigned char* out) {
+  const RaySpheres plain{j.spheres, j.n};
+  PackedRayScene sc{nullptr, nullptr, 0, 0};
+  bool bvh = false;
+  if (j.ps) {
+    sc = PackedRayScene{j.ps->geom.data(), j.ps->bvhNodes.data(), j.ps->n, j.ps->n4};
+    bvh = !j.ps->bvhNodes.empty();
+  }
+  for (size_t k = k0; k < k1; ++k) {
+    const V3 a = v3(segs[k].a.x, segs[k].a.y, segs[k].a.z);
+    const V3 b = v3(segs[k].b.x, segs[k].b.y, segs[k].b.z);
+    float gap;
+    const V3 d = segment_ray(a, b, gap);
+    bool blk;
+    if (!j.ps) blk = blocked(plain, a, d, gap);
+    else if (bvh) blk = ray_blocked<true>(sc, j.box, a, d, gap, true);
+    else blk = ray_blocked<false>(sc, j.box, a, d, gap, true);
+    out[k] = blk ? 0 : 1;
+  }
+}
+
+// Contiguous bands of [0, n) on nthreads threads.
+static void host_bands(size_t n, int nthreads, const std::function<void(size_t, size_t)>& fn) {
+  size_t nt = nthreads > 0 ? (size_t)nthreads : 1;
+  if (nt > n) nt = n;
+  if (nt <= 1) {
+    fn(0, n);
+    return;
+  }
+  std::vector<std::thread> pool;
+  for (size_t k = 0; k < nt; ++k) pool.emplace_back(fn, n * k / nt, n * (k + 1) / nt);
+  for (auto& th : pool) th.join();
+}
+
+// ---- device side ----
+
+// The trace kernels' scene over the context's tables, without frames or
+// masks; `stk`: the wave's BVH traversal stack in LDS.
+template <bool kBvh>
+using RayScene = DevScene<false, 64, kBvh, 0>;
+
+template <bool kBvh>
+__device__ __forceinline__ void ray_scene(const KernelArgs& a, RayScene<kBvh>& sc, int* stk) {
+  sc.lfr = nullptr;
+  sc.nfl = 0;
+  sc.geom = (cfloat_p)a.geom;
+  sc.crad2 = (cfloat_p)a.crad2;
+  sc.mats = (cfloat_p)a.mats;
+  sc.lgeom = reinterpret_cast<const float4*>(a.geom);
+  sc.lights = (cfloat_p)a.lights;
+  sc.smask = nullptr;
+  sc.cone = nullptr;
+  sc.prim = (cfloat_p)a.prim;
+  sc.bvhNodes = (cfloat_p)a.bvhNodes;
+  sc.bvhStk = stk;
+  sc.capRec = nullptr;
+  sc.capOff = nullptr;
+  sc.ovRec = nullptr;
+  sc.ovOff = nullptr;
+  sc.n = a.n;
+  sc.m = a.m;
+  sc.n4 = a.n4;
+}
+
+// One lane per ray; n > 0.  Lanes past n take the last ray and stay inactive.
+template <bool kBvh>
+__global__ __launch_bounds__(64) void intersect_kernel(const KernelArgs a, const RayBox box,
+                                                       const rtg_ray* __restrict__ rays, size_t n,
+                                                       rtg_hit* __restrict__ hits) {
+  __shared__ int stk[kBvh ? 64 : 1];
+  RayScene<kBvh> sc;
+  ray_scene<kBvh>(a, sc, stk);
+  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool active = k < n;
+  const float* r = reinterpret_cast<const float*>(rays + (active ? k : n - 1));  // 24 B
+  const V3 o = v3(r[0], r[1], r[2]);
+  const V3 d = v3(r[3], r[4], r[5]);
+  float t;
+  const int id = ray_closest<kBvh>(sc, box, o, d, active, t);
+  if (active) {  // k < n: inside the batch's records
+    V3 c = v3(0.f, 0.f, 0.f);
+    float r2;
+    if (id >= 0) c = sc.sphere_lane((unsigned)id, r2);  // id < n: a scene record
+    unsigned w[8];
+    hit_record(o, d, id, t, c, w);
+    uint4* out = reinterpret_cast<uint4*>(hits + k);  // 16-byte aligned (rtg_intersect_device)
+    out[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    out[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+}
+
+template <bool kBvh>
+__global__ __launch_bounds__(64) void visible_kernel(const KernelArgs a, const RayBox box,
+                                                     const rtg_segment* __restrict__ segs,
+                                                     size_t n, unsigned char* __restrict__ out) {
+  __shared__ int stk[kBvh ? 64 : 1];
+  RayScene<kBvh> sc;
+  ray_scene<kBvh>(a, sc, stk);
+  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool active = k < n;
+  const float* r = reinterpret_cast<const float*>(segs + (active ? k : n - 1));  // 24 B
+  const V3 pa = v3(r[0], r[1], r[2]);
+  const V3 pb = v3(r[3], r[4], r[5]);
+  float gap;
+  const V3 d = segment_ray(pa, pb, gap);
+  const bool blk = ray_blocked<kBvh>(sc, box, pa, d, gap, active);
+  if (active) out[k] = blk ? 0 : 1;  // k < n
+}
+
+}  // namespace rtg
+
+using namespace rtg;
+
+// Argument checks of the host and one-shot forms (no HIP call).
+static int check_ray_args(const char* what, const rtg_sphere* spheres, unsigned sphNum,
+                          const void* in, const void* out) {
+  if (!in || !out) {
+    rtg_set_error("%s: null %s buffer", what, in ? "output" : "input");
+    return RTG_ERR_INVALID;
+  }
+  if (sphNum && !spheres) {
+    rtg_set_error("%s: null scene array", what);
+    return RTG_ERR_INVALID;
+  }
+  return RTG_OK;
+}
+
+// The launch geometry of a batch of n > 0 rays: one-wave workgroups.
+static int ray_blocks(const char* what, size_t n, unsigned* blocks) {
+  const size_t b = (n + 63) / 64;
+  if (b > 0x7FFFFFFFu) {
+    rtg_set_error("%s: batch too large (%zu workgroups)", what, b);
+    return RTG_ERR_INVALID;
+  }
+  *blocks = (unsigned)b;
+  return RTG_OK;
+}
+
+static int host_job(const char* what, const rtg_sphere* spheres, unsigned sphNum, int walk,
+                    PackedScene* ps, HostRayJob* job) {
+  if (walk != 0 && walk != 1) {
+    rtg_set_error("%s: walk %d (0: plain loops, 1: the kernel's query path)", what, walk);
+    return RTG_ERR_INVALID;
+  }
+  job->spheres = spheres;
+  job->n = sphNum;
+  job->ps = nullptr;
+  job->box = RayBox{};
+  if (walk == 1) {
+    if (sphNum >= RTG_MAX_SPHERES) {
+      rtg_set_error("%s: %u spheres (at most %u)", what, sphNum, RTG_MAX_SPHERES - 1);
+      return RTG_ERR_INVALID;
+    }
+    pack_scene(spheres, sphNum, nullptr, 0, ps);  // as rtg_context_set_scene
+    job->ps = ps;
+    job->box = ray_box(ps->originBox);
+  }
+  return RTG_OK;
+}
+
+extern "C" {
+
+int rtg_intersect_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_ray* rays, size_t n,
+                       rtg_hit* hitsHost, int walk, int nthreads) {
+  rtg_clear_error();
+  int rc = check_ray_args("intersect", spheres, sphNum, rays, hitsHost);
+  if (rc) return rc;
+  PackedScene ps;
+  HostRayJob job;
+  rc = host_job("intersect", spheres, sphNum, walk, &ps, &job);
+  if (rc) return rc;
+  if (n == 0) return RTG_OK;
+  host_bands(n, nthreads,
+             [&](size_t k0, size_t k1) { intersect_host_range(job, rays, k0, k1, hitsHost); });
+  return RTG_OK;
+}
+
+int rtg_visible_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_segment* segs, size_t n,
+                     unsigned char* outHost, int walk, int nthreads) {
+  rtg_clear_error();
+  int rc = check_ray_args("visible", spheres, sphNum, segs, outHost);
+  if (rc) return rc;
+  PackedScene ps;
+  HostRayJob job;
+  rc = host_job("visible", spheres, sphNum, walk, &ps, &job);
+  if (rc) return rc;
+  if (n == 0) return RTG_OK;
+  host_bands(n, nthreads,
+             [&](size_t k0, size_t k1) { visible_host_range(job, segs, k0, k1, outHost); });
+  return RTG_OK;
+}
+
+int rtg_intersect_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
+                         rtg_hit* hitsDevice, void* stream) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  KernelArgs a{};
+  RayBox box{};
+  int device = 0;
+  if (!rtg_context_ray_scene(ctx, &a, &box, &device)) {
+    rtg_set_error("intersect: no context/scene");
+    return RTG_ERR_INVALID;
+  }
+  if (!raysDevice || !hitsDevice) {
+    rtg_set_error("intersect: null %s buffer", raysDevice ? "hit" : "ray");
+    return RTG_ERR_INVALID;
+  }
+  if (((uintptr_t)hitsDevice & 15u) != 0) {
+    rtg_set_error("intersect: hits not 16-byte aligned");
+    return RTG_ERR_INVALID;
+  }
+  if (n == 0) return RTG_OK;
+  unsigned blocks;
+  const int rc = ray_blocks("intersect", n, &blocks);
+  if (rc) return rc;
+  void (*fn)(const KernelArgs, const RayBox, const rtg_ray*, size_t, rtg_hit*) =
+      a.bvhNodes ? intersect_kernel<true> : intersect_kernel<false>;
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, raysDevice, n,
+                     hitsDevice);
+  HIP_TRY(hipGetLastError());
+  return RTG_OK;
+}
+
+int rtg_visible_device(rtg_context* ctx, const rtg_segment* segsDevice, size_t n,
+                       unsigned char* outDevice, void* stream) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  KernelArgs a{};
+  RayBox box{};
+  int device = 0;
+  if (!rtg_context_ray_scene(ctx, &a, &box, &device)) {
+    rtg_set_error("visible: no context/scene");
+    return RTG_ERR_INVALID;
+  }
+  if (!segsDevice || !outDevice) {
+    rtg_set_error("visible: null %s buffer", segsDevice ? "output" : "segment");
+    return RTG_ERR_INVALID;
+  }
+  if (n == 0) return RTG_OK;
+  unsigned blocks;
+  const int rc = ray_blocks("visible", n, &blocks);
+  if (rc) return rc;
+  void (*fn)(const KernelArgs, const RayBox, const rtg_segment*, size_t, unsigned char*) =
+      a.bvhNodes ? visible_kernel<true> : visible_kernel<false>;
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, segsDevice, n,
+                     outDevice);
+  HIP_TRY(hipGetLastError());
+  return RTG_OK;
+}
+
+// One-shot body: scene and `inBytes` of input up, `launch` on the context,
+// `outBytes` down.
+static int ray_one_shot(int device, const rtg_sphere* spheres, unsigned sphNum, const void* in,
+                        size_t inBytes, void* out, size_t outBytes,
+                        const std::function<int(rtg_context*, const void*, void*)>& launch) {
+  rtg_context* ctx = nullptr;
+  int rc = rtg_context_create(device, &ctx);
+  if (rc) return rc;
+  void *dIn = nullptr, *dOut = nullptr;
+  rc = rtg_context_set_scene(ctx, spheres, sphNum, nullptr, 0);
+  if (!rc && (hipMalloc(&dIn, inBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess)) {
+    rtg_set_error("hipMalloc(%zu + %zu) failed", inBytes, outBytes);
+    rc = RTG_ERR_NOMEM;
+  }
+  if (!rc && hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess) {
+    rtg_set_error("upload of %zu bytes failed", inBytes);
+    rc = RTG_ERR_HIP;
+  }
+  if (!rc) rc = launch(ctx, dIn, dOut);
+  if (!rc) {
+    hipError_t e = hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+      rtg_set_error("kernel/readback failed: %s", hipGetErrorString(e));
+      rc = RTG_ERR_HIP;
+    }
+  }
+  (void)hipFree(dIn);
+  (void)hipFree(dOut);
+  rtg_context_destroy(ctx);
+  return rc;
+}
+
+int rtg_intersect(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_ray* rays,
+                  size_t n, rtg_hit* hitsHost) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  const int rc = check_ray_args("intersect", spheres, sphNum, rays, hitsHost);
+  if (rc) return rc;
+  if (n == 0) return RTG_OK;
+  return ray_one_shot(device, spheres, sphNum, rays, n * sizeof(rtg_ray), hitsHost,
+                      n * sizeof(rtg_hit), [&](rtg_context* ctx, const void* in, void* out) {
+                        return rtg_intersect_device(ctx, (const rtg_ray*)in, n, (rtg_hit*)out,
+                                                    nullptr);
+                      });
+}
+
+int rtg_visible(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_segment* segs,
+                size_t n, unsigned char* outHost) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  const int rc = check_ray_args("visible", spheres, sphNum, segs, outHost);
+  if (rc) return rc;
+  if (n == 0) return RTG_OK;
+  return ray_one_shot(device, spheres, sphNum, segs, n * sizeof(rtg_segment), outHost, n,
+                      [&](rtg_context* ctx, const void* in, void* out) {
+                        return rtg_visible_device(ctx, (const rtg_segment*)in, n,
+                                                  (unsigned char*)out, nullptr);
+                      });
+}
+
+}  // extern "C"

@@ -56,6 +56,10 @@ struct PackedScene {
   // record of kBvhWords words per node (rtg_trace.h BvhRec, loaded with two
   // 64-byte scalar loads); empty for small or non-finite scenes.
   std::vector<float> bvhNodes;
+  // With a BVH, the origin box B* its sphere boxes were grown for (origin_box:
+  // lo.xyz, hi.xyz, omax); the batch ray queries (rtg_rays.hip) widen the
+  // boxes for rays that start outside it.
+  double originBox[7] = {0, 0, 0, 0, 0, 0, 0};
   // Sphere lists of BVH scenes (sphere_lists): capsule and overlap lists.
   std::vector<float> capRec, ovRec;
   std::vector<unsigned> capOff, ovOff;
@@ -713,6 +717,11 @@ inline bool build_bvh(const rtg_sphere* spheres, unsigned n, PackedScene* ps) {
   // coordinate below 2^57 (the origin box and the grown boxes within it) the
   // products stay below 2^121, finite.  Larger scenes take the flat queries.
   if (!(ob.omax <= 0x1p56)) return false;
+  for (int a = 0; a < 3; ++a) {
+    ps->originBox[a] = ob.lo[a];
+    ps->originBox[3 + a] = ob.hi[a];
+  }
+  ps->originBox[6] = ob.omax;
   // grown boxes: 6 floats per sphere
   std::vector<float> gb((size_t)n * 6);
   for (unsigned i = 0; i < n; ++i) {

@@ -41,6 +41,10 @@ static void usage() {
   printf("      --out        FILE    Output PPM (default testPPM.ppm)\n");
   printf("      --gbuffer    FILE    Also write the primary-hit G-buffer: W*H raw little-endian\n");
   printf("                           rtg_gbuf_px records (id, t, hits, sample, normal, idSum)\n");
+  printf("      --rays       FILE    Also intersect the rays of FILE with the scene: raw little-endian\n");
+  printf("                           24-byte rtg_ray records (origin, dir); needs --hits\n");
+  printf("      --hits       FILE    Write their closest hits: 32-byte rtg_hit records\n");
+  printf("                           (id, t, point, normal)\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -62,7 +66,7 @@ int main(int argc, char** argv) {
   unsigned device = 0, W = 800, H = 600, nSph = 3, nLgt = 2, depth = 5, repeat = 1;
   unsigned long long seed = 42;
   float aa = 3.f, zoom = -4.f;
-  std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut;
+  std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut;
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   for (int i = 1; i < argc; ++i) {
@@ -113,6 +117,10 @@ int main(int argc, char** argv) {
       out = need(a);
     } else if (!strcmp(a, "--gbuffer")) {
       gbufOut = need(a);
+    } else if (!strcmp(a, "--rays")) {
+      raysIn = need(a);
+    } else if (!strcmp(a, "--hits")) {
+      hitsOut = need(a);
     } else if (!strcmp(a, "--scene")) {
       sceneIn = need(a);
     } else if (!strcmp(a, "--save-scene")) {
@@ -129,6 +137,11 @@ int main(int argc, char** argv) {
       usage();
       return 1;
     }
+  }
+
+  if (raysIn.empty() != hitsOut.empty()) {
+    printf("--rays and --hits go together\n");
+    return 1;
   }
 
   std::vector<rtg_sphere> spheres;
@@ -220,6 +233,40 @@ int main(int argc, char** argv) {
     }
     printf("Wrote %s (%zu G-buffer records of %zu bytes)\n", gbufOut.c_str(), gbuf.size(),
            sizeof(rtg_gbuf_px));
+  }
+
+  if (!raysIn.empty()) {  // records as they lie in memory, like the G-buffer's
+    std::vector<rtg_ray> rays;
+    FILE* f = fopen(raysIn.c_str(), "rb");
+    bool ok = f != nullptr;
+    if (ok) {
+      ok = fseek(f, 0, SEEK_END) == 0;
+      const long bytes = ok ? ftell(f) : -1;
+      ok = ok && bytes >= 0 && bytes % (long)sizeof(rtg_ray) == 0 && fseek(f, 0, SEEK_SET) == 0;
+      if (ok) {
+        rays.resize((size_t)bytes / sizeof(rtg_ray));
+        ok = fread(rays.data(), sizeof(rtg_ray), rays.size(), f) == rays.size();
+      }
+      fclose(f);
+    }
+    if (!ok) {
+      fprintf(stderr, "Error: can't read %s as %zu-byte ray records\n", raysIn.c_str(),
+              sizeof(rtg_ray));
+      exit(EXIT_FAILURE);
+    }
+    std::vector<rtg_hit> hits(rays.size());
+    if (!rays.empty())
+      check(rtg_intersect((int)device, spheres.data(), nSph, rays.data(), rays.size(),
+                          hits.data()),
+            "rtg_intersect");
+    f = fopen(hitsOut.c_str(), "wb");
+    if (!f || fwrite(hits.data(), sizeof(rtg_hit), hits.size(), f) != hits.size() ||
+        fclose(f) != 0) {
+      fprintf(stderr, "Error: can't write %s\n", hitsOut.c_str());
+      exit(EXIT_FAILURE);
+    }
+    printf("Wrote %s (%zu hit records of %zu bytes)\n", hitsOut.c_str(), hits.size(),
+           sizeof(rtg_hit));
   }
   return 0;
 }

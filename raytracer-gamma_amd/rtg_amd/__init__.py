@@ -48,6 +48,11 @@ assert SPHERE_DTYPE.itemsize == 48 and LIGHT_DTYPE.itemsize == 24
 GBUF_DTYPE = np.dtype([("id", "<i4"), ("t", "<f4"), ("hits", "<u4"), ("sample", "<u4"),
                        ("normal", "<f4", 3), ("idSum", "<u4")])
 assert GBUF_DTYPE.itemsize == 32
+# rtg_ray, rtg_segment and rtg_hit (include/rtg.h): the batch ray queries' records
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("dir", "<f4", 3)])
+SEGMENT_DTYPE = np.dtype([("a", "<f4", 3), ("b", "<f4", 3)])
+HIT_DTYPE = np.dtype([("id", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3)])
+assert RAY_DTYPE.itemsize == 24 and SEGMENT_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 32
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -67,6 +72,8 @@ EXPORTED = [
     "rtg_multi_create", "rtg_multi_set_scene", "rtg_multi_render", "rtg_multi_destroy",
     "rtg_multi_set_gather", "rtg_place_shard_device",
     "rtg_gbuffer_device", "rtg_gbuffer", "rtg_gbuffer_host",
+    "rtg_intersect_device", "rtg_intersect", "rtg_intersect_host",
+    "rtg_visible_device", "rtg_visible", "rtg_visible_host",
 ]
 
 
@@ -148,6 +155,10 @@ def lib() -> ctypes.CDLL:
         L.rtg_gbuffer_device.argtypes = [vp, u, u, f, f, u, u, u, vp, vp]
         L.rtg_gbuffer.argtypes = [i, vp, u, u, u, f, f, vp]
         L.rtg_gbuffer_host.argtypes = [vp, u, u, u, f, f, vp, i]
+        for q in ("intersect", "visible"):
+            getattr(L, f"rtg_{q}_device").argtypes = [vp, vp, sz, vp, vp]
+            getattr(L, f"rtg_{q}").argtypes = [i, vp, u, vp, sz, vp]
+            getattr(L, f"rtg_{q}_host").argtypes = [vp, u, vp, sz, vp, i, i]
 
         pu = ctypes.POINTER(u)
         L.rtg_scene_load.argtypes = [ctypes.c_char_p, vp, u, pu, vp, u, pu]
@@ -317,6 +328,63 @@ def gbuffer_host(spheres, width: int, height: int, zoom: float = -4.0,
     out = np.empty((height, width), GBUF_DTYPE)
     _check(lib().rtg_gbuffer_host(_ptr(spheres), len(spheres), width, height, float(zoom),
                                   float(alias_factor), _ptr(out), threads), "rtg_gbuffer_host")
+    return out
+
+
+def _batch(records, dtype, out_dtype):
+    """A batch as a contiguous 1-D record array (an (N, 6) float32 array is
+    taken as N records), its length, and the result array with pointers that
+    are never null (an empty batch is legal: RTG_OK, nothing written)."""
+    a = np.asarray(records)
+    if a.dtype != dtype:
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 6).view(dtype).reshape(-1)
+    a = np.ascontiguousarray(a).reshape(-1)
+    n = len(a)
+    out = np.empty(n, out_dtype)
+    src = a if n else np.zeros(1, dtype)
+    dst = out if n else np.zeros(1, out_dtype)
+    return src, n, out, dst
+
+
+def intersect(spheres, rays, device: int = 0) -> np.ndarray:
+    """Closest hit of every ray of a batch on the GPU (rtg_intersect): RAY_DTYPE
+    records (or an (N, 6) float32 array: origin, dir) in, HIT_DTYPE records out,
+    calcIntersection's answer bit for bit.  Directions are used as given."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    src, n, out, dst = _batch(rays, RAY_DTYPE, HIT_DTYPE)
+    _check(lib().rtg_intersect(device, _ptr(spheres), len(spheres), _ptr(src), n, _ptr(dst)),
+           "rtg_intersect")
+    return out
+
+
+def intersect_host(spheres, rays, walk: int = 0, threads: int = 1) -> np.ndarray:
+    """The same on the host (rtg_intersect_host; no GPU needed).  walk 0: plain
+    loops over every ray and sphere; walk 1: the device kernel's own query path
+    (BVH, 64-sphere query or flat loop) compiled for the host."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    src, n, out, dst = _batch(rays, RAY_DTYPE, HIT_DTYPE)
+    _check(lib().rtg_intersect_host(_ptr(spheres), len(spheres), _ptr(src), n, _ptr(dst), walk,
+                                    threads), "rtg_intersect_host")
+    return out
+
+
+def visible(spheres, segments, device: int = 0) -> np.ndarray:
+    """Line of sight of every segment of a batch on the GPU (rtg_visible):
+    SEGMENT_DTYPE records (or (N, 6) float32: a, b) in, uint8 out, 1 where
+    hasClearLineOfSight(a, b) holds."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    src, n, out, dst = _batch(segments, SEGMENT_DTYPE, np.uint8)
+    _check(lib().rtg_visible(device, _ptr(spheres), len(spheres), _ptr(src), n, _ptr(dst)),
+           "rtg_visible")
+    return out
+
+
+def visible_host(spheres, segments, walk: int = 0, threads: int = 1) -> np.ndarray:
+    """The same on the host (rtg_visible_host; walk as intersect_host)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    src, n, out, dst = _batch(segments, SEGMENT_DTYPE, np.uint8)
+    _check(lib().rtg_visible_host(_ptr(spheres), len(spheres), _ptr(src), n, _ptr(dst), walk,
+                                  threads), "rtg_visible_host")
     return out
 
 
@@ -491,6 +559,23 @@ class Context:
                                         ctypes.c_void_p(dst_ptr),
                                         ctypes.c_void_p(stream) if stream else None),
                "rtg_gbuffer_device")
+
+    def intersect_device(self, rays_ptr: int, n: int, dst_ptr: int, stream: int = 0):
+        """Closest hits of n rays at rays_ptr (device, 24-byte RAY_DTYPE records:
+        an (N, 6) float32 tensor) into dst_ptr (device, 32-byte HIT_DTYPE records,
+        16-byte aligned: an (N, 8) int32 tensor), asynchronously on `stream`."""
+        _check(lib().rtg_intersect_device(self._h, ctypes.c_void_p(rays_ptr), n,
+                                          ctypes.c_void_p(dst_ptr),
+                                          ctypes.c_void_p(stream) if stream else None),
+               "rtg_intersect_device")
+
+    def visible_device(self, segs_ptr: int, n: int, dst_ptr: int, stream: int = 0):
+        """Line of sight of n segments at segs_ptr (device, 24-byte SEGMENT_DTYPE
+        records) into dst_ptr (device, one uint8 per segment: 1 visible)."""
+        _check(lib().rtg_visible_device(self._h, ctypes.c_void_p(segs_ptr), n,
+                                        ctypes.c_void_p(dst_ptr),
+                                        ctypes.c_void_p(stream) if stream else None),
+               "rtg_visible_device")
 
     def render_rows_device(self, width, height, rows_ptr: int, n_rows: int, dst_ptr: int,
                            zoom=-4.0, alias_factor=3.0, stack_size=6, stream: int = 0):

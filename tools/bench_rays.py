@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE]
+
+Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
+with the scene and the rays resident, on three batches of bench.py's frames:
+
+  c3_ordered    the C3 scene (16 spheres), the 3840 x 2160 aa = 1 primary rays
+                in pixel order
+  c5_ordered    the C5 scene (1024 spheres, the BVH), the same rays
+  c5_shuffled   the C5 scene, those rays in a seeded random permutation
+
+Device events around back-to-back launches on one stream (a window of about
+0.3 s), after a warm-up; medians over the rounds.  Writes FILE (default
+profiles/rays/bench.json) with ms and Mrays/s of the three, the ordered /
+shuffled ratio on C5 (the coherence sensitivity rtg.h mentions) and one
+sanity relation, reported and not gated: rtg_gbuffer_device of the C3 frame
+at aa = 1, timed in the same process round by round.  The ray query has no
+primary cull (group_sel), so it is expected to be the slower of the two.
+--parent-json FILE stores that file's object under "parent_commit" (the same
+measurements taken on the parent commit's build, for the side-by-side).
+The tool also checks that the ordered C3 hits are the G-buffer's (id, t,
+normal) and that the shuffled hits are the ordered ones permuted.  GPU only.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "raytracer-gamma_amd"))
+sys.path.insert(0, ROOT)
+import rtg_amd as R  # noqa: E402
+from bench import CONFIGS  # noqa: E402
+
+F = np.float32
+
+
+def primary_rays(W, H, zoom=-4.0):
+    """The aa = 1 primary rays of a W x H frame (main.cpp:384-436) in float32,
+    pixel order: origin 0, direction vnorm((x, y, zoom))."""
+    xs, ys, asp = F(16) / F(W), F(12) / F(H), F(16) / F(12)
+    halfW, halfH = F(W) * F(0.5), F(H) * F(0.5)
+    y, x = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    vx = ((x.astype(F) - halfW) * xs) * asp
+    vy = (halfH - y.astype(F)) * ys
+    vz = np.full(x.shape, F(zoom))
+    l = F(1) / np.sqrt((vx * vx + vy * vy) + vz * vz)
+    out = np.zeros((H * W, 6), F)
+    out[:, 3], out[:, 4], out[:, 5] = (l * vx).ravel(), (l * vy).ravel(), (l * vz).ravel()
+    return out
+
+
+def timed(fn, stream, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(reps):
+        fn()
+    e1.record(stream)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def measure(fns, rounds, window_ms=300.0):
+    """Median, min and max ms per launch of each fn, interleaved round by round."""
+    s = torch.cuda.current_stream()
+    reps = []
+    for fn in fns:
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        reps.append(max(3, min(2000, int(window_ms / max(timed(fn, s, 2), 1e-3)))))
+    t = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            t[k].append(timed(fn, s, reps[k]))
+    return [{"ms_median": round(float(np.median(v)), 5), "ms_min": round(min(v), 5),
+             "ms_max": round(max(v), 5), "launches_per_round": r} for v, r in zip(t, reps)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rays", "bench.json"))
+    ap.add_argument("--parent-json", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_rays: needs a GPU")
+    W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
+    assert (W, H) == CONFIGS["c5"][:2]
+    n = W * H
+    rays_np = primary_rays(W, H)
+    perm = np.random.default_rng(42).permutation(n)
+    rays = torch.from_numpy(rays_np).cuda()
+    shuffled = torch.from_numpy(rays_np[perm]).cuda()
+    hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+    hits2 = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+    gb = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"W": W, "H": H, "rays": n, "device": R.device_info(0), "rounds": args.rounds,
+           "batches": {}}
+
+    def rate(m):
+        m["Mrays_per_s"] = round(n / (m["ms_median"] * 1e-3) / 1e6, 1)
+        return m
+
+    # C3: ordered batch and the G-buffer at aa = 1 of the same frame
+    sph, lg = R.generate_scene(CONFIGS["c3"][2], CONFIGS["c3"][3], 42)
+    ctx = R.Context(0)
+    ctx.set_scene(sph, lg)
+    q, g = measure([lambda: ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream),
+                    lambda: ctx.gbuffer_device(W, H, gb.data_ptr(), alias_factor=1.0,
+                                               stream=stream)], args.rounds)
+    ctx.close()
+    res["batches"]["c3_ordered"] = rate(q)
+    same = bool((hits[:, :2] == gb[:, :2]).all() and (hits[:, 5:8] == gb[:, 4:7]).all())
+    res["gbuffer_aa1_c3"] = dict(g, intersect_over_gbuffer=round(q["ms_median"] / g["ms_median"], 3),
+                                 hits_equal_gbuffer=same,
+                                 hit_rays=int((hits[:, 0] >= 0).sum()))
+
+    # C5: ordered and shuffled
+    sph, lg = R.generate_scene(CONFIGS["c5"][2], CONFIGS["c5"][3], 42)
+    ctx = R.Context(0)
+    ctx.set_scene(sph, lg)
+    o, s = measure([lambda: ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream),
+                    lambda: ctx.intersect_device(shuffled.data_ptr(), n, hits2.data_ptr(), stream)],
+                   args.rounds)
+    ctx.close()
+    res["batches"]["c5_ordered"] = rate(o)
+    res["batches"]["c5_shuffled"] = rate(s)
+    res["c5_shuffled_over_ordered"] = round(s["ms_median"] / o["ms_median"], 3)
+    permuted = bool((hits[torch.from_numpy(perm).cuda()] == hits2).all())
+    res["c5_shuffled_hits_are_ordered_permuted"] = permuted
+    res["c5_hit_rays"] = int((hits[:, 0] >= 0).sum())
+    if args.parent_json:
+        with open(args.parent_json) as f:
+            res["parent_commit"] = json.load(f)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res), flush=True)
+    sys.exit(0 if same and permuted else 1)
+
+
+if __name__ == "__main__":
+    main()
