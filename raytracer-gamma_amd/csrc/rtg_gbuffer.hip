@@ -24,12 +24,8 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <functional>
-#include <thread>
-#include <vector>
-
 #include "rtg.h"
-#include "rtg_internal.h"
+#include "rtg_entry.h"
 #include "rtg_trace_kernels.h"
 #include "rtg_scene_pack.h"
 
@@ -38,16 +34,6 @@ static_assert(offsetof(rtg_gbuf_px, t) == 4 && offsetof(rtg_gbuf_px, hits) == 8 
                   offsetof(rtg_gbuf_px, sample) == 12 && offsetof(rtg_gbuf_px, normal) == 16 &&
                   offsetof(rtg_gbuf_px, idSum) == 28,
               "rtg_gbuf_px layout (two 16-byte halves)");
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      rtg_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                    __LINE__);                                                     \
-      return RTG_ERR_HIP;                                                          \
-    }                                                                              \
-  } while (0)
 
 namespace rtg {
 
@@ -71,17 +57,12 @@ RTG_HD void gbuf_take(GbufAcc& r, int id, float t, unsigned s) {
     }
   }
 }
-RTG_HD unsigned gbuf_bits(float v) {  // NaN as the frame's NaNs (rtg.h)
-  unsigned u;
-  memcpy(&u, &v, 4);
-  return (v != v) ? 0xFFC00000u : u;
-}
-// The finished record of pixel (x, gy) as two 16-byte halves; the normal is
+// The finished record of pixel (x, gy) as its eight words; the normal is
 // the shading normal of the winning hit only (raytracer.h:464-468: P = o +
 // t d with o = (0,0,0), N = vnorm(P - c)).
 template <class Scene>
 RTG_HD void gbuf_record(const Scene& sc, const Camera& cam, unsigned x, unsigned gy,
-                        const GbufAcc& r, unsigned* lo, unsigned* hi) {
+                        const GbufAcc& r, unsigned* w) {
   V3 N = v3(0.f, 0.f, 0.f);
   if (r.id >= 0) {
     const unsigned nAA = (unsigned)cam.nAA;
@@ -92,30 +73,19 @@ RTG_HD void gbuf_record(const Scene& sc, const Camera& cam, unsigned x, unsigned
     const V3 P = vadd(v3(0.f, 0.f, 0.f), vsmul(r.t, d));
     N = vnorm(vsub(P, c));
   }
-  lo[0] = (unsigned)r.id;
-  lo[1] = gbuf_bits(r.t);
-  lo[2] = r.hits;
-  lo[3] = r.sample;
-  hi[0] = gbuf_bits(N.x);
-  hi[1] = gbuf_bits(N.y);
-  hi[2] = gbuf_bits(N.z);
-  hi[3] = r.idSum;
+  w[0] = (unsigned)r.id;
+  w[1] = nan_bits(r.t);
+  w[2] = r.hits;
+  w[3] = r.sample;
+  w[4] = nan_bits(N.x);
+  w[5] = nan_bits(N.y);
+  w[6] = nan_bits(N.z);
+  w[7] = r.idSum;
 }
 
-// The caller's sphere array as a Scene of closest_hit: r*r as raySphere
-// forms it (raytracer.h:100).
-struct HostSpheres {
-  const rtg_sphere* s;
-  unsigned n;
-  V3 sphere(unsigned i, float& r2) const {
-    r2 = s[i].radius * s[i].radius;
-    return v3(s[i].pos.x, s[i].pos.y, s[i].pos.z);
-  }
-};
-
-static void gbuffer_host_rows(const HostSpheres& sc, const Camera& cam, unsigned W, unsigned y0,
-                              unsigned y1, rtg_gbuf_px* dst) {
-  for (unsigned y = y0; y < y1; ++y)
+static void gbuffer_host_rows(const HostSpheres& sc, const Camera& cam, unsigned W, size_t y0,
+                              size_t y1, rtg_gbuf_px* dst) {
+  for (unsigned y = (unsigned)y0; y < y1; ++y)
     for (unsigned x = 0; x < W; ++x) {
       GbufAcc r;
       for (int i = 0; i < cam.nAA; ++i)
@@ -126,39 +96,15 @@ static void gbuffer_host_rows(const HostSpheres& sc, const Camera& cam, unsigned
           gbuf_take(r, id, t, (unsigned)(i * cam.nAA + j));
         }
       unsigned w[8];
-      gbuf_record(sc, cam, x, y, r, w, w + 4);
+      gbuf_record(sc, cam, x, y, r, w);
       memcpy(&dst[(size_t)y * W + x], w, sizeof w);
     }
 }
 
-// The trace kernels' scene over the context's tables (global memory, scalar
-// loads for wave-uniform indices), without frames; `stk`: the wave's BVH
-// traversal stack in LDS.
+// The trace kernels' scene over the context's tables (bind_scene: global
+// memory, scalar loads for wave-uniform indices), without frames.
 template <bool kBvh>
 using GbufScene = DevScene<false, 64, kBvh, kFusePrim>;
-
-template <bool kBvh>
-__device__ __forceinline__ void gbuf_scene(const KernelArgs& a, GbufScene<kBvh>& sc, int* stk) {
-  sc.lfr = nullptr;
-  sc.nfl = 0;
-  sc.geom = (cfloat_p)a.geom;
-  sc.crad2 = (cfloat_p)a.crad2;
-  sc.mats = (cfloat_p)a.mats;
-  sc.lgeom = reinterpret_cast<const float4*>(a.geom);
-  sc.lights = (cfloat_p)a.lights;
-  sc.smask = (cuint_p)a.smask;
-  sc.cone = (cuint_p)a.cone;
-  sc.prim = (cfloat_p)a.prim;
-  sc.bvhNodes = (cfloat_p)a.bvhNodes;
-  sc.bvhStk = stk;
-  sc.capRec = (cfloat_p)a.capRec;
-  sc.capOff = (cuint_p)a.capOff;
-  sc.ovRec = (cfloat_p)a.ovRec;
-  sc.ovOff = (cuint_p)a.ovOff;
-  sc.n = a.n;
-  sc.m = a.m;
-  sc.n4 = a.n4;
-}
 
 // The closest hit of a primary ray of a scene without a usable sphere mask:
 // the BVH when the scene has one (kBvh), else every sphere, four per step.
@@ -167,13 +113,6 @@ __device__ __forceinline__ int gbuf_closest(const GbufScene<kBvh>& sc, V3 d, flo
   const V3 o = v3(0.f, 0.f, 0.f);
   if constexpr (kBvh) return closest_bvh(sc, make_query(o, d), t);
   else return closest_hit4(sc, o, d, t);
-}
-
-__device__ __forceinline__ void gbuf_store(rtg_gbuf_px* px, const unsigned* lo,
-                                           const unsigned* hi) {
-  uint4* o = reinterpret_cast<uint4*>(px);  // 16-byte aligned (rtg_gbuffer_device)
-  o[0] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  o[1] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
 }
 
 // Order the wave's LDS accesses before and after this point.
@@ -226,9 +165,9 @@ __device__ __forceinline__ void gbuf_group(const KernelArgs& a, const GbufScene<
     const unsigned base = pl * SP;  // base + SP <= 64: pl < PPW
     GbufAcc r;
     for (unsigned k = 0; k < SP; ++k) gbuf_take(r, sId[base + k], sT[base + k], k);
-    unsigned lo[4], hi[4];
-    gbuf_record(sc, a.cam, x, gy, r, lo, hi);
-    gbuf_store(dst + p, lo, hi);  // p < total: inside the shard's records
+    unsigned w[8];
+    gbuf_record(sc, a.cam, x, gy, r, w);
+    store_record(dst + p, w);  // p < total: inside the shard's records
   }
   gbuf_wave_sync();  // the next group parks its samples in the same slots
 }
@@ -250,14 +189,14 @@ __global__ __launch_bounds__(64) void gbuffer_samples_kernel(const KernelArgs a,
   __shared__ int sId[64];
   __shared__ int stk[kBvh ? 64 : 1];
   GbufScene<kBvh> sc;
-  gbuf_scene<kBvh>(a, sc, stk);
+  bind_scene_no_frames(sc, a.scene, stk);  // stk: the wave's BVH traversal stack
   const unsigned lane = threadIdx.x;
   const unsigned nAA = (unsigned)a.cam.nAA;
   const unsigned PPW = 64u / (nAA * nAA);
   const size_t total = (size_t)a.W * a.rowsLocal;
   const size_t g0 = (size_t)blockIdx.x * 64;  // the wave's first group
   const size_t g = g0 + lane;
-  const bool masked = !kBvh && a.n <= 64;
+  const bool masked = !kBvh && a.scene.n <= 64;
   uint64_t sel = 0;
   if (masked && g < groups) sel = group_sel(a, g, PPW, total);
   const uint64_t live = __ballot(g < groups && (!masked || sel != 0ull));
@@ -293,7 +232,7 @@ __global__ __launch_bounds__(64) void gbuffer_pixels_kernel(const KernelArgs a, 
                                                             rtg_gbuf_px* __restrict__ dst) {
   __shared__ int stk[kBvh ? 64 : 1];
   GbufScene<kBvh> sc;
-  gbuf_scene<kBvh>(a, sc, stk);
+  bind_scene_no_frames(sc, a.scene, stk);  // stk: the wave's BVH traversal stack
   const size_t total = (size_t)a.W * a.rowsLocal;
   const size_t p = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (p >= total) return;
@@ -309,9 +248,9 @@ __global__ __launch_bounds__(64) void gbuffer_pixels_kernel(const KernelArgs a, 
       const int id = gbuf_closest<kBvh>(sc, dir, t);
       gbuf_take(r, id, t, (unsigned)(i * nAA + j));
     }
-  unsigned lo[4], hi[4];
-  gbuf_record(sc, a.cam, x, gy, r, lo, hi);
-  gbuf_store(dst + p, lo, hi);
+  unsigned w[8];
+  gbuf_record(sc, a.cam, x, gy, r, w);
+  store_record(dst + p, w);
 }
 
 }  // namespace rtg
@@ -344,19 +283,9 @@ int rtg_gbuffer_host(const rtg_sphere* spheres, unsigned sphNum, unsigned width,
                                     &cam);
   if (rc) return rc;
   const HostSpheres sc{spheres, sphNum};
-  unsigned nt = nthreads > 0 ? (unsigned)nthreads : 1u;
-  if (nt > height) nt = height;
-  if (nt == 1) {
-    gbuffer_host_rows(sc, cam, width, 0, height, dstHost);
-    return RTG_OK;
-  }
-  std::vector<std::thread> pool;
-  for (unsigned k = 0; k < nt; ++k) {  // contiguous row bands
-    const unsigned y0 = (unsigned)((uint64_t)height * k / nt);
-    const unsigned y1 = (unsigned)((uint64_t)height * (k + 1) / nt);
-    pool.emplace_back(gbuffer_host_rows, std::cref(sc), std::cref(cam), width, y0, y1, dstHost);
-  }
-  for (auto& th : pool) th.join();
+  host_bands(height, nthreads, [&](size_t y0, size_t y1) {  // contiguous row bands
+    gbuffer_host_rows(sc, cam, width, y0, y1, dstHost);
+  });
   return RTG_OK;
 }
 
@@ -367,7 +296,7 @@ int rtg_gbuffer_device(rtg_context* ctx, unsigned width, unsigned height, float 
   rtg_clear_error();
   KernelArgs a{};
   int device = 0;
-  if (!rtg_context_scene(ctx, &a, &device)) {
+  if (!rtg_context_scene(ctx, &a.scene, &device)) {
     rtg_set_error("gbuffer: no context/scene");
     return RTG_ERR_INVALID;
   }
@@ -405,7 +334,7 @@ int rtg_gbuffer_device(rtg_context* ctx, unsigned width, unsigned height, float 
     rtg_set_error("gbuffer: frame too large (%zu workgroups)", blocks);
     return RTG_ERR_INVALID;
   }
-  const bool bvh = a.bvhNodes != nullptr;
+  const bool bvh = a.scene.bvhNodes != nullptr;
   void (*fn)(const KernelArgs, size_t, rtg_gbuf_px*) =
       sampleKernel ? (bvh ? gbuffer_samples_kernel<true> : gbuffer_samples_kernel<false>)
                    : (bvh ? gbuffer_pixels_kernel<true> : gbuffer_pixels_kernel<false>);
@@ -424,27 +353,12 @@ int rtg_gbuffer(int device, const rtg_sphere* spheres, unsigned sphNum, unsigned
   const int rc0 = check_gbuffer_args(spheres, sphNum, width, height, zoom, aliasFactor, dstHost,
                                      &cam);
   if (rc0) return rc0;
-  rtg_context* ctx = nullptr;
-  int rc = rtg_context_create(device, &ctx);
-  if (rc) return rc;
-  rtg_gbuf_px* d = nullptr;
-  const size_t bytes = (size_t)width * height * sizeof(rtg_gbuf_px);
-  rc = rtg_context_set_scene(ctx, spheres, sphNum, nullptr, 0);
-  if (!rc && hipMalloc(&d, bytes) != hipSuccess) {
-    rtg_set_error("hipMalloc(%zu) failed", bytes);
-    rc = RTG_ERR_NOMEM;
-  }
-  if (!rc) rc = rtg_gbuffer_device(ctx, width, height, zoom, aliasFactor, 16, 0, 1, d, nullptr);
-  if (!rc) {
-    hipError_t e = hipMemcpy(dstHost, d, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rtg_set_error("kernel/readback failed: %s", hipGetErrorString(e));
-      rc = RTG_ERR_HIP;
-    }
-  }
-  (void)hipFree(d);
-  rtg_context_destroy(ctx);
-  return rc;
+  return one_shot(device, spheres, sphNum, nullptr, 0, nullptr, 0, dstHost,
+                  (size_t)width * height * sizeof(rtg_gbuf_px),
+                  [&](rtg_context* ctx, const void*, void* d) {
+                    return rtg_gbuffer_device(ctx, width, height, zoom, aliasFactor, 16, 0, 1,
+                                              (rtg_gbuf_px*)d, nullptr);
+                  });
 }
 
 }  // extern "C"

@@ -22,20 +22,10 @@
 #include <vector>
 
 #include "rtg.h"
-#include "rtg_internal.h"
+#include "rtg_entry.h"
 #include "rtg_trace_kernels.h"
 #include "rtg_rays.h"
 #include "rtg_scene_pack.h"
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      rtg_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                    __LINE__);                                                     \
-      return RTG_ERR_HIP;                                                          \
-    }                                                                              \
-  } while (0)
 
 namespace rtg {
 
@@ -272,20 +262,8 @@ static TraceFn pick_trace(int S, int variant, bool bvh, int list) {
 
 struct rtg_context {
   int device = 0;
-  unsigned n = 0, m = 0, n4 = 0;
-  float4* geom = nullptr;
-  float* crad2 = nullptr;
-  float* mats = nullptr;
-  float* lights = nullptr;
-  unsigned* smask = nullptr;  // shadow masks (null when the scene has none)
-  unsigned* cone = nullptr;   // secondary-ray cone masks (null when none)
-  float* prim = nullptr;      // primary-cull sphere constants
-  float* bvhNodes = nullptr;  // BVH node records (null when the scene has none)
-  rtg::RayBox rayBox{};       // the BVH's origin box, for the batch ray queries (rtg_rays.hip)
-  float* capRec = nullptr;    // sphere lists of BVH scenes (null when none)
-  unsigned* capOff = nullptr;
-  float* ovRec = nullptr;
-  unsigned* ovOff = nullptr;
+  alignas(8) rtg::SceneTables scene{};  // the resident scene's tables (kSceneTables)
+  rtg::RayBox rayBox{};  // the BVH's origin box, for the batch ray queries (rtg_rays.hip)
   unsigned* maxScratch = nullptr;
   unsigned long long* diag = nullptr;  // probe counters of diagnostic variants
   unsigned long long* counts = nullptr;  // unit counters of the counting build (variant 120)
@@ -360,66 +338,89 @@ struct rtg_context {
 
 using namespace rtg;
 
+// The scene's device tables, one row each: PackedScene's vector (of floats or
+// of words), the table's slot in SceneTables, the elements allocated behind
+// the copy (the lists' wide record loads read past the last record) and the
+// name in the error text.  An empty vector means no table: the slot stays null.
+struct SceneTable {
+  std::vector<float> PackedScene::*f;
+  std::vector<unsigned> PackedScene::*u;
+  size_t slot;
+  size_t pad;
+  const char* what;
+  size_t words(const PackedScene& ps) const { return f ? (ps.*f).size() : (ps.*u).size(); }
+  const void* data(const PackedScene& ps) const {
+    return f ? (const void*)(ps.*f).data() : (const void*)(ps.*u).data();
+  }
+  void* get(const SceneTables& t) const {
+    void* p;
+    memcpy(&p, (const char*)&t + slot, sizeof p);
+    return p;
+  }
+  void set(SceneTables& t, void* p) const { memcpy((char*)&t + slot, &p, sizeof p); }
+};
+#define RTG_TABLE_F(name, pad, what) {&PackedScene::name, nullptr, offsetof(SceneTables, name), pad, what}
+#define RTG_TABLE_U(name, what) {nullptr, &PackedScene::name, offsetof(SceneTables, name), 0, what}
+static const SceneTable kSceneTables[] = {
+    RTG_TABLE_F(geom, 0, "scene"),
+    RTG_TABLE_F(crad2, 0, "scene"),
+    RTG_TABLE_F(mats, 0, "scene"),
+    RTG_TABLE_F(lights, 0, "scene"),
+    RTG_TABLE_U(smask, "shadow masks"),
+    RTG_TABLE_U(cone, "cone masks"),
+    RTG_TABLE_F(prim, 0, "the primary-cull constants"),
+    RTG_TABLE_F(bvhNodes, 0, "the BVH"),
+    RTG_TABLE_F(capRec, 4 * kCapWords, "the sphere lists"),
+    RTG_TABLE_U(capOff, "the sphere lists"),
+    RTG_TABLE_F(ovRec, kListWords, "the sphere lists"),
+    RTG_TABLE_U(ovOff, "the sphere lists"),
+};
+#undef RTG_TABLE_F
+#undef RTG_TABLE_U
+
 static void free_scene(rtg_context* c) {
-  (void)hipFree(c->geom);
-  (void)hipFree(c->crad2);
-  (void)hipFree(c->mats);
-  (void)hipFree(c->lights);
-  (void)hipFree(c->smask);
-  (void)hipFree(c->cone);
-  c->cone = nullptr;
-  (void)hipFree(c->prim);
-  c->prim = nullptr;
-  (void)hipFree(c->bvhNodes);
-  (void)hipFree(c->capRec);
-  (void)hipFree(c->capOff);
-  (void)hipFree(c->ovRec);
-  (void)hipFree(c->ovOff);
-  c->capRec = nullptr;
-  c->capOff = nullptr;
-  c->ovRec = nullptr;
-  c->ovOff = nullptr;
-  c->smask = nullptr;
-  c->bvhNodes = nullptr;
-  c->geom = nullptr;
-  c->crad2 = nullptr;
-  c->mats = nullptr;
-  c->lights = nullptr;
+  for (const SceneTable& e : kSceneTables) (void)hipFree(e.get(c->scene));
+  c->scene = SceneTables{};
   c->hasScene = false;
 }
 
-// The resident scene's tables as kernel arguments.
-static void scene_args(const rtg_context* ctx, KernelArgs* a) {
-  a->geom = ctx->geom;
-  a->crad2 = ctx->crad2;
-  a->mats = ctx->mats;
-  a->lights = ctx->lights;
-  a->smask = ctx->smask;
-  a->cone = ctx->cone;
-  a->prim = ctx->prim;
-  a->bvhNodes = ctx->bvhNodes;
-  a->capRec = ctx->capRec;
-  a->capOff = ctx->capOff;
-  a->ovRec = ctx->ovRec;
-  a->ovOff = ctx->ovOff;
-  a->n = ctx->n;
-  a->m = ctx->m;
-  a->n4 = ctx->n4;
+bool rtg_context_scene(const rtg_context* ctx, SceneTables* t, int* device, RayBox* box) {
+  if (!ctx || !ctx->hasScene) return false;
+  *t = ctx->scene;
+  *device = ctx->device;
+  if (box) *box = ctx->rayBox;
+  return true;
 }
 
-// A context's device and resident scene for the launchers of other
-// translation units (rtg_gbuffer.hip); false when it has no scene.
-bool rtg_context_scene(const rtg_context* ctx, KernelArgs* a, int* device) {
-  if (!ctx || !ctx->hasScene) return false;
-  scene_args(ctx, a);
-  *device = ctx->device;
-  return true;
-}
-// The same with the BVH's origin box (rtg_rays.hip).
-bool rtg_context_ray_scene(const rtg_context* ctx, KernelArgs* a, RayBox* box, int* device) {
-  if (!rtg_context_scene(ctx, a, device)) return false;
-  *box = ctx->rayBox;
-  return true;
+int rtg::one_shot(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+                  unsigned lgtNum, const void* in, size_t inBytes, void* out, size_t outBytes,
+                  const std::function<int(rtg_context*, const void*, void*)>& launch) {
+  rtg_context* ctx = nullptr;
+  int rc = rtg_context_create(device, &ctx);
+  if (rc) return rc;
+  void *dIn = nullptr, *dOut = nullptr;
+  rc = rtg_context_set_scene(ctx, spheres, sphNum, lights, lgtNum);
+  if (!rc && ((inBytes && hipMalloc(&dIn, inBytes) != hipSuccess) ||
+              hipMalloc(&dOut, outBytes ? outBytes : 4) != hipSuccess)) {
+    rtg_set_error("hipMalloc(%zu + %zu) failed", inBytes, outBytes);
+    rc = RTG_ERR_NOMEM;
+  }
+  if (!rc && inBytes && hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess) {
+    rtg_set_error("upload of %zu bytes failed", inBytes);
+    rc = RTG_ERR_HIP;
+  }
+  if (!rc) rc = launch(ctx, dIn, dOut);
+  if (!rc) {
+    hipError_t e = hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+      rtg_set_error("kernel/readback failed: %s", hipGetErrorString(e));
+      rc = RTG_ERR_HIP;
+    }
+  }
+  (void)hipFree(dIn);
+  (void)hipFree(dOut);
+  rtg_context_destroy(ctx);
+  return rc;
 }
 
 // Argument checks shared by the one-shot entry points (no HIP call made).
@@ -718,94 +719,39 @@ int rtg_context_set_scene(rtg_context* ctx, const rtg_sphere* spheres, unsigned 
   PackedScene ps;
   pack_scene(spheres, sphNum, lights, lgtNum, &ps);
   const auto tUp = clk::now();
-  std::vector<float4> geom(ps.geom.size() / 4);
-  memcpy(geom.data(), ps.geom.data(), ps.geom.size() * sizeof(float));
-  const std::vector<float>& crad2 = ps.crad2;
-  const std::vector<float>& mats = ps.mats;
-  const std::vector<float>& lg = ps.lights;
-  if (hipMalloc(&ctx->geom, geom.size() * sizeof(float4)) != hipSuccess ||
-      hipMalloc(&ctx->crad2, crad2.size() * sizeof(float)) != hipSuccess ||
-      hipMalloc(&ctx->mats, mats.size() * sizeof(float)) != hipSuccess ||
-      hipMalloc(&ctx->lights, lg.size() * sizeof(float)) != hipSuccess) {
-    free_scene(ctx);
-    rtg_set_error("hipMalloc failed for scene");
-    return RTG_ERR_NOMEM;
-  }
-  HIP_TRY(hipMemcpy(ctx->geom, geom.data(), geom.size() * sizeof(float4),
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->crad2, crad2.data(), crad2.size() * sizeof(float),
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->mats, mats.data(), mats.size() * sizeof(float),
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->lights, lg.data(), lg.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (!ps.smask.empty()) {
-    if (hipMalloc(&ctx->smask, ps.smask.size() * sizeof(unsigned)) != hipSuccess) {
-      free_scene(ctx);
-      rtg_set_error("hipMalloc failed for shadow masks");
-      return RTG_ERR_NOMEM;
+  size_t bytes = 0;
+  for (const SceneTable& e : kSceneTables) {
+    const size_t words = e.words(ps);
+    if (words == 0) continue;
+    void* d = nullptr;
+    int rc = RTG_OK;
+    if (hipMalloc(&d, (words + e.pad) * 4) != hipSuccess) {
+      rtg_set_error("hipMalloc failed for %s", e.what);
+      rc = RTG_ERR_NOMEM;
+    } else {
+      e.set(ctx->scene, d);
+      const hipError_t err = hipMemcpy(d, e.data(ps), words * 4, hipMemcpyHostToDevice);
+      if (err != hipSuccess) {
+        rtg_set_error("upload of %s failed: %s", e.what, hipGetErrorString(err));
+        rc = RTG_ERR_HIP;
+      }
     }
-    HIP_TRY(hipMemcpy(ctx->smask, ps.smask.data(), ps.smask.size() * sizeof(unsigned),
-                      hipMemcpyHostToDevice));
-  }
-  if (hipMalloc(&ctx->prim, ps.prim.size() * sizeof(float)) != hipSuccess) {
-    free_scene(ctx);
-    rtg_set_error("hipMalloc failed for the primary-cull constants");
-    return RTG_ERR_NOMEM;
-  }
-  HIP_TRY(hipMemcpy(ctx->prim, ps.prim.data(), ps.prim.size() * sizeof(float),
-                    hipMemcpyHostToDevice));
-  if (!ps.cone.empty()) {
-    if (hipMalloc(&ctx->cone, ps.cone.size() * sizeof(unsigned)) != hipSuccess) {
-      free_scene(ctx);
-      rtg_set_error("hipMalloc failed for cone masks");
-      return RTG_ERR_NOMEM;
+    if (rc) {
+      free_scene(ctx);  // the tables uploaded so far
+      return rc;
     }
-    HIP_TRY(hipMemcpy(ctx->cone, ps.cone.data(), ps.cone.size() * sizeof(unsigned),
-                      hipMemcpyHostToDevice));
+    bytes += words * 4;
   }
-  if (!ps.bvhNodes.empty()) {
-    if (hipMalloc(&ctx->bvhNodes, ps.bvhNodes.size() * sizeof(float)) != hipSuccess) {
-      free_scene(ctx);
-      rtg_set_error("hipMalloc failed for the BVH");
-      return RTG_ERR_NOMEM;
-    }
-    HIP_TRY(hipMemcpy(ctx->bvhNodes, ps.bvhNodes.data(), ps.bvhNodes.size() * sizeof(float),
-                      hipMemcpyHostToDevice));
-  }
-  if (!ps.capOff.empty()) {
-    if (hipMalloc(&ctx->capRec, (ps.capRec.size() + 4 * kCapWords) * sizeof(float)) != hipSuccess ||
-        hipMalloc(&ctx->capOff, ps.capOff.size() * sizeof(unsigned)) != hipSuccess ||
-        hipMalloc(&ctx->ovRec, (ps.ovRec.size() + kListWords) * sizeof(float)) != hipSuccess ||
-        hipMalloc(&ctx->ovOff, ps.ovOff.size() * sizeof(unsigned)) != hipSuccess) {
-      free_scene(ctx);
-      rtg_set_error("hipMalloc failed for the sphere lists");
-      return RTG_ERR_NOMEM;
-    }
-    HIP_TRY(hipMemcpy(ctx->capRec, ps.capRec.data(), ps.capRec.size() * sizeof(float),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->capOff, ps.capOff.data(), ps.capOff.size() * sizeof(unsigned),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->ovRec, ps.ovRec.data(), ps.ovRec.size() * sizeof(float),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->ovOff, ps.ovOff.data(), ps.ovOff.size() * sizeof(unsigned),
-                      hipMemcpyHostToDevice));
-  }
-  ctx->n = sphNum;
-  ctx->m = lgtNum;
-  ctx->n4 = ps.n4;
+  ctx->scene.n = sphNum;
+  ctx->scene.m = lgtNum;
+  ctx->scene.n4 = ps.n4;
   ctx->rayBox = ray_box(ps.originBox);
   ctx->hasScene = true;
   ++ctx->sceneGen;  // new geometry keys: no launch-order feedback from the old scene
   const auto tEnd = clk::now();
   ctx->sceneStats[0] = std::chrono::duration<double, std::milli>(tUp - tPack).count();
   ctx->sceneStats[1] = std::chrono::duration<double, std::milli>(tEnd - tUp).count();
-  ctx->sceneStats[2] = (double)((ps.geom.size() + ps.crad2.size() + ps.mats.size() +
-                                 ps.lights.size() + ps.prim.size() + ps.bvhNodes.size() +
-                                 ps.capRec.size() + ps.ovRec.size()) *
-                                    sizeof(float) +
-                                (ps.smask.size() + ps.cone.size() + ps.capOff.size() +
-                                 ps.ovOff.size()) *
-                                    sizeof(unsigned));
+  ctx->sceneStats[2] = (double)bytes;
   ctx->sceneStats[3] = (double)(ps.bvhNodes.size() / (kBvhWords * kBvhCopies));
   return RTG_OK;
 }
@@ -885,7 +831,7 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
     rtg_set_error("render: null destination");
     return RTG_ERR_INVALID;
   }
-  scene_args(ctx, &a);
+  a.scene = ctx->scene;
   a.W = width;
   a.rowsLocal = rows;
   a.rowBlock = rowBlock ? rowBlock : 1;
@@ -950,7 +896,7 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
     // eight longest-first runs, whole frames in four
     const unsigned nRuns = groups <= kRuns8MaxGroups ? 8u : 4u;
     const size_t listCap = (nRuns / 2) * kListParts * partCap;  // list entries (KernelArgs::groupCap)
-    if (ctx->n <= 64 && listCap < 0xFFFFFFFFull) {
+    if (ctx->scene.n <= 64 && listCap < 0xFFFFFFFFull) {
       listed = true;
       const hipStream_t st = (hipStream_t)stream;
       slotIdx = ctx->nextSlot;  // the ring advances at the commit below
@@ -1051,8 +997,8 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
   }
   // the compacted default kernel of a scene with shadow/overlap and cone masks
   // takes them as compile-time facts (kMasks)
-  const int listKind = !listed ? 0 : (ctx->smask && ctx->cone) ? 2 : 1;
-  TraceFn fn = pick_trace(stackSize, variant, ctx->bvhNodes != nullptr, listKind);
+  const int listKind = !listed ? 0 : (ctx->scene.smask && ctx->scene.cone) ? 2 : 1;
+  TraceFn fn = pick_trace(stackSize, variant, ctx->scene.bvhNodes != nullptr, listKind);
   if (!fn) {
     rtg_set_error("no kernel for stackSize %d (valid: 1..%d), variant %d", stackSize,
                   RTG_MAX_STACK, variant);
@@ -1060,9 +1006,9 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
   }
   // the frame levels the chosen kernel keeps in LDS (its kBvh instantiation
   // keeps one fewer, LdsFramesTop)
-  const bool bvhKernel = ctx->bvhNodes != nullptr && has_bvh_kernel(variant);
+  const bool bvhKernel = ctx->scene.bvhNodes != nullptr && has_bvh_kernel(variant);
   const size_t frameLds = (size_t)frame_lds_levels(stackSize, bvhKernel) * threads * 16;
-  const size_t lds = frameLds + (ctx->bvhNodes ? (size_t)(threads / 64) * 64 * sizeof(int) : 0);
+  const size_t lds = frameLds + (ctx->scene.bvhNodes ? (size_t)(threads / 64) * 64 * sizeof(int) : 0);
   if (ctx->opts.flags & RTG_LAUNCH_TIMELINE) {
     const size_t waves = (size_t)grid.x * grid.y * (threads / 64);
     if (ctx->timelineCap < waves) {
@@ -1174,37 +1120,13 @@ int rtg_render_rows(int device, const rtg_sphere* spheres, unsigned sphNum,
       return RTG_ERR_INVALID;
     }
   if (nRows == 0) return RTG_OK;
-  rtg_context* ctx = nullptr;
-  int rc = rtg_context_create(device, &ctx);
-  if (rc) return rc;
-  rtg_vec* d = nullptr;
-  unsigned* drows = nullptr;
-  const size_t bytes = (size_t)width * nRows * sizeof(rtg_vec);
-  rc = rtg_context_set_scene(ctx, spheres, sphNum, lights, lgtNum);
-  if (!rc && (hipMalloc(&d, bytes) != hipSuccess ||
-              hipMalloc(&drows, nRows * sizeof(unsigned)) != hipSuccess)) {
-    rtg_set_error("hipMalloc failed");
-    rc = RTG_ERR_NOMEM;
-  }
-  if (!rc && hipMemcpy(drows, rows, nRows * sizeof(unsigned), hipMemcpyHostToDevice) !=
-                 hipSuccess) {
-    rtg_set_error("row list upload failed");
-    rc = RTG_ERR_HIP;
-  }
-  if (!rc)
-    rc = rtg_render_rows_device(ctx, width, height, zoom, aliasFactor, stackSize, drows, nRows,
-                                d, nullptr);
-  if (!rc) {
-    hipError_t e = hipMemcpy(dstHost, d, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rtg_set_error("kernel/readback failed: %s", hipGetErrorString(e));
-      rc = RTG_ERR_HIP;
-    }
-  }
-  (void)hipFree(d);
-  (void)hipFree(drows);
-  rtg_context_destroy(ctx);
-  return rc;
+  return one_shot(device, spheres, sphNum, lights, lgtNum, rows, nRows * sizeof(unsigned), dstHost,
+                  (size_t)width * nRows * sizeof(rtg_vec),
+                  [&](rtg_context* ctx, const void* drows, void* d) {
+                    return rtg_render_rows_device(ctx, width, height, zoom, aliasFactor, stackSize,
+                                                  (const unsigned*)drows, nRows, (rtg_vec*)d,
+                                                  nullptr);
+                  });
 }
 
 int rtg_max_colour_device(rtg_context* ctx, const rtg_vec* pixelsDevice, size_t n,
@@ -1326,29 +1248,12 @@ int rtg_render(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg
   int rc0 = check_render_args(spheres, sphNum, lights, lgtNum, width, height, zoom, aliasFactor,
                               stackSize, dstHost);
   if (rc0) return rc0;
-  rtg_context* ctx = nullptr;
-  int rc = rtg_context_create(device, &ctx);
-  if (rc) return rc;
-  rtg_vec* d = nullptr;
-  const size_t bytes = (size_t)width * height * sizeof(rtg_vec);
-  rc = rtg_context_set_scene(ctx, spheres, sphNum, lights, lgtNum);
-  if (!rc && hipMalloc(&d, bytes ? bytes : 4) != hipSuccess) {
-    rtg_set_error("hipMalloc(%zu) failed", bytes);
-    rc = RTG_ERR_NOMEM;
-  }
-  if (!rc)
-    rc = rtg_render_device(ctx, width, height, zoom, aliasFactor, stackSize, 16, 0, 1, d,
-                           nullptr);
-  if (!rc) {
-    hipError_t e = hipMemcpy(dstHost, d, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rtg_set_error("kernel/readback failed: %s", hipGetErrorString(e));
-      rc = RTG_ERR_HIP;
-    }
-  }
-  (void)hipFree(d);
-  rtg_context_destroy(ctx);
-  return rc;
+  return one_shot(device, spheres, sphNum, lights, lgtNum, nullptr, 0, dstHost,
+                  (size_t)width * height * sizeof(rtg_vec),
+                  [&](rtg_context* ctx, const void*, void* d) {
+                    return rtg_render_device(ctx, width, height, zoom, aliasFactor, stackSize, 16,
+                                             0, 1, (rtg_vec*)d, nullptr);
+                  });
 }
 
 }  // extern "C"

@@ -36,7 +36,3 @@ inline RayBox ray_box(const double ob[7]) {
 }
 
 }  // namespace rtg
-
-// rtg_kernel.hip: rtg_context_scene with the scene's origin box.
-bool rtg_context_ray_scene(const rtg_context* ctx, rtg::KernelArgs* a, rtg::RayBox* box,
-                           int* device);

@@ -10,11 +10,14 @@
 // size; the launches take none of rtg_context's render scratch.
 //
 // Query per scene kind, all with the device functions of rtg_trace.h:
-//   BVH scene (KernelArgs::bvhNodes)  the walk below (closest_wide / blocked_wide)
-//   n4 <= 64                          closest_hit64 / blocked64
-//   anything else                     closest_hit4 / blocked (every sphere)
+//   BVH scene (SceneTables::bvhNodes)  the render kernels' walk, widened
+//                                      (closest_bvh<true> / blocked_bvh<true>)
+//   n4 <= 64                           closest_hit64 / blocked64
+//   anything else                      closest_hit4 / blocked (every sphere)
 // The primary-ray masks (group_sel), the shadow, overlap and cone masks and
-// the capsule lists are keyed to the renderer's own rays and are not used.
+// the capsule lists are keyed to the renderer's own rays and are not used:
+// bind_scene binds them like every table, and none of these queries reads
+// them (has_smask / has_cone / has_lists are asked by the shading code only).
 //
 // ORIGINS OUTSIDE B*: the path taken is INFLATION (no flat fallback for finite
 // origins).  The BVH's boxes (build_bvh, bvh_grow, rtg_scene_pack.h) keep every
@@ -37,10 +40,12 @@
 // term covers 3 eps (|plane| + omax).  Every sphere box therefore needs at
 // most
 //   delta = 2^-8 D + 2^-18 [M > omax] M
-// more half-width (ray_delta rounds it up by 1 + 2^-10), and the walk tests
-// every child box as [lo - delta, hi + delta].  A child box is the union of
-// its spheres' grown boxes; the union inflated by delta contains each member
-// inflated by delta, so inner nodes need nothing else.  Roundings on the way:
+// more half-width (ray_delta rounds it up by 1 + 2^-10), and the walk (kWide,
+// bvh_ray_node in rtg_trace.h: the one walk there is, with the render kernels'
+// prune order, slot passes and push order) tests every child box as [lo -
+// delta, hi + delta].  A child box is the union of its spheres' grown boxes;
+// the union inflated by delta contains each member inflated by delta, so
+// inner nodes need nothing else.  Roundings on the way:
 //  * D is taken to RayBox, B* rounded inward, so it can only grow; its
 //    subtractions, squares, sum and v_sqrt_f32 are each within 2^-23
 //    relative, and the factor 1 + 2^-10 on delta covers them;
@@ -102,12 +107,8 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <functional>
-#include <thread>
-#include <vector>
-
 #include "rtg.h"
-#include "rtg_internal.h"
+#include "rtg_entry.h"
 #include "rtg_trace_kernels.h"
 #include "rtg_rays.h"
 #include "rtg_scene_pack.h"
@@ -116,16 +117,6 @@ static_assert(sizeof(rtg_ray) == 24 && sizeof(rtg_segment) == 24, "rays are 24 B
 static_assert(sizeof(rtg_hit) == 32 && offsetof(rtg_hit, t) == 4 && offsetof(rtg_hit, point) == 8 &&
                   offsetof(rtg_hit, normal) == 20,
               "rtg_hit layout (two 16-byte halves)");
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      rtg_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                    __LINE__);                                                     \
-      return RTG_ERR_HIP;                                                          \
-    }                                                                              \
-  } while (0)
 
 namespace rtg {
 
@@ -143,119 +134,6 @@ RTG_HD float ray_delta(const RayBox& B, V3 o, bool& odd) {
   return (0x1p-8f * D + 0x1p-18f * Mo) * (1.0f + 0x1p-10f);
 }
 
-// One node of a widened walk: bvh_ray_node (rtg_trace.h) with every child box
-// taken as [lo - delta, hi + delta] and a per-lane `active`.  kShadow: the
-// shadow query (reach reachT / reachD, lanes leave when `blk`), else the
-// closest-hit query (the reach is the live minT).
-template <bool kShadow, class Scene>
-RTG_HD int ray_node(const Scene& sc, const RayQ& q, const BoxQ& b, float delta, unsigned nd,
-                    unsigned oct, bool active, float dn, float reachT, float reachD, float gap,
-                    float& minT, int& best, bool& blk, BvhStack& st) {
-  BvhRec r;
-  sc.bvh_rec(nd * kBvhCopies + oct, r);
-  int pc[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) pc[k] = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (r.ch[k] < 0) {  // wave-uniform: a sphere slot
-      const float* g = &r.s[6 * k];
-      const V3 c = v3(g[0], g[1], g[2]);
-      const V3 p = vsub(q.o, c);
-      const float xd = fmaf(q.d.x, p.x, fmaf(q.d.y, p.y, q.d.z * p.z));
-      const float p2 = fmaf(p.x, p.x, fmaf(p.y, p.y, p.z * p.z));
-      const float cs = p2 - g[3];
-      const float v = fmaf(xd, xd, fmaf(-q.ap, cs, 0x1p-100f));  // pass1_rad
-      const float rD = kShadow ? reachD : minT * dn;
-      const bool act = kShadow ? (active && !blk) : active;
-      if (act && !beyond(p2, g[5], rD) && !(v < 0.f) && !behind(0.5f * q.den, xd, cs, g[3])) {
-        bool res;
-        const float t = ray_sphere_leaf(q, c, g[4], res);
-        if constexpr (kShadow) take_blocker(t, q.d, gap, blk);
-        else take_closer(t, ~r.ch[k], minT, best);
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (r.ch[k] > 0) {  // a child node: its box widened by the lane's delta
-      const float* g = &r.s[6 * k];
-      float tn;
-      const float rT = kShadow ? reachT : minT;
-      const bool act = kShadow ? (active && !blk) : active;
-      const bool pass =
-          act && slab_pass(b, v3(g[0] - delta, g[1] - delta, g[2] - delta),
-                           v3(g[3] + delta, g[4] + delta, g[5] + delta), rT, tn);
-      if (sc.any(pass)) pc[k] = r.ch[k];
-    }
-  }
-  int nxt = 0;  // slots already front to back: the nearest next, the others pushed far first
-#pragma unroll
-  for (int k = 3; k >= 0; --k) {
-    if (pc[k] > 0) {
-      if (nxt > 0) st.push(nxt);
-      nxt = pc[k];
-    }
-  }
-  return nxt;
-}
-
-// closest_bvh (rtg_trace.h) over the widened boxes; the whole wave enters,
-// `active` lanes query.
-template <class Scene>
-RTG_HD int closest_wide(const Scene& sc, const RayQ& q, float delta, bool active, float& tOut) {
-  float minT = 1000.f;
-  int best = -1;
-  bool blk = false;
-  tOut = minT;
-  if (!sc.any(active)) return best;
-  const float dn = norm_up(q.den * 0.5f);
-  const BoxQ b = make_boxq(q);
-  BvhStack st(sc.bvh_stack());
-  const unsigned oct = query_octant(sc, q);
-  unsigned nd = 0;  // the root
-  for (;;) {        // wave-uniform
-    const int nx = ray_node<false>(sc, q, b, delta, nd, oct, active, dn, 0.f, 0.f, 0.f, minT, best,
-                                   blk, st);
-    if (nx > 0) {
-      nd = (unsigned)nx;
-    } else {
-      if (st.empty()) break;
-      nd = (unsigned)st.pop();
-    }
-  }
-  tOut = minT;
-  return best;
-}
-
-// blocked_bvh (rtg_trace.h) over the widened boxes.  Active lanes have 2 a in
-// the Markstein range, so the reach in ray units is sqrt(gap / a) rounded up.
-template <class Scene>
-RTG_HD bool blocked_wide(const Scene& sc, const RayQ& q, float gap, float delta, bool active) {
-  bool blk = false;
-  float minT = 0.f;
-  int best = 0;
-  if (!sc.any(active)) return blk;
-  const float reachD = norm_up(gap);
-  const float reachT = fminf(sqrt_hw(gap * rcp_hw(q.den * 0.5f)) * (1.0f + 0x1p-18f), 1000.f);
-  const BoxQ b = make_boxq(q);
-  BvhStack st(sc.bvh_stack());
-  const unsigned oct = query_octant(sc, q);
-  unsigned nd = 0;  // the root
-  for (;;) {        // wave-uniform
-    const int nx = ray_node<true>(sc, q, b, delta, nd, oct, active, 0.f, reachT, reachD, gap, minT,
-                                  best, blk, st);
-    if (sc.all(blk || !active)) break;
-    if (nx > 0) {
-      nd = (unsigned)nx;
-    } else {
-      if (st.empty()) break;
-      nd = (unsigned)st.pop();
-    }
-  }
-  return blk;
-}
-
 // calcIntersection for ray (o, d) of an `active` lane; the whole wave enters
 // (kBvh: the walk is wave-uniform).  Inactive lanes get a miss.
 template <bool kBvh, class Scene>
@@ -265,7 +143,7 @@ RTG_HD int ray_closest(const Scene& sc, const RayBox& box, V3 o, V3 d, bool acti
     bool odd;
     const float delta = ray_delta(box, o, odd);
     odd = active && (odd || !q.fast);
-    int id = closest_wide(sc, q, delta, active && !odd, t);
+    int id = closest_bvh<true>(sc, q, t, delta, active && !odd);
     if (sc.any(odd)) {
       if (odd) id = closest_hit4(sc, o, d, t);
     }
@@ -286,7 +164,9 @@ RTG_HD bool ray_blocked(const Scene& sc, const RayBox& box, V3 o, V3 d, float ga
     bool odd;
     const float delta = ray_delta(box, o, odd);
     odd = active && (odd || !q.fast);
-    bool blk = blocked_wide(sc, q, gap, delta, active && !odd);
+    // (active lanes have 2 a in the Markstein range: the walk's reach in ray
+    // units is sqrt(gap / a) rounded up)
+    bool blk = blocked_bvh<true>(sc, q, gap, delta, active && !odd);
     if (sc.any(odd)) {
       if (odd) blk = blocked(sc, o, d, gap);
     }
@@ -298,12 +178,6 @@ RTG_HD bool ray_blocked(const Scene& sc, const RayBox& box, V3 o, V3 d, float ga
   }
 }
 
-RTG_HD unsigned ray_bits(float v) {  // NaN as the frame's NaNs (rtg.h)
-  unsigned u;
-  memcpy(&u, &v, 4);
-  return (v != v) ? 0xFFC00000u : u;
-}
-
 // The hit record of ray (o, d) with closest hit (id, t) as two 16-byte
 // halves; point and normal of the winner (raytracer.h:172-177), c its centre.
 RTG_HD void hit_record(V3 o, V3 d, int id, float t, V3 c, unsigned* w) {
@@ -313,13 +187,13 @@ RTG_HD void hit_record(V3 o, V3 d, int id, float t, V3 c, unsigned* w) {
     N = vnorm(vsub(P, c));
   }
   w[0] = (unsigned)id;
-  w[1] = ray_bits(t);
-  w[2] = ray_bits(P.x);
-  w[3] = ray_bits(P.y);
-  w[4] = ray_bits(P.z);
-  w[5] = ray_bits(N.x);
-  w[6] = ray_bits(N.y);
-  w[7] = ray_bits(N.z);
+  w[1] = nan_bits(t);
+  w[2] = nan_bits(P.x);
+  w[3] = nan_bits(P.y);
+  w[4] = nan_bits(P.z);
+  w[5] = nan_bits(N.x);
+  w[6] = nan_bits(N.y);
+  w[7] = nan_bits(N.z);
 }
 
 // A segment's shadow ray (raytracer.h:279-286): gap before normalising.
@@ -331,22 +205,12 @@ RTG_HD V3 segment_ray(V3 a, V3 b, float& gap) {
 
 // ---- host forms ----
 
-// The caller's sphere array as a Scene of closest_hit / blocked: r*r as
-// raySphere forms it (raytracer.h:100).
-struct RaySpheres {
-  const rtg_sphere* s;
-  unsigned n;
-  V3 sphere(unsigned i, float& r2) const {
-    r2 = s[i].radius * s[i].radius;
-    return v3(s[i].pos.x, s[i].pos.y, s[i].pos.z);
-  }
-};
-
 // The packed tables (pack_scene) as a one-lane Scene of the kernels' queries.
 struct PackedRayScene {
   const float* geom;
   const float* bvhNodes;
   unsigned n, n4;
+  void count(int, long) const {}
   bool all(bool b) const { return b; }
   bool any(bool b) const { return b; }
   V3 first_lane(V3 v) const { return v; }
@@ -382,7 +246,7 @@ static V3 host_centre(const HostRayJob& j, int id) {
 
 static void intersect_host_range(const HostRayJob& j, const rtg_ray* rays, size_t k0, size_t k1,
                                  rtg_hit* hits) {
-  const RaySpheres plain{j.spheres, j.n};
+  const HostSpheres plain{j.spheres, j.n};
   PackedRayScene sc{nullptr, nullptr, 0, 0};
   bool bvh = false;
   if (j.ps) {
@@ -405,7 +269,7 @@ static void intersect_host_range(const HostRayJob& j, const rtg_ray* rays, size_
 
 static void visible_host_range(const HostRayJob& j, const rtg_segment* segs, size_t k0, size_t k1,
                                unsigned char* out) {
-  const RaySpheres plain{j.spheres, j.n};
+  const HostSpheres plain{j.spheres, j.n};
   PackedRayScene sc{nullptr, nullptr, 0, 0};
   bool bvh = false;
   if (j.ps) {
@@ -425,57 +289,21 @@ static void visible_host_range(const HostRayJob& j, const rtg_segment* segs, siz
   }
 }
 
-// Contiguous bands of [0, n) on nthreads threads.
-static void host_bands(size_t n, int nthreads, const std::function<void(size_t, size_t)>& fn) {
-  size_t nt = nthreads > 0 ? (size_t)nthreads : 1;
-  if (nt > n) nt = n;
-  if (nt <= 1) {
-    fn(0, n);
-    return;
-  }
-  std::vector<std::thread> pool;
-  for (size_t k = 0; k < nt; ++k) pool.emplace_back(fn, n * k / nt, n * (k + 1) / nt);
-  for (auto& th : pool) th.join();
-}
-
 // ---- device side ----
 
-// The trace kernels' scene over the context's tables, without frames or
-// masks; `stk`: the wave's BVH traversal stack in LDS.
+// The trace kernels' scene over the context's tables (bind_scene), without
+// frames.
 template <bool kBvh>
 using RayScene = DevScene<false, 64, kBvh, 0>;
 
-template <bool kBvh>
-__device__ __forceinline__ void ray_scene(const KernelArgs& a, RayScene<kBvh>& sc, int* stk) {
-  sc.lfr = nullptr;
-  sc.nfl = 0;
-  sc.geom = (cfloat_p)a.geom;
-  sc.crad2 = (cfloat_p)a.crad2;
-  sc.mats = (cfloat_p)a.mats;
-  sc.lgeom = reinterpret_cast<const float4*>(a.geom);
-  sc.lights = (cfloat_p)a.lights;
-  sc.smask = nullptr;
-  sc.cone = nullptr;
-  sc.prim = (cfloat_p)a.prim;
-  sc.bvhNodes = (cfloat_p)a.bvhNodes;
-  sc.bvhStk = stk;
-  sc.capRec = nullptr;
-  sc.capOff = nullptr;
-  sc.ovRec = nullptr;
-  sc.ovOff = nullptr;
-  sc.n = a.n;
-  sc.m = a.m;
-  sc.n4 = a.n4;
-}
-
 // One lane per ray; n > 0.  Lanes past n take the last ray and stay inactive.
 template <bool kBvh>
-__global__ __launch_bounds__(64) void intersect_kernel(const KernelArgs a, const RayBox box,
+__global__ __launch_bounds__(64) void intersect_kernel(const SceneTables a, const RayBox box,
                                                        const rtg_ray* __restrict__ rays, size_t n,
                                                        rtg_hit* __restrict__ hits) {
   __shared__ int stk[kBvh ? 64 : 1];
   RayScene<kBvh> sc;
-  ray_scene<kBvh>(a, sc, stk);
+  bind_scene_no_frames(sc, a, stk);  // stk: the wave's BVH traversal stack
   const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
   const bool active = k < n;
   const float* r = reinterpret_cast<const float*>(rays + (active ? k : n - 1));  // 24 B
@@ -489,19 +317,17 @@ __global__ __launch_bounds__(64) void intersect_kernel(const KernelArgs a, const
     if (id >= 0) c = sc.sphere_lane((unsigned)id, r2);  // id < n: a scene record
     unsigned w[8];
     hit_record(o, d, id, t, c, w);
-    uint4* out = reinterpret_cast<uint4*>(hits + k);  // 16-byte aligned (rtg_intersect_device)
-    out[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    out[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    store_record(hits + k, w);
   }
 }
 
 template <bool kBvh>
-__global__ __launch_bounds__(64) void visible_kernel(const KernelArgs a, const RayBox box,
+__global__ __launch_bounds__(64) void visible_kernel(const SceneTables a, const RayBox box,
                                                      const rtg_segment* __restrict__ segs,
                                                      size_t n, unsigned char* __restrict__ out) {
   __shared__ int stk[kBvh ? 64 : 1];
   RayScene<kBvh> sc;
-  ray_scene<kBvh>(a, sc, stk);
+  bind_scene_no_frames(sc, a, stk);  // stk: the wave's BVH traversal stack
   const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
   const bool active = k < n;
   const float* r = reinterpret_cast<const float*>(segs + (active ? k : n - 1));  // 24 B
@@ -600,10 +426,10 @@ int rtg_intersect_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
                          rtg_hit* hitsDevice, void* stream) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
-  KernelArgs a{};
+  SceneTables a{};
   RayBox box{};
   int device = 0;
-  if (!rtg_context_ray_scene(ctx, &a, &box, &device)) {
+  if (!rtg_context_scene(ctx, &a, &device, &box)) {
     rtg_set_error("intersect: no context/scene");
     return RTG_ERR_INVALID;
   }
@@ -619,7 +445,7 @@ int rtg_intersect_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
   unsigned blocks;
   const int rc = ray_blocks("intersect", n, &blocks);
   if (rc) return rc;
-  void (*fn)(const KernelArgs, const RayBox, const rtg_ray*, size_t, rtg_hit*) =
+  void (*fn)(const SceneTables, const RayBox, const rtg_ray*, size_t, rtg_hit*) =
       a.bvhNodes ? intersect_kernel<true> : intersect_kernel<false>;
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, raysDevice, n,
@@ -632,10 +458,10 @@ int rtg_visible_device(rtg_context* ctx, const rtg_segment* segsDevice, size_t n
                        unsigned char* outDevice, void* stream) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
-  KernelArgs a{};
+  SceneTables a{};
   RayBox box{};
   int device = 0;
-  if (!rtg_context_ray_scene(ctx, &a, &box, &device)) {
+  if (!rtg_context_scene(ctx, &a, &device, &box)) {
     rtg_set_error("visible: no context/scene");
     return RTG_ERR_INVALID;
   }
@@ -647,45 +473,13 @@ int rtg_visible_device(rtg_context* ctx, const rtg_segment* segsDevice, size_t n
   unsigned blocks;
   const int rc = ray_blocks("visible", n, &blocks);
   if (rc) return rc;
-  void (*fn)(const KernelArgs, const RayBox, const rtg_segment*, size_t, unsigned char*) =
+  void (*fn)(const SceneTables, const RayBox, const rtg_segment*, size_t, unsigned char*) =
       a.bvhNodes ? visible_kernel<true> : visible_kernel<false>;
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, segsDevice, n,
                      outDevice);
   HIP_TRY(hipGetLastError());
   return RTG_OK;
-}
-
-// One-shot body: scene and `inBytes` of input up, `launch` on the context,
-// `outBytes` down.
-static int ray_one_shot(int device, const rtg_sphere* spheres, unsigned sphNum, const void* in,
-                        size_t inBytes, void* out, size_t outBytes,
-                        const std::function<int(rtg_context*, const void*, void*)>& launch) {
-  rtg_context* ctx = nullptr;
-  int rc = rtg_context_create(device, &ctx);
-  if (rc) return rc;
-  void *dIn = nullptr, *dOut = nullptr;
-  rc = rtg_context_set_scene(ctx, spheres, sphNum, nullptr, 0);
-  if (!rc && (hipMalloc(&dIn, inBytes) != hipSuccess || hipMalloc(&dOut, outBytes) != hipSuccess)) {
-    rtg_set_error("hipMalloc(%zu + %zu) failed", inBytes, outBytes);
-    rc = RTG_ERR_NOMEM;
-  }
-  if (!rc && hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess) {
-    rtg_set_error("upload of %zu bytes failed", inBytes);
-    rc = RTG_ERR_HIP;
-  }
-  if (!rc) rc = launch(ctx, dIn, dOut);
-  if (!rc) {
-    hipError_t e = hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rtg_set_error("kernel/readback failed: %s", hipGetErrorString(e));
-      rc = RTG_ERR_HIP;
-    }
-  }
-  (void)hipFree(dIn);
-  (void)hipFree(dOut);
-  rtg_context_destroy(ctx);
-  return rc;
 }
 
 int rtg_intersect(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_ray* rays,
@@ -695,11 +489,10 @@ int rtg_intersect(int device, const rtg_sphere* spheres, unsigned sphNum, const 
   const int rc = check_ray_args("intersect", spheres, sphNum, rays, hitsHost);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
-  return ray_one_shot(device, spheres, sphNum, rays, n * sizeof(rtg_ray), hitsHost,
-                      n * sizeof(rtg_hit), [&](rtg_context* ctx, const void* in, void* out) {
-                        return rtg_intersect_device(ctx, (const rtg_ray*)in, n, (rtg_hit*)out,
-                                                    nullptr);
-                      });
+  return one_shot(device, spheres, sphNum, nullptr, 0, rays, n * sizeof(rtg_ray), hitsHost,
+                  n * sizeof(rtg_hit), [&](rtg_context* ctx, const void* in, void* out) {
+                    return rtg_intersect_device(ctx, (const rtg_ray*)in, n, (rtg_hit*)out, nullptr);
+                  });
 }
 
 int rtg_visible(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_segment* segs,
@@ -709,11 +502,11 @@ int rtg_visible(int device, const rtg_sphere* spheres, unsigned sphNum, const rt
   const int rc = check_ray_args("visible", spheres, sphNum, segs, outHost);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
-  return ray_one_shot(device, spheres, sphNum, segs, n * sizeof(rtg_segment), outHost, n,
-                      [&](rtg_context* ctx, const void* in, void* out) {
-                        return rtg_visible_device(ctx, (const rtg_segment*)in, n,
-                                                  (unsigned char*)out, nullptr);
-                      });
+  return one_shot(device, spheres, sphNum, nullptr, 0, segs, n * sizeof(rtg_segment), outHost, n,
+                  [&](rtg_context* ctx, const void* in, void* out) {
+                    return rtg_visible_device(ctx, (const rtg_segment*)in, n, (unsigned char*)out,
+                                              nullptr);
+                  });
 }
 
 }  // extern "C"

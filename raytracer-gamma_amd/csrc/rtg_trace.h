@@ -613,8 +613,9 @@ RTG_HD int container_list(const Scene& sc, V3 pt, int h, float& nT);
 template <class Scene>
 RTG_HD bool blocked_cap_lanes(const Scene& sc, V3 o, V3 d, float gap, unsigned l, int h,
                               unsigned cell, V3 ch, float r2h, bool& full);
-template <class Scene>
-RTG_HD int closest_bvh(const Scene& sc, const RayQ& q, float& tOut);
+template <bool kWide = false, class Scene>
+RTG_HD int closest_bvh(const Scene& sc, const RayQ& q, float& tOut, float delta = 0.f,
+                       bool active = true);
 // Most distinct spheres a wave walks the per-sphere lists of (blocked_cap_lanes
 // and friends) before its remaining lanes take the BVH.
 #ifndef RTG_LIST_WALKS  // A/B builds only (tools/ab_build.sh EXTRA=-DRTG_LIST_WALKS=N)
@@ -1526,12 +1527,16 @@ struct BvhRec {
 //    slots those the sphere slots left: still conservative (later visits use
 //    them anyway), and a leaf hit in the node can cull its siblings (items
 //    51-52).
-template <class Scene, class Leaf>
+// kWide (the batch ray queries, rtg_rays.hip: origins outside the BVH's origin
+// box): every child box is tested as [lo - delta, hi + delta], delta per lane
+// (ray_delta).  A compile-time flag: without it the boxes are the stored
+// planes themselves, with no vector work added to them.
+template <bool kWide = false, class Scene, class Leaf>
 RTG_HD int bvh_ray_node(const Scene& sc, const RayQ& q, const BoxQ& b, unsigned nd, bool active,
                         float reachT, float reachD, BvhStack& st, Leaf&& leaf,
                         bool shadowQ = false, unsigned oct = 0,
                         const float* liveReach = nullptr, const bool* liveBlk = nullptr,
-                        float liveDn = 0.f) {
+                        float liveDn = 0.f, float delta = 0.f) {
   BvhRec r;
   sc.bvh_rec(nd * kBvhCopies + oct, r);
   int pc[4];
@@ -1542,7 +1547,12 @@ RTG_HD int bvh_ray_node(const Scene& sc, const RayQ& q, const BoxQ& b, unsigned 
     float tn;
     const float rT = liveReach ? *liveReach : reachT;
     const bool act = liveBlk ? (active && !*liveBlk) : active;
-    const bool pass = act && slab_pass(b, v3(g[0], g[1], g[2]), v3(g[3], g[4], g[5]), rT, tn);
+    V3 lo = v3(g[0], g[1], g[2]), hi = v3(g[3], g[4], g[5]);
+    if constexpr (kWide) {
+      lo = v3(lo.x - delta, lo.y - delta, lo.z - delta);
+      hi = v3(hi.x + delta, hi.y + delta, hi.z + delta);
+    }
+    const bool pass = act && slab_pass(b, lo, hi, rT, tn);
     if (pass) sc.count(kUBvhPass, 1);
     if (sc.any(pass)) pc[k] = x;
   };
@@ -1606,10 +1616,17 @@ RTG_HD void take_blocker(float t, V3 d, float gap, bool& blk) {
 
 // Closest hit: the lexicographic minimum of (t, i) over every accepted root
 // below 1000 (minT from 1000, as calcIntersection).
-template <class Scene>
-RTG_HD int closest_bvh(const Scene& sc, const RayQ& q, float& tOut) {
+// kWide: the whole wave enters, only `active` lanes query (the others get a
+// miss), over boxes widened by each lane's `delta` (bvh_ray_node); neither
+// argument is read without it.
+template <bool kWide, class Scene>
+RTG_HD int closest_bvh(const Scene& sc, const RayQ& q, float& tOut, float delta, bool active) {
   float minT = 1000.f;
   int best = -1;
+  if constexpr (kWide) {
+    tOut = minT;
+    if (!sc.any(active)) return best;
+  }
   const float dn = norm_up(q.den * 0.5f);
   const BoxQ b = make_boxq(q);
   BvhStack st(sc.bvh_stack());
@@ -1617,14 +1634,14 @@ RTG_HD int closest_bvh(const Scene& sc, const RayQ& q, float& tOut) {
   unsigned nd = 0;  // the root
   for (;;) {        // wave-uniform
     sc.count(kUBvhNode, 1);
-    const int nx = bvh_ray_node(sc, q, b, nd, true, minT, minT * dn, st,
-                                [&](unsigned i, V3 ce, float r2) {
+    const int nx = bvh_ray_node<kWide>(sc, q, b, nd, kWide ? active : true, minT, minT * dn, st,
+                                       [&](unsigned i, V3 ce, float r2) {
       sc.count(kCntFullCand, 1);
       sc.count(kUBvhExact, 1);
       bool res;
       const float t = ray_sphere_leaf(q, ce, r2, res);
       take_closer(t, (int)i, minT, best);
-    }, false, oct, &minT, nullptr, dn);
+    }, false, oct, &minT, nullptr, dn, delta);
     if (nx > 0) {
       nd = (unsigned)nx;
     } else {
@@ -1639,9 +1656,14 @@ RTG_HD int closest_bvh(const Scene& sc, const RayQ& q, float& tOut) {
 // Shadow ray: blocked iff an accepted root t < 1000 has |t D|^2 < gap, so t
 // < sqrt(gap / a) (1 + 2^-18) covers the float test's rounding; a lane
 // outside the Markstein range (a tiny or huge) keeps the plain t < 1000.
-template <class Scene>
-RTG_HD bool blocked_bvh(const Scene& sc, const RayQ& q, float gap) {
+// kWide: as closest_bvh; a lane that is not `active` is never blocked.
+template <bool kWide = false, class Scene>
+RTG_HD bool blocked_bvh(const Scene& sc, const RayQ& q, float gap, float delta = 0.f,
+                        bool active = true) {
   bool blk = false;
+  if constexpr (kWide) {
+    if (!sc.any(active)) return blk;
+  }
   const float reachD = norm_up(gap);
   float reachT = sqrt_hw(gap * rcp_hw(q.den * 0.5f)) * (1.0f + 0x1p-18f);
   reachT = q.fast ? fminf(reachT, 1000.f) : 1000.f;
@@ -1652,15 +1674,15 @@ RTG_HD bool blocked_bvh(const Scene& sc, const RayQ& q, float gap) {
   unsigned nd = 0;  // the root
   for (;;) {        // wave-uniform
     sc.count(kUBvhNode, 1);
-    const int nx = bvh_ray_node(sc, q, b, nd, !blk, reachT, reachD, st,
-                                [&](unsigned, V3 ce, float r2) {
+    const int nx = bvh_ray_node<kWide>(sc, q, b, nd, kWide ? (active && !blk) : !blk, reachT,
+                                       reachD, st, [&](unsigned, V3 ce, float r2) {
       sc.count(kCntShadowCand, 1);
       sc.count(kUBvhExact, 1);
       bool res;
       const float t = ray_sphere_leaf(q, ce, r2, res);
       take_blocker(t, q.d, gap, blk);
-    }, true, oct, nullptr, &blk);
-    if (sc.all(blk)) break;
+    }, true, oct, nullptr, &blk, 0.f, delta);
+    if (sc.all(kWide ? (blk || !active) : blk)) break;
     if (nx > 0) {
       nd = (unsigned)nx;
     } else {

@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rtg.h"
@@ -489,7 +490,13 @@ constexpr unsigned kStatStride = 16;   // unsigned long long
 struct KernelArgs;
 typedef void (*TraceFn)(const KernelArgs);
 
-struct KernelArgs {
+// The resident scene's device tables (PackedScene's vectors, uploaded by
+// rtg_context_set_scene): what a context holds, what every kernel family gets
+// at the head of its arguments and what bind_scene hands to a DevScene.
+// Packed to 4-byte alignment so that it has no tail padding: KernelArgs::cam
+// follows n4 directly, as the kernels' argument block always had it (the
+// static_asserts below).  Every holder places it at an 8-byte offset.
+struct __attribute__((packed, aligned(4))) SceneTables {
   const float4* geom;
   const float* crad2;
   const float* mats;
@@ -503,6 +510,10 @@ struct KernelArgs {
   const float* ovRec;
   const unsigned* ovOff;
   unsigned n, m, n4;
+};
+
+struct KernelArgs {
+  SceneTables scene;
   Camera cam;
   unsigned W, rowsLocal, rowBlock, shard, nShards;
   double invW, invRowBlock;  // RN(1.0 / W), RN(1.0 / rowBlock) (divmod_u64)
@@ -545,6 +556,42 @@ struct KernelArgs {
   unsigned long long* counts;  // 2 x kCntSlots unit counters (counting build, variant 120)
   uint4* timeline;           // per-wave records (RTG_LAUNCH_TIMELINE) or null
 };
+// The kernels' argument block does not move: the tables, the camera behind
+// n4 without padding, the destination, the end.
+static_assert(sizeof(SceneTables) == 108 && offsetof(KernelArgs, scene) == 0 &&
+                  offsetof(KernelArgs, cam) == 108 && offsetof(KernelArgs, dst) == 192 &&
+                  sizeof(KernelArgs) == 304,
+              "KernelArgs layout");
+
+// Binds scene `sc` (a DevScene) to the tables; `stk`: the wave's 64-entry BVH
+// traversal stack in LDS.  The frame area (lfr, nfl) is the caller's.
+template <class Sc>
+__device__ __forceinline__ void bind_scene(Sc& sc, const SceneTables& t, int* stk) {
+  sc.mats = (cfloat_p)t.mats;
+  sc.lgeom = t.geom;
+  sc.geom = (cfloat_p)t.geom;
+  sc.crad2 = (cfloat_p)t.crad2;
+  sc.lights = (cfloat_p)t.lights;
+  sc.smask = (cuint_p)t.smask;
+  sc.cone = (cuint_p)t.cone;
+  sc.prim = (cfloat_p)t.prim;
+  sc.bvhNodes = (cfloat_p)t.bvhNodes;
+  sc.capRec = (cfloat_p)t.capRec;
+  sc.capOff = (cuint_p)t.capOff;
+  sc.ovRec = (cfloat_p)t.ovRec;
+  sc.ovOff = (cuint_p)t.ovOff;
+  sc.bvhStk = stk;
+  sc.n = t.n;
+  sc.m = t.m;
+  sc.n4 = t.n4;
+}
+// The same for a kernel that keeps no frames in LDS (G-buffer, ray queries).
+template <class Sc>
+__device__ __forceinline__ void bind_scene_no_frames(Sc& sc, const SceneTables& t, int* stk) {
+  sc.lfr = nullptr;
+  sc.nfl = 0;
+  bind_scene(sc, t, stk);
+}
 
 // floor(a / d) for a <= 64, 1 <= d <= 64: (a + 0.5) / d is at least 1/128
 // from an integer, far beyond the float product's error.
@@ -606,10 +653,10 @@ __device__ __forceinline__ uint64_t group_sel(const KernelArgs& a, size_t g, uns
     }
   }
   const PrimBundle pb = primary_bundle(x0, x1, y0, y1, a.cam.zoom);
-  const RTG_CONST float* geom = (const RTG_CONST float*)a.geom;
-  const RTG_CONST float* pc = (const RTG_CONST float*)a.prim;
+  const RTG_CONST float* geom = (const RTG_CONST float*)a.scene.geom;
+  const RTG_CONST float* pc = (const RTG_CONST float*)a.scene.prim;
   uint64_t sel = 0;
-  for (unsigned i = 0; i < a.n; ++i) {  // wave-uniform: scalar sphere records
+  for (unsigned i = 0; i < a.scene.n; ++i) {  // wave-uniform: scalar sphere records
     const RTG_CONST float* r = geom + 4 * i;
     const RTG_CONST float* k = pc + 4 * i;
     if (primary_possible(pb, v3(r[0], r[1], r[2]), k[0], k[1], k[2])) sel |= 1ull << i;
@@ -657,25 +704,10 @@ __device__ __forceinline__ void stage_scene(const KernelArgs& a, Sc& sc) {
   constexpr int NFL = frame_lds_levels(S, Sc::kIsBvh);
   sc.lfr = reinterpret_cast<FrameC*>(lds4) + threadIdx.x;
   sc.nfl = NFL;
-  sc.mats = (cfloat_p)a.mats;
-  sc.lgeom = reinterpret_cast<const float4*>(a.geom);
-  sc.geom = (cfloat_p)a.geom;
-  sc.crad2 = (cfloat_p)a.crad2;
-  sc.lights = (cfloat_p)a.lights;
-  sc.smask = (cuint_p)a.smask;
-  sc.cone = (cuint_p)a.cone;
-  sc.prim = (cfloat_p)a.prim;
-  sc.bvhNodes = (cfloat_p)a.bvhNodes;
-  sc.capRec = (cfloat_p)a.capRec;
-  sc.capOff = (cuint_p)a.capOff;
-  sc.ovRec = (cfloat_p)a.ovRec;
-  sc.ovOff = (cuint_p)a.ovOff;
   // BVH scenes: 64 stack entries per wave after the frames (the launcher adds
   // them to the LDS size).
-  sc.bvhStk = reinterpret_cast<int*>(lds4 + NFL * kThreads) + (threadIdx.x >> 6) * 64;
-  sc.n = a.n;
-  sc.m = a.m;
-  sc.n4 = a.n4;
+  bind_scene(sc, a.scene,
+             reinterpret_cast<int*>(lds4 + NFL * kThreads) + (threadIdx.x >> 6) * 64);
 }
 
 // One 8 x 8 pixel tile per wave: tile (tx, ty) of the shard's local rows.
@@ -697,7 +729,7 @@ __device__ __forceinline__ void trace_tile(const KernelArgs& a, Sc& sc, unsigned
   // per lane against that bundle, then a ballot (see primary_possible).
   uint64_t primSel = ~0ull;
   bool usePrim = false;
-  if (a.n <= 64) {
+  if (a.scene.n <= 64) {
     float x0 = 3.0e38f, x1 = -3.0e38f, y0 = 3.0e38f, y1 = -3.0e38f;
     if (valid) primary_bounds(a.cam, x, gy, x0, x1, y0, y1);
     for (int off = 32; off > 0; off >>= 1) {
@@ -708,7 +740,7 @@ __device__ __forceinline__ void trace_tile(const KernelArgs& a, Sc& sc, unsigned
     }
     const PrimBundle pb = primary_bundle(x0, x1, y0, y1, a.cam.zoom);
     bool possible = false;
-    if (lane < a.n) {
+    if (lane < a.scene.n) {
       const float4 g = sc.lgeom[lane];
       possible = sc.prim_possible(pb, lane, v3(g.x, g.y, g.z));
     }
@@ -848,7 +880,7 @@ __device__ __forceinline__ void trace_group(const KernelArgs& a0, Sc& sc, size_t
   if (hasSel) {
     primSel = gsel;
     usePrim = true;
-  } else if (RTG_PROBE_FLOOR < 2 && !Sc::kIsBvh && a.n <= 64) {  // (BVH scenes: n > 64)
+  } else if (RTG_PROBE_FLOOR < 2 && !Sc::kIsBvh && a.scene.n <= 64) {  // (BVH scenes: n > 64)
     float x0, x1, y0, y1;
     // Wave-uniform: do the wave's valid pixels lie in one row?  Then the
     // bounds are four lanes' values, since every float step of main.cpp:
@@ -877,7 +909,7 @@ __device__ __forceinline__ void trace_group(const KernelArgs& a0, Sc& sc, size_t
     }
     const PrimBundle pb = primary_bundle(x0, x1, y0, y1, a.cam.zoom);
     bool possible = false;
-    if (lane < a.n) {
+    if (lane < a.scene.n) {
       const float4 g = sc.lgeom[lane];
       possible = sc.prim_possible(pb, lane, v3(g.x, g.y, g.z));
     }
@@ -1168,8 +1200,12 @@ RTG_DECL(8) RTG_DECL(9) RTG_DECL(10) RTG_DECL(11) RTG_DECL(12) RTG_DECL(13)
 RTG_DECL(14) RTG_DECL(15) RTG_DECL(16)
 #undef RTG_DECL
 
+struct RayBox;  // rtg_rays.h
+
 }  // namespace rtg
 
-// rtg_kernel.hip: a context's device and the scene tables of its KernelArgs
-// (geom .. n4); false when the context is null or has no scene.
-bool rtg_context_scene(const rtg_context* ctx, rtg::KernelArgs* a, int* device);
+// rtg_kernel.hip: a context's device, its scene tables and, when asked for,
+// the BVH's origin box (the batch ray queries); false when the context is
+// null or has no scene.
+bool rtg_context_scene(const rtg_context* ctx, rtg::SceneTables* t, int* device,
+                       rtg::RayBox* box = nullptr);

@@ -108,6 +108,76 @@ def test_device_equals_plain_loops(R, torch_cuda, name):
         ctx.close()
 
 
+# ---- 6b. waves with no lane in the walk's range ----
+
+def _odd_rays(sph, seed):
+    """64 rays outside the BVH walk's range (rtg_rays.hip, `odd`), k % 4: a
+    zero direction, a NaN / +-inf origin component, direction lengths 2^-40
+    and 2^40 (2 d.d outside [2^-60, 2^60])."""
+    rng = np.random.default_rng(seed)
+    out = raygen.inside(rng, sph, 64).astype(np.float64)
+    unit = out[:, 3:] / np.linalg.norm(out[:, 3:], axis=1, keepdims=True)
+    k = np.arange(64)
+    out[k % 4 == 0, 3:] = 0
+    out[k % 4 == 2, 3:] = unit[k % 4 == 2] * 2.0 ** -40
+    out[k % 4 == 3, 3:] = unit[k % 4 == 3] * 2.0 ** 40
+    bad = np.flatnonzero(k % 4 == 1)
+    out[bad, (bad // 4) % 3] = np.asarray([np.nan, np.inf, -np.inf])[(bad // 12) % 3]
+    out = out.astype(np.float32)
+    o, d = out[:, :3], out[:, 3:].astype(np.float64)
+    a2 = 2.0 * (d * d).sum(1)
+    assert (~(np.abs(o) <= 2.0 ** 56).all(1) | ~((a2 >= 2.0 ** -60) & (a2 <= 2.0 ** 60))).all()
+    return out
+
+
+def _odd_segments(sph, seed):
+    """The same for segments, whose direction is normalised (a length alone
+    puts none outside the range), k % 4: a == b, a NaN / +-inf component of a,
+    one of b, a component of a at +-2^60 (finite, beyond the slab range 2^56)."""
+    rng = np.random.default_rng(seed)
+    out = raygen.inside(rng, sph, 64)
+    out[:, 3:] = raygen.inside(rng, sph, 64)[:, :3]
+    k = np.arange(64)
+    out[k % 4 == 0, 3:] = out[k % 4 == 0, :3]
+    vals = np.asarray([np.nan, np.inf, -np.inf], np.float32)
+    for kind, col0 in ((1, 0), (2, 3)):
+        bad = np.flatnonzero(k % 4 == kind)
+        out[bad, col0 + (bad // 4) % 3] = vals[(bad // 12) % 3]
+    far = np.flatnonzero(k % 4 == 3)
+    out[far, (far // 4) % 3] = np.where(far % 8 == 3, 2.0 ** 60, -2.0 ** 60)
+    with np.errstate(invalid="ignore"):  # inf - inf
+        a, dist = out[:, :3], out[:, 3:].astype(np.float64) - out[:, :3]
+        gap = (dist * dist).sum(1)
+    assert (~(np.abs(a) <= 2.0 ** 56).all(1) | ~np.isfinite(gap) | (gap == 0)).all()
+    return out
+
+
+@pytest.mark.parametrize("name", [200, "c5"])
+def test_waves_outside_the_walks_range(R, torch_cuda, name):
+    """BVH scenes: a wave whose 64 lanes are all outside the walk's range (the
+    walk returns at once, every lane takes the plain loop) followed by a wave
+    with one ordinary ray (the normal walk) in one launch, and the 64 alone;
+    hits and visibility are the host's plain loops, byte for byte, and nothing
+    is written past the batch (_intersect, _visible).  visible_device also
+    takes the ray arrays as segments, as the other tests do."""
+    sph = scene(name)
+    rng = np.random.default_rng(77)
+    rays = np.concatenate([_odd_rays(sph, 31), raygen.inside(rng, sph, 1)])
+    segs = np.concatenate([_odd_segments(sph, 32), raygen.segments(rng, sph, 4)[:1]])
+    ctx = R.Context(0)
+    ctx.set_scene(sph, np.zeros(0, R.LIGHT_DTYPE))
+    try:
+        for n in (65, 64):
+            got = _intersect(R, torch_cuda, ctx, rays[:n])
+            want = R.intersect_host(sph, rays[:n], walk=0)
+            assert got.tobytes() == want.tobytes(), (n, _diff(got, want))
+            for s in (segs[:n], rays[:n]):
+                vis = _visible(R, torch_cuda, ctx, s)
+                assert vis.tobytes() == R.visible_host(sph, s, walk=0).tobytes(), n
+    finally:
+        ctx.close()
+
+
 # ---- 7. primary rays == G-buffer ----
 
 @pytest.mark.parametrize("name", [12, 200])
