@@ -22,6 +22,8 @@
  *                                                      rtg_gbuffer_host
  *   calcIntersection / hasClearLineOfSight for a       rtg_intersect[_device|_host] /
  *     caller's own rays  raytracer.h:145-194, 272-309  rtg_visible[_device|_host]
+ *   rayTrace for a caller's own rays                   rtg_raytrace[_device|_host]
+ *     raytracer.h:410-636
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
  *   output_device_info  device_info.cpp:30             rtg_device_info
  *   parseArguments --list/--device  device_picker.h:70 rtg_device_count / device index args
@@ -310,6 +312,64 @@ int rtg_visible(int device, const rtg_sphere* spheres, unsigned sphNum,
                 const rtg_segment* segs, size_t n, unsigned char* outHost);
 int rtg_visible_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_segment* segs,
                      size_t n, unsigned char* outHost, int walk, int nthreads);
+
+/* ---- batch ray tracing: rayTrace's colour for arbitrary rays ----
+ * The third scene function of the reference, rayTrace itself (raytracer.h:
+ * 410-636), for a buffer of the caller's own rays: a frame from a moved
+ * camera, a reflection probe, a cube map, or the colour along one suspicious
+ * ray.  A buffer of rays goes in, a buffer of colours comes out:
+ *
+ *   dst[k] = rayTrace(spheres, n, lights, m, ray, bgMaterial, 0) with
+ *   ray = {rays[k].origin, rays[k].dir, intensity (1,1,1)} and the background
+ *   material of main.cpp:423-426 (the one every render uses), for stack
+ *   capacity stackSize (RTSTACK_MAXSIZE), bit for bit.
+ *
+ * `dir` is used as given: it is not normalised, and any length is legal.
+ * The value is rayTrace's return before main.cpp:442-445 scales and sums it:
+ * NaN words are written as 0xFFC00000, as the frame's, and a -0 stays -0.
+ * To rebuild a pixel from its nS sample rays, fold them as the reference
+ * does, in float and in sample order:
+ *   pix = 0; for each sample s in order: pix += col[s] * (1 / nS);
+ * (1 / nS is the float quotient 1.f / (aliasFactor * aliasFactor)); with the
+ * sample directions of main.cpp:411-436 that is the render's pixel, bit for
+ * bit.  NaN, infinite and degenerate rays follow the comparisons as written,
+ * as in rtg_intersect.
+ *
+ * The device call follows rtg_context_set_semantics (CPU or OpenCL), as the
+ * renders do; the host call takes the mode as an argument.
+ * rtg_set_launch_opts does not apply.  The device call is asynchronous on
+ * `stream`, takes none of the context's render scratch (group lists, cost
+ * tables, slots) and may be mixed freely with rtg_render_device,
+ * rtg_gbuffer_device and the ray queries on one context; its frames live in
+ * LDS and private memory as in the render kernels.  Rays are independent; the
+ * order of a batch affects speed only (the 64 rays of a wave walk the scene
+ * together).  The call is exact for origins anywhere, at every level of a
+ * ray's tree, because it uses none of the tables the renders keep for their
+ * own camera; a render of the same rays is therefore faster (README).
+ *
+ * n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID with a message, before
+ * any GPU call, for a null buffer, a context without a scene, stackSize
+ * outside 1..RTG_MAX_STACK, an unknown walk or semantics, or a batch of more
+ * than 2^31-1 workgroups (64 rays each).
+ *
+ * Out of scope: a per-ray intensity, a caller-chosen refractive material for
+ * the ray's medium, camera or resolve helpers, multi-GPU batches, and sorting
+ * a batch for coherence. */
+int rtg_raytrace_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
+                        int stackSize, rtg_vec* dstDevice, void* stream);
+/* One-shot: uploads the scene and the rays, runs on `device`, downloads n colours. */
+int rtg_raytrace(int device, const rtg_sphere* spheres, unsigned sphNum,
+                 const rtg_light* lights, unsigned lgtNum, const rtg_ray* rays,
+                 size_t n, int stackSize, rtg_vec* dstHost);
+/* The same on the host, no GPU call.  walk 0: plain loops over every sphere
+ * for every query of every ray's tree (the yardstick).  walk 1: the device
+ * kernel's own path compiled for the host, one ray per "wave", over the scene
+ * tables built as rtg_context_set_scene builds them (as rtg_intersect_host).
+ * semantics: RTG_SEMANTICS_CPU or RTG_SEMANTICS_OPENCL.  nthreads <= 0: 1. */
+int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum,
+                      const rtg_light* lights, unsigned lgtNum, const rtg_ray* rays,
+                      size_t n, int stackSize, int semantics, rtg_vec* dstHost,
+                      int walk, int nthreads);
 
 /* Semantics of a context's renders.  RTG_SEMANTICS_CPU (default) is the
  * reference CPU path (raytracer.h), bit for bit.  RTG_SEMANTICS_OPENCL is the

@@ -384,11 +384,13 @@ static void free_scene(rtg_context* c) {
   c->hasScene = false;
 }
 
-bool rtg_context_scene(const rtg_context* ctx, SceneTables* t, int* device, RayBox* box) {
+bool rtg_context_scene(const rtg_context* ctx, SceneTables* t, int* device, RayBox* box,
+                       int* semantics) {
   if (!ctx || !ctx->hasScene) return false;
   *t = ctx->scene;
   *device = ctx->device;
   if (box) *box = ctx->rayBox;
+  if (semantics) *semantics = ctx->semantics;
   return true;
 }
 

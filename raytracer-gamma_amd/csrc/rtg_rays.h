@@ -1,6 +1,9 @@
-// rtg_rays.h — what the batch ray queries (rtg_rays.hip) share with the
-// context (rtg_kernel.hip): the BVH's origin box as a kernel argument of the
-// ray kernels alone (KernelArgs and the trace kernels do not know it).
+// rtg_rays.h — what the batch ray queries (rtg_rays.hip) and the batch ray
+// tracer (rtg_raytrace.hip, the per-S raytrace kernels) share with each other
+// and with the context (rtg_kernel.hip): the BVH's origin box as a kernel
+// argument of the ray kernels alone (KernelArgs and the trace kernels do not
+// know it), and the two queries that are exact for any origin (the argument is
+// at the head of rtg_rays.hip).
 #pragma once
 
 #include <math.h>
@@ -34,5 +37,81 @@ inline RayBox ray_box(const double ob[7]) {
   b.omax = down(ob[6]);
   return b;
 }
+
+// The extra half-width every BVH box gets for a ray from o (rtg_rays.hip's
+// header); `odd`: the origin is outside the slab arithmetic's range.
+RTG_HD float ray_delta(const RayBox& B, V3 o, bool& odd) {
+  const float ax = fabsf(o.x), ay = fabsf(o.y), az = fabsf(o.z);
+  odd = !(ax <= 0x1p56f && ay <= 0x1p56f && az <= 0x1p56f);  // NaN: odd
+  const float M = fmaxf(ax, fmaxf(ay, az));
+  const float ex = fmaxf(fmaxf(B.lo[0] - o.x, o.x - B.hi[0]), 0.f);
+  const float ey = fmaxf(fmaxf(B.lo[1] - o.y, o.y - B.hi[1]), 0.f);
+  const float ez = fmaxf(fmaxf(B.lo[2] - o.z, o.z - B.hi[2]), 0.f);
+  const float D = sqrt_hw(ex * ex + ey * ey + ez * ez);
+  const float Mo = M > B.omax ? M : 0.f;
+  return (0x1p-8f * D + 0x1p-18f * Mo) * (1.0f + 0x1p-10f);
+}
+
+// calcIntersection for ray (o, d) of an `active` lane; the whole wave enters
+// (kBvh: the walk is wave-uniform).  Inactive lanes get a miss.
+template <bool kBvh, class Scene>
+RTG_HD int ray_closest(const Scene& sc, const RayBox& box, V3 o, V3 d, bool active, float& t) {
+  if constexpr (kBvh) {
+    const RayQ q = make_query(o, d);
+    bool odd;
+    const float delta = ray_delta(box, o, odd);
+    odd = active && (odd || !q.fast);
+    int id = closest_bvh<true>(sc, q, t, delta, active && !odd);
+    if (sc.any(odd)) {
+      if (odd) id = closest_hit4(sc, o, d, t);
+    }
+    return id;
+  } else {
+    t = 1000.f;
+    if (!active) return -1;
+    if (sc.n4 <= 64) return closest_hit64(sc, o, d, t);
+    return closest_hit4(sc, o, d, t);
+  }
+}
+
+// hasClearLineOfSight's blocker search for the ray (o, d) with gap |b - a|^2.
+template <bool kBvh, class Scene>
+RTG_HD bool ray_blocked(const Scene& sc, const RayBox& box, V3 o, V3 d, float gap, bool active) {
+  if constexpr (kBvh) {
+    const RayQ q = make_query(o, d);
+    bool odd;
+    const float delta = ray_delta(box, o, odd);
+    odd = active && (odd || !q.fast);
+    // (active lanes have 2 a in the Markstein range: the walk's reach in ray
+    // units is sqrt(gap / a) rounded up)
+    bool blk = blocked_bvh<true>(sc, q, gap, delta, active && !odd);
+    if (sc.any(odd)) {
+      if (odd) blk = blocked(sc, o, d, gap);
+    }
+    return blk;
+  } else {
+    if (!active) return false;
+    if (sc.n4 <= 64) return blocked64(sc, o, d, gap);
+    return blocked(sc, o, d, gap);
+  }
+}
+
+// The query path of a caller's own ray tree (trace_sample's RP, rtg_trace.h):
+// every node's closest hit and every shadow ray is one of the two queries
+// above, with the delta of that query's own origin.  The lanes of a wave in
+// trace_sample's loop are the ones still tracing, all of them querying.
+template <bool kBvh>
+struct RayPath {
+  static constexpr bool kOn = true;
+  RayBox box;
+  template <class Scene>
+  RTG_HD int closest(const Scene& sc, V3 o, V3 d, float& t) const {
+    return ray_closest<kBvh>(sc, box, o, d, true, t);
+  }
+  template <class Scene>
+  RTG_HD bool blocked(const Scene& sc, V3 o, V3 d, float gap) const {
+    return ray_blocked<kBvh>(sc, box, o, d, gap, true);
+  }
+};
 
 }  // namespace rtg

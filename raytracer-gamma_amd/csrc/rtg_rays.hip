@@ -9,6 +9,10 @@
 // returns early from it.  One translation unit, no instantiation per stack
 // size; the launches take none of rtg_context's render scratch.
 //
+// The two queries themselves (ray_delta, ray_closest, ray_blocked) are in
+// rtg_rays.h, shared with the batch ray tracer (rtg_raytrace.hip), which asks
+// them at every level of a ray's tree; the argument below is theirs.
+//
 // Query per scene kind, all with the device functions of rtg_trace.h:
 //   BVH scene (SceneTables::bvhNodes)  the render kernels' walk, widened
 //                                      (closest_bvh<true> / blocked_bvh<true>)
@@ -119,64 +123,6 @@ static_assert(sizeof(rtg_hit) == 32 && offsetof(rtg_hit, t) == 4 && offsetof(rtg
               "rtg_hit layout (two 16-byte halves)");
 
 namespace rtg {
-
-// The extra half-width every BVH box gets for a ray from o (header); `odd`:
-// the origin is outside the slab arithmetic's range.
-RTG_HD float ray_delta(const RayBox& B, V3 o, bool& odd) {
-  const float ax = fabsf(o.x), ay = fabsf(o.y), az = fabsf(o.z);
-  odd = !(ax <= 0x1p56f && ay <= 0x1p56f && az <= 0x1p56f);  // NaN: odd
-  const float M = fmaxf(ax, fmaxf(ay, az));
-  const float ex = fmaxf(fmaxf(B.lo[0] - o.x, o.x - B.hi[0]), 0.f);
-  const float ey = fmaxf(fmaxf(B.lo[1] - o.y, o.y - B.hi[1]), 0.f);
-  const float ez = fmaxf(fmaxf(B.lo[2] - o.z, o.z - B.hi[2]), 0.f);
-  const float D = sqrt_hw(ex * ex + ey * ey + ez * ez);
-  const float Mo = M > B.omax ? M : 0.f;
-  return (0x1p-8f * D + 0x1p-18f * Mo) * (1.0f + 0x1p-10f);
-}
-
-// calcIntersection for ray (o, d) of an `active` lane; the whole wave enters
-// (kBvh: the walk is wave-uniform).  Inactive lanes get a miss.
-template <bool kBvh, class Scene>
-RTG_HD int ray_closest(const Scene& sc, const RayBox& box, V3 o, V3 d, bool active, float& t) {
-  if constexpr (kBvh) {
-    const RayQ q = make_query(o, d);
-    bool odd;
-    const float delta = ray_delta(box, o, odd);
-    odd = active && (odd || !q.fast);
-    int id = closest_bvh<true>(sc, q, t, delta, active && !odd);
-    if (sc.any(odd)) {
-      if (odd) id = closest_hit4(sc, o, d, t);
-    }
-    return id;
-  } else {
-    t = 1000.f;
-    if (!active) return -1;
-    if (sc.n4 <= 64) return closest_hit64(sc, o, d, t);
-    return closest_hit4(sc, o, d, t);
-  }
-}
-
-// hasClearLineOfSight's blocker search for the ray (o, d) with gap |b - a|^2.
-template <bool kBvh, class Scene>
-RTG_HD bool ray_blocked(const Scene& sc, const RayBox& box, V3 o, V3 d, float gap, bool active) {
-  if constexpr (kBvh) {
-    const RayQ q = make_query(o, d);
-    bool odd;
-    const float delta = ray_delta(box, o, odd);
-    odd = active && (odd || !q.fast);
-    // (active lanes have 2 a in the Markstein range: the walk's reach in ray
-    // units is sqrt(gap / a) rounded up)
-    bool blk = blocked_bvh<true>(sc, q, gap, delta, active && !odd);
-    if (sc.any(odd)) {
-      if (odd) blk = blocked(sc, o, d, gap);
-    }
-    return blk;
-  } else {
-    if (!active) return false;
-    if (sc.n4 <= 64) return blocked64(sc, o, d, gap);
-    return blocked(sc, o, d, gap);
-  }
-}
 
 // The hit record of ray (o, d) with closest hit (id, t) as two 16-byte
 // halves; point and normal of the winner (raytracer.h:172-177), c its centre.

@@ -643,9 +643,17 @@ struct IsBvhScene<S, std::void_t<decltype(S::kIsBvh)>> : std::bool_constant<S::k
 // Q == 4: shadow rays test only the union of the wave's shadow masks
 // (shadow_masks, rtg_scene_pack.h) for the hit sphere `hit`; `guardOK` tells
 // that P lies in that sphere's guard ball (else every sphere is tested).
-template <int Q, class Scene>
+// RP: the query path of a caller's own ray tree (rtg_raytrace*, RayPath in
+// rtg_rays.h: every shadow and closest-hit query through ray_blocked /
+// ray_closest, no table keyed to the renderer's rays); NoRayPath (the renders)
+// compiles none of it.
+struct NoRayPath {
+  static constexpr bool kOn = false;
+};
+template <int Q, class RP = NoRayPath, class Scene>
 RTG_HD V3 matte_light(const Scene& sc, V3 P, V3 N, int hit = -1, bool guardOK = false,
-                      unsigned cell = kCapFull, V3 hc = V3{}, float hr2 = 0.f) {
+                      unsigned cell = kCapFull, V3 hc = V3{}, float hr2 = 0.f,
+                      const RP& rp = RP()) {
   V3 sum = v3(0.f, 0.f, 0.f);
   const unsigned m = sc.m;
   for (unsigned l = 0; l < m; ++l) {
@@ -661,7 +669,10 @@ RTG_HD V3 matte_light(const Scene& sc, V3 P, V3 N, int hit = -1, bool guardOK = 
     // error below 3.1 2^-24 m) proves incidence < 0: the light adds nothing and
     // casts no shadow ray.  The wave skips the light when every lane proves it
     // (m >= 2^-100 keeps the bounds relative; NaN never skips).
-    if constexpr (!IsBvhScene<Scene>::value) {
+    // (Not for a caller's rays either: their hit points may lie 2^48 from the
+    // lights, where the products of the reference's incidence can underflow;
+    // nor in the literal form Q == 0, the host yardstick.)
+    if constexpr (!IsBvhScene<Scene>::value && !RP::kOn && Q != 0) {
       const float fe = fmaf(N.x, dist.x, fmaf(N.y, dist.y, N.z * dist.z));
       const float fm = fmaf(fabsf(N.x), fabsf(dist.x),
                             fmaf(fabsf(N.y), fabsf(dist.y), fabsf(N.z * dist.z)));
@@ -675,7 +686,9 @@ RTG_HD V3 matte_light(const Scene& sc, V3 P, V3 N, int hit = -1, bool guardOK = 
       sc.count(kUShadow, 1);
       sc.probe_begin(kProbeShadow);
       bool blk;
-      if constexpr (Q == 4) {
+      if constexpr (RP::kOn) {
+        blk = rp.blocked(sc, P, dir, gap);
+      } else if constexpr (Q == 4) {
         if (sc.has_smask()) {
           const uint64_t su = sc.shadow_union(l, hit, guardOK);
           sc.count(kCntShadowQ, 1);
@@ -928,14 +941,20 @@ RTG_HD FrameR load_frame_r(const FrameR& src) {
 // leaf's colour is doubled once, not twice.  sinA1 stays f64: :507 is the CPU
 // path's double expression, which the .cl compiled for gfx950 evaluates in
 // double too (pinned against it, oracle/build_ref_cl.sh).
-template <int S, int Q, bool kCL = false, class Scene, class FStore>
+// o0, rp: the ray's origin and the query path of a caller's own ray (RayPath,
+// rtg_rays.h; Q == 2, no usePrim): every level's closest hit is rp.closest and
+// every shadow ray rp.blocked, the refraction target primary_container; none
+// of the chain below, which is proved for the renderer's rays only.
+template <int S, int Q, bool kCL = false, class RP = NoRayPath, class Scene, class FStore>
 RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = false,
-                       uint64_t primSel = ~0ull) {
+                       uint64_t primSel = ~0ull, V3 o0 = V3{0.f, 0.f, 0.f},
+                       const RP& rp = RP()) {
+  static_assert(!RP::kOn || Q == 2, "a caller's rays run the Q == 2 shading path");
   constexpr int NF = (S > 1) ? (S - 1) : 1;
   FrameR fr[NF];                        // reflection child rays (private memory)
   int sp = 0;                           // == level of the node being processed
   V3 ret = v3(0.f, 0.f, 0.f);           // colourSum register
-  V3 o = v3(0.f, 0.f, 0.f), d = dir0, I = v3(1.f, 1.f, 1.f);
+  V3 o = o0, d = dir0, I = v3(1.f, 1.f, 1.f);
   int rm = (int)sc.n;                   // background material
   int enterH = -1;  // Q == 4: the sphere this ray entered (refraction child), or -1
   int originH = -1;  // Q == 4: the sphere whose origin ball holds this ray's origin, or -1
@@ -954,7 +973,10 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
     // copy of each query kind keeps the kernel's code small: DESIGN.md §4
     // item 66)
     bool full = false;
-    if (usePrim) {  // the primary ray: only spheres its wave's bundle can reach
+    if constexpr (RP::kOn) {
+      sc.count(kCntFullQ, 1);
+      hit = rp.closest(sc, o, d, t);
+    } else if (usePrim) {  // the primary ray: only spheres its wave's bundle can reach
       sc.count(kCntPrimQ, 1);
       sc.count(kCntPrimSel, __builtin_popcountll(primSel));
       hit = closest_hit_sel(sc, o, d, t, primSel);
@@ -1069,7 +1091,7 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
         V3 tmp = vmul(I, mh.matte);
         tmp = vsmul(op, tmp);
         sc.probe_begin(kProbeMatte);
-        const V3 mc = matte_light<Q>(sc, P, N, hit, guardOK, cell, c, r2h);
+        const V3 mc = matte_light<Q, RP>(sc, P, N, hit, guardOK, cell, c, r2h, rp);
         sc.probe_end(kProbeMatte);
         tmp = vmul(mc, tmp);
         colour = vadd(tmp, colour);

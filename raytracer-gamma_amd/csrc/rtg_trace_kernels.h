@@ -1205,7 +1205,8 @@ struct RayBox;  // rtg_rays.h
 }  // namespace rtg
 
 // rtg_kernel.hip: a context's device, its scene tables and, when asked for,
-// the BVH's origin box (the batch ray queries); false when the context is
-// null or has no scene.
+// the BVH's origin box (the batch ray queries) and its semantics
+// (rtg_context_set_semantics: the batch ray tracer); false when the context
+// is null or has no scene.
 bool rtg_context_scene(const rtg_context* ctx, rtg::SceneTables* t, int* device,
-                       rtg::RayBox* box = nullptr);
+                       rtg::RayBox* box = nullptr, int* semantics = nullptr);

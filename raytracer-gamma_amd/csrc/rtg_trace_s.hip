@@ -1,5 +1,7 @@
 // rtg_trace_s.hip — instantiates the trace kernels for ONE stack capacity,
-// RTG_S (set by the Makefile: one object per S = 1..16, built in parallel).
+// RTG_S (set by the Makefile: one object per S = 1..16, built in parallel):
+// the render kernels (trace_fn) and the batch ray tracer's (raytrace_fn).
+#include "rtg_raytrace_kernels.h"
 #include "rtg_trace_kernels.h"
 
 #ifndef RTG_S
@@ -11,5 +13,8 @@
 namespace rtg {
 TraceFn RTG_CAT(trace_fn_s, RTG_S)(int variant, bool bvh, int list) {
   return trace_fn<RTG_S>(variant, bvh, list);
+}
+RayTraceFn RTG_CAT(raytrace_fn_s, RTG_S)(bool bvh, bool cl) {
+  return raytrace_fn<RTG_S>(bvh, cl);
 }
 }  // namespace rtg

@@ -42,9 +42,12 @@ static void usage() {
   printf("      --gbuffer    FILE    Also write the primary-hit G-buffer: W*H raw little-endian\n");
   printf("                           rtg_gbuf_px records (id, t, hits, sample, normal, idSum)\n");
   printf("      --rays       FILE    Also intersect the rays of FILE with the scene: raw little-endian\n");
-  printf("                           24-byte rtg_ray records (origin, dir); needs --hits\n");
+  printf("                           24-byte rtg_ray records (origin, dir); needs --hits and/or\n");
+  printf("                           --radiance\n");
   printf("      --hits       FILE    Write their closest hits: 32-byte rtg_hit records\n");
   printf("                           (id, t, point, normal)\n");
+  printf("      --radiance   FILE    Write their colours (rayTrace's return at --depth and\n");
+  printf("                           --semantics): 12-byte rtg_vec records\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -66,7 +69,7 @@ int main(int argc, char** argv) {
   unsigned device = 0, W = 800, H = 600, nSph = 3, nLgt = 2, depth = 5, repeat = 1;
   unsigned long long seed = 42;
   float aa = 3.f, zoom = -4.f;
-  std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut;
+  std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut, radianceOut;
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   for (int i = 1; i < argc; ++i) {
@@ -121,6 +124,8 @@ int main(int argc, char** argv) {
       raysIn = need(a);
     } else if (!strcmp(a, "--hits")) {
       hitsOut = need(a);
+    } else if (!strcmp(a, "--radiance")) {
+      radianceOut = need(a);
     } else if (!strcmp(a, "--scene")) {
       sceneIn = need(a);
     } else if (!strcmp(a, "--save-scene")) {
@@ -139,8 +144,12 @@ int main(int argc, char** argv) {
     }
   }
 
-  if (raysIn.empty() != hitsOut.empty()) {
+  if (raysIn.empty() ? !hitsOut.empty() : (hitsOut.empty() && radianceOut.empty())) {
     printf("--rays and --hits go together\n");
+    return 1;
+  }
+  if (raysIn.empty() && !radianceOut.empty()) {
+    printf("--radiance needs --rays\n");
     return 1;
   }
 
@@ -254,19 +263,59 @@ int main(int argc, char** argv) {
               sizeof(rtg_ray));
       exit(EXIT_FAILURE);
     }
-    std::vector<rtg_hit> hits(rays.size());
-    if (!rays.empty())
-      check(rtg_intersect((int)device, spheres.data(), nSph, rays.data(), rays.size(),
-                          hits.data()),
-            "rtg_intersect");
-    f = fopen(hitsOut.c_str(), "wb");
-    if (!f || fwrite(hits.data(), sizeof(rtg_hit), hits.size(), f) != hits.size() ||
-        fclose(f) != 0) {
-      fprintf(stderr, "Error: can't write %s\n", hitsOut.c_str());
-      exit(EXIT_FAILURE);
+    if (!hitsOut.empty()) {
+      std::vector<rtg_hit> hits(rays.size());
+      if (!rays.empty())
+        check(rtg_intersect((int)device, spheres.data(), nSph, rays.data(), rays.size(),
+                            hits.data()),
+              "rtg_intersect");
+      f = fopen(hitsOut.c_str(), "wb");
+      if (!f || fwrite(hits.data(), sizeof(rtg_hit), hits.size(), f) != hits.size() ||
+          fclose(f) != 0) {
+        fprintf(stderr, "Error: can't write %s\n", hitsOut.c_str());
+        exit(EXIT_FAILURE);
+      }
+      printf("Wrote %s (%zu hit records of %zu bytes)\n", hitsOut.c_str(), hits.size(),
+             sizeof(rtg_hit));
     }
-    printf("Wrote %s (%zu hit records of %zu bytes)\n", hitsOut.c_str(), hits.size(),
-           sizeof(rtg_hit));
+    if (!radianceOut.empty()) {
+      std::vector<rtg_vec> cols(rays.size());
+      if (!rays.empty() && semantics == RTG_SEMANTICS_CPU) {
+        check(rtg_raytrace((int)device, spheres.data(), nSph, lights.data(), nLgt, rays.data(),
+                           rays.size(), (int)depth + 1, cols.data()),
+              "rtg_raytrace");
+      } else if (!rays.empty()) {  // semantics is per context, as for the render above
+        rtg_context* ctx = nullptr;
+        check(rtg_context_create((int)device, &ctx), "rtg_context_create");
+        check(rtg_context_set_semantics(ctx, semantics), "rtg_context_set_semantics");
+        check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
+              "rtg_context_set_scene");
+        rtg_ray* dr = nullptr;
+        rtg_vec* dc = nullptr;
+        if (hipMalloc(&dr, rays.size() * sizeof(rtg_ray)) != hipSuccess ||
+            hipMalloc(&dc, cols.size() * sizeof(rtg_vec)) != hipSuccess)
+          check(RTG_ERR_NOMEM, "hipMalloc");
+        if (hipMemcpy(dr, rays.data(), rays.size() * sizeof(rtg_ray), hipMemcpyHostToDevice) !=
+            hipSuccess)
+          check(RTG_ERR_HIP, "upload");
+        check(rtg_raytrace_device(ctx, dr, rays.size(), (int)depth + 1, dc, nullptr),
+              "rtg_raytrace_device");
+        if (hipMemcpy(cols.data(), dc, cols.size() * sizeof(rtg_vec), hipMemcpyDeviceToHost) !=
+            hipSuccess)
+          check(RTG_ERR_HIP, "readback");
+        (void)hipFree(dr);
+        (void)hipFree(dc);
+        rtg_context_destroy(ctx);
+      }
+      f = fopen(radianceOut.c_str(), "wb");
+      if (!f || fwrite(cols.data(), sizeof(rtg_vec), cols.size(), f) != cols.size() ||
+          fclose(f) != 0) {
+        fprintf(stderr, "Error: can't write %s\n", radianceOut.c_str());
+        exit(EXIT_FAILURE);
+      }
+      printf("Wrote %s (%zu colours of %zu bytes)\n", radianceOut.c_str(), cols.size(),
+             sizeof(rtg_vec));
+    }
   }
   return 0;
 }

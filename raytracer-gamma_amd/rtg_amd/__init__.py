@@ -74,6 +74,7 @@ EXPORTED = [
     "rtg_gbuffer_device", "rtg_gbuffer", "rtg_gbuffer_host",
     "rtg_intersect_device", "rtg_intersect", "rtg_intersect_host",
     "rtg_visible_device", "rtg_visible", "rtg_visible_host",
+    "rtg_raytrace_device", "rtg_raytrace", "rtg_raytrace_host",
 ]
 
 
@@ -159,6 +160,9 @@ def lib() -> ctypes.CDLL:
             getattr(L, f"rtg_{q}_device").argtypes = [vp, vp, sz, vp, vp]
             getattr(L, f"rtg_{q}").argtypes = [i, vp, u, vp, sz, vp]
             getattr(L, f"rtg_{q}_host").argtypes = [vp, u, vp, sz, vp, i, i]
+        L.rtg_raytrace_device.argtypes = [vp, vp, sz, i, vp, vp]
+        L.rtg_raytrace.argtypes = [i, vp, u, vp, u, vp, sz, i, vp]
+        L.rtg_raytrace_host.argtypes = [vp, u, vp, u, vp, sz, i, i, vp, i, i]
 
         pu = ctypes.POINTER(u)
         L.rtg_scene_load.argtypes = [ctypes.c_char_p, vp, u, pu, vp, u, pu]
@@ -388,6 +392,39 @@ def visible_host(spheres, segments, walk: int = 0, threads: int = 1) -> np.ndarr
     return out
 
 
+def _colours(rays):
+    """A ray batch and its (N, 3) float32 result, as _batch."""
+    src, n, out, dst = _batch(rays, RAY_DTYPE, np.dtype(("<f4", 3)))
+    return src, n, out.reshape(n, 3), dst
+
+
+def raytrace(spheres, lights, rays, stack_size: int = 6, device: int = 0) -> np.ndarray:
+    """rayTrace's colour of every ray of a batch on the GPU (rtg_raytrace):
+    RAY_DTYPE records (or (N, 6) float32: origin, dir) in, (N, 3) float32 out,
+    the reference's return value bit for bit (before the 1/nS scale of a
+    pixel's sum).  Directions are used as given."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    src, n, out, dst = _colours(rays)
+    _check(lib().rtg_raytrace(device, _ptr(spheres), len(spheres), _ptr(lights), len(lights),
+                              _ptr(src), n, stack_size, _ptr(dst)), "rtg_raytrace")
+    return out
+
+
+def raytrace_host(spheres, lights, rays, stack_size: int = 6, semantics: int = 0,
+                  walk: int = 0, threads: int = 1) -> np.ndarray:
+    """The same on the host (rtg_raytrace_host; no GPU needed).  walk 0: plain
+    loops over every sphere for every query; walk 1: the device kernel's own
+    path compiled for the host.  semantics: 0 the CPU path, 1 the OpenCL kernel's."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    src, n, out, dst = _colours(rays)
+    _check(lib().rtg_raytrace_host(_ptr(spheres), len(spheres), _ptr(lights), len(lights),
+                                   _ptr(src), n, stack_size, semantics, _ptr(dst), walk, threads),
+           "rtg_raytrace_host")
+    return out
+
+
 class MultiContext:
     """Persistent multi-device handle (rtg_multi_*): RCCL communicator, contexts,
     streams and buffers kept across frames."""
@@ -576,6 +613,16 @@ class Context:
                                         ctypes.c_void_p(dst_ptr),
                                         ctypes.c_void_p(stream) if stream else None),
                "rtg_visible_device")
+
+    def raytrace_device(self, rays_ptr: int, n: int, dst_ptr: int, stack_size: int = 6,
+                        stream: int = 0):
+        """rayTrace's colours of n rays at rays_ptr (device, 24-byte RAY_DTYPE
+        records) into dst_ptr (device, an (N, 3) float32 tensor), asynchronously
+        on `stream`, under the context's semantics."""
+        _check(lib().rtg_raytrace_device(self._h, ctypes.c_void_p(rays_ptr), n, stack_size,
+                                         ctypes.c_void_p(dst_ptr),
+                                         ctypes.c_void_p(stream) if stream else None),
+               "rtg_raytrace_device")
 
     def render_rows_device(self, width, height, rows_ptr: int, n_rows: int, dst_ptr: int,
                            zoom=-4.0, alias_factor=3.0, stack_size=6, stream: int = 0):

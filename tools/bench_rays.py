@@ -19,7 +19,18 @@ primary cull (group_sel), so it is expected to be the slower of the two.
 --parent-json FILE stores that file's object under "parent_commit" (the same
 measurements taken on the parent commit's build, for the side-by-side).
 The tool also checks that the ordered C3 hits are the G-buffer's (id, t,
-normal) and that the shuffled hits are the ordered ones permuted.  GPU only.
+normal) and that the shuffled hits are the ordered ones permuted.
+
+rtg_raytrace_device (the batch ray tracer, csrc/rtg_raytrace.hip) gets rows of
+its own under "raytrace": for C3 and C5 at their golden stack sizes (6 and 8),
+the same 8.3 M one-sample primary rays in pixel order and shuffled, and next
+to each, round by round in the same process, rtg_render_device of that frame
+at alias_factor = 1, which traces exactly those rays.  The render has the
+camera's cull, the compacted launch and the launch-order feedback, and every
+table keyed to its own rays; the batch call has none of them.  The ratio
+raytrace / render is therefore the price of generality; it is reported, not
+gated.  The ordered colours must be the render's frame and the shuffled ones
+the ordered ones permuted.  GPU only.
 """
 import argparse
 import json
@@ -85,6 +96,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rays", "bench.json"))
     ap.add_argument("--parent-json", default="")
+    ap.add_argument("--commit", default="", help="recorded as the commit the numbers are of")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_rays: needs a GPU")
@@ -100,7 +112,7 @@ def main():
     gb = torch.empty((n, 8), dtype=torch.int32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     res = {"W": W, "H": H, "rays": n, "device": R.device_info(0), "rounds": args.rounds,
-           "batches": {}}
+           "commit": args.commit, "batches": {}}
 
     def rate(m):
         m["Mrays_per_s"] = round(n / (m["ms_median"] * 1e-3) / 1e6, 1)
@@ -134,6 +146,37 @@ def main():
     permuted = bool((hits[torch.from_numpy(perm).cuda()] == hits2).all())
     res["c5_shuffled_hits_are_ordered_permuted"] = permuted
     res["c5_hit_rays"] = int((hits[:, 0] >= 0).sum())
+    del hits, hits2, gb
+
+    # the batch ray tracer next to the render of the same rays
+    col = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    col2 = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    fb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    dperm = torch.from_numpy(perm).cuda()
+    res["raytrace"] = {}
+    ok = True
+    for name in ("c3", "c5"):
+        S = CONFIGS[name][4] + 1
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        o, s, r = measure(
+            [lambda: ctx.raytrace_device(rays.data_ptr(), n, col.data_ptr(), S, stream),
+             lambda: ctx.raytrace_device(shuffled.data_ptr(), n, col2.data_ptr(), S, stream),
+             lambda: ctx.render_device(W, H, fb.data_ptr(), alias_factor=1.0, stack_size=S,
+                                       stream=stream)], args.rounds)
+        ctx.close()
+        # NaNs as written (0xFFC00000 on both sides): compare the words
+        frame = bool((col.view(torch.int32) == fb.view(-1, 3).view(torch.int32)).all())
+        permuted = bool((col[dperm].view(torch.int32) == col2.view(torch.int32)).all())
+        ok = ok and frame and permuted
+        res["raytrace"][name] = {
+            "stack_size": S, "ordered": rate(o), "shuffled": rate(s), "render_aa1": r,
+            "ordered_over_render": round(o["ms_median"] / r["ms_median"], 3),
+            "shuffled_over_render": round(s["ms_median"] / r["ms_median"], 3),
+            "shuffled_over_ordered": round(s["ms_median"] / o["ms_median"], 3),
+            "ordered_colours_equal_render": frame,
+            "shuffled_colours_are_ordered_permuted": permuted}
     if args.parent_json:
         with open(args.parent_json) as f:
             res["parent_commit"] = json.load(f)
@@ -142,7 +185,7 @@ def main():
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res), flush=True)
-    sys.exit(0 if same and permuted else 1)
+    sys.exit(0 if same and res["c5_shuffled_hits_are_ordered_permuted"] and ok else 1)
 
 
 if __name__ == "__main__":
