@@ -24,6 +24,8 @@
  *     caller's own rays  raytracer.h:145-194, 272-309  rtg_visible[_device|_host]
  *   rayTrace for a caller's own rays                   rtg_raytrace[_device|_host]
  *     raytracer.h:410-636
+ *   the camera of main.cpp:384-436, moved to a pose   rtg_camera_look_at, rtg_camera_rays[_device|_host],
+ *     (fixed at 0 looking down -z in the reference)    rtg_render_camera[_device|_host]
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
  *   output_device_info  device_info.cpp:30             rtg_device_info
  *   parseArguments --list/--device  device_picker.h:70 rtg_device_count / device index args
@@ -353,8 +355,8 @@ int rtg_visible_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_segme
  * than 2^31-1 workgroups (64 rays each).
  *
  * Out of scope: a per-ray intensity, a caller-chosen refractive material for
- * the ray's medium, camera or resolve helpers, multi-GPU batches, and sorting
- * a batch for coherence. */
+ * the ray's medium, multi-GPU batches, and sorting a batch for coherence.
+ * (A frame's rays and its fold: the posed camera, below.) */
 int rtg_raytrace_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
                         int stackSize, rtg_vec* dstDevice, void* stream);
 /* One-shot: uploads the scene and the rays, runs on `device`, downloads n colours. */
@@ -370,6 +372,87 @@ int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum,
                       const rtg_light* lights, unsigned lgtNum, const rtg_ray* rays,
                       size_t n, int stackSize, int semantics, rtg_vec* dstHost,
                       int walk, int nthreads);
+
+/* ---- posed camera: rays and frames from any viewpoint ----
+ * The reference keeps its camera at the origin looking down -z (main.cpp:
+ * 384-436), and so do rtg_render* and rtg_gbuffer*.  A pose moves it.  The
+ * camera vector of sample (i, j) of pixel (x, y) is (rx, ry, zoom) with rx,
+ * ry exactly those of main.cpp:411-436; the posed ray is, per component q in
+ * float with no contraction and in this operand order,
+ *
+ *   v.q    = (rx * right.q + ry * up.q) + zoom * back.q
+ *   dir    = vnorm(v)            (vec.h:41: l = 1/sqrt(dot), l * v)
+ *   origin = eye
+ *
+ * The basis is used as given: it is not normalised or orthogonalised, so a
+ * scaled, sheared or mirrored basis is legal.  NaN, infinite or zero
+ * components follow the arithmetic and the comparisons as written, as in
+ * rtg_intersect.  The identity pose (eye 0, right (1,0,0), up (0,1,0), back
+ * (0,0,1)) gives, for a nonzero zoom, the render's ray bit for bit.
+ *
+ * The frame of a pose is, per pixel,
+ *   pix = 0; for each sample s in the reference's order (i outer, j inner):
+ *       pix += (1/nS) * rayTrace(ray_s)
+ * in main.cpp:442-445's operations, rayTrace as rtg_raytrace* defines it
+ * (background material, intensity (1,1,1), stack capacity stackSize, the
+ * context's semantics), NaN words stored as 0xFFC00000: bit for bit the fold
+ * of rtg_raytrace_host(walk 0) over rtg_camera_rays_host's rays, and at the
+ * identity pose rtg_render's frame.  Like rtg_raytrace it uses none of the
+ * tables the renders keep for their own camera, so it is exact for any pose
+ * and slower than rtg_render_device at the identity pose (README).
+ *
+ * RTG_ERR_INVALID with a message, before any GPU call, for a null pointer, an
+ * empty frame, an aliasFactor above 256 or NaN, stackSize outside
+ * 1..RTG_MAX_STACK, an unknown walk or semantics, a context without a scene
+ * (the render only) or a frame of more than 2^31-1 workgroups.
+ *
+ * Out of scope: row shards and multi-GPU for posed frames, a posed G-buffer
+ * call (rtg_camera_rays_device plus rtg_intersect_device gives it), a camera
+ * record in scene files, lens models. */
+typedef struct rtg_camera { rtg_vec eye, right, up, back; } rtg_camera;   /* 48 B */
+void rtg_camera_identity(rtg_camera* out);
+/* All in float, in this order: back = vnorm(eye - target), right =
+ * vnorm(cross(up, back)), up' = cross(back, right), with cross(a, b) =
+ * (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).  look_at(0,
+ * (0,0,-1), (0,1,0)) is the identity pose.  A degenerate input (eye ==
+ * target, up parallel to the view) yields the NaN basis the arithmetic
+ * yields and RTG_OK; the only error is a null pointer. */
+int rtg_camera_look_at(const rtg_vec* eye, const rtg_vec* target, const rtg_vec* up,
+                       rtg_camera* out);
+/* *nAA = iterations of `for (int i = 0; i < aliasFactor; ++i)`: a pixel has
+ * nAA * nAA samples.  aliasFactor above 256 or NaN is RTG_ERR_INVALID. */
+int rtg_camera_sample_count(float aliasFactor, unsigned* nAA);
+/* The pose's sample rays: W * H * nAA * nAA records in pixel order (row
+ * major), a pixel's samples in the reference's order.  nAA == 0 writes
+ * nothing and is RTG_OK.  nthreads <= 0: 1. */
+int rtg_camera_rays_host(const rtg_camera* cam, unsigned width, unsigned height, float zoom,
+                         float aliasFactor, rtg_ray* raysHost, int nthreads);
+/* The same into device memory, asynchronously on `stream`.  The context names
+ * the device; it needs no scene. */
+int rtg_camera_rays_device(rtg_context* ctx, const rtg_camera* cam, unsigned width,
+                           unsigned height, float zoom, float aliasFactor, rtg_ray* raysDevice,
+                           void* stream);
+/* Fused render of the pose's whole W x H frame (row major) into device memory
+ * on `stream`, asynchronously: no ray buffer, no colour buffer, no fold on the
+ * caller's side.  Follows rtg_context_set_semantics; rtg_set_launch_opts does
+ * not apply.  Takes none of the context's render scratch: it may be mixed
+ * freely with rtg_render_device, rtg_gbuffer_device, the ray queries and
+ * rtg_raytrace_device on one context. */
+int rtg_render_camera_device(rtg_context* ctx, const rtg_camera* cam, unsigned width,
+                             unsigned height, float zoom, float aliasFactor, int stackSize,
+                             rtg_vec* dstDevice, void* stream);
+/* One-shot: uploads the scene, renders on `device`, downloads W*H rtg_vec. */
+int rtg_render_camera(int device, const rtg_sphere* spheres, unsigned sphNum,
+                      const rtg_light* lights, unsigned lgtNum, const rtg_camera* cam,
+                      unsigned width, unsigned height, float zoom, float aliasFactor,
+                      int stackSize, rtg_vec* dstHost);
+/* The same on the host, no GPU call; walk, semantics and nthreads as in
+ * rtg_raytrace_host (walk 0: plain loops, the yardstick; walk 1: the kernel's
+ * own path over the packed tables). */
+int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+                           unsigned lgtNum, const rtg_camera* cam, unsigned width,
+                           unsigned height, float zoom, float aliasFactor, int stackSize,
+                           int semantics, rtg_vec* dstHost, int walk, int nthreads);
 
 /* Semantics of a context's renders.  RTG_SEMANTICS_CPU (default) is the
  * reference CPU path (raytracer.h), bit for bit.  RTG_SEMANTICS_OPENCL is the

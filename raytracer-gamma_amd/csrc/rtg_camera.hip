@@ -1,0 +1,350 @@
+// rtg_camera.hip — the posed camera of librtg.so (rtg_camera*, rtg_render_camera*,
+// rtg.h): a frame, or the sample rays of a frame, from any viewpoint.
+//
+// The reference keeps its camera at 0 looking down -z (main.cpp:384-436), and
+// so do the renders.  A pose {eye, right, up, back} moves it: the sample's
+// screen-plane point (rx, ry) is sample_dir's, and its ray is
+//   origin = eye,  dir = vnorm((rx * right + ry * up) + zoom * back)
+// per component in float with no contraction (camera_dir, rtg_camera.h: one
+// function for every form below).  The identity pose gives the render's ray
+// bit for bit.
+//
+// The fused render (camera_kernel, rtg_camera_kernels.h, per S in
+// rtg_trace_s.hip) forms each sample ray in registers, runs rayTrace on it as
+// rtg_raytrace_device does (trace_sample with the query path RayPath,
+// rtg_rays.h: exact for any origin at every level of the tree; none of the
+// renders' table paths, for the reasons at the head of rtg_raytrace.hip) and
+// folds the pixel as shade_pixel does.  The posed frame is therefore, bit for
+// bit, the host fold of rtg_raytrace_host(walk 0) over rtg_camera_rays_host's
+// rays: no ray buffer, no colour buffer and no fold on the caller's side.
+//
+// This file holds the pose helpers, the generator (kernel and host form), the
+// launcher of the fused kernel, the argument checks and the host forms of the
+// render (walk 0: trace_sample<S, 0> with plain loops, the yardstick; walk 1:
+// the kernel's own path over the packed tables, one pixel per "wave").
+//
+// FP contract: the Makefile's FPFLAGS, as every kernel.
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "rtg.h"
+#include "rtg_camera.h"
+#include "rtg_camera_kernels.h"
+#include "rtg_entry.h"
+#include "rtg_host_scene.h"
+#include "rtg_rays.h"
+#include "rtg_scene_pack.h"
+
+static_assert(sizeof(rtg_camera) == 48 && sizeof(rtg::CamPose) == 48, "the pose is 48 B");
+static_assert(sizeof(rtg_ray) == 24 && sizeof(rtg_vec) == 12, "24 B per ray, 12 B per pixel");
+
+namespace rtg {
+
+static CameraFn pick_camera(int S, bool bvh, bool cl) {
+  switch (S) {
+#define RTG_CASE(k) case k: return camera_fn_s##k(bvh, cl);
+    RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
+    RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
+    RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
+#undef RTG_CASE
+    default: return nullptr;
+  }
+}
+
+// ---- the generator ----
+
+// Ray k of the frame: pixel k / nS in row-major order, its sample k % nS in
+// the reference's order (i outer, j inner).
+RTG_HD void camera_ray(const Camera& cam, const CamPose& p, unsigned W, size_t k, float* r) {
+  const size_t nS = (size_t)cam.nAA * cam.nAA;
+  const size_t px = k / nS;
+  const int s = (int)(k % nS);
+  const V3 d = camera_dir(cam, p, (unsigned)(px % W), (unsigned)(px / W), s / cam.nAA, s % cam.nAA);
+  r[0] = p.eye.x; r[1] = p.eye.y; r[2] = p.eye.z;
+  r[3] = d.x; r[4] = d.y; r[5] = d.z;
+}
+
+// One lane per sample ray, 24 B out; n > 0 (so cam.nAA > 0).
+__global__ __launch_bounds__(64) void camera_rays_kernel(const Camera cam, const CamPose pose,
+                                                         unsigned W, size_t n,
+                                                         rtg_ray* __restrict__ rays) {
+  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (k >= n) return;
+  camera_ray(cam, pose, W, k, reinterpret_cast<float*>(rays + k));  // k < n: 24 B of the batch
+}
+
+// ---- host forms of the render ----
+
+// Pixels [k0, k1) of the frame; kWalk 1: the kernel's path, else plain loops.
+template <int S, bool kCL, bool kWalk, bool kBvh>
+static void camera_host_range(const PackedScene& ps, const RayBox& box, const Camera& cam,
+                              const CamPose& pose, unsigned W, size_t k0, size_t k1,
+                              rtg_vec* dst) {
+  const HostScene<kBvh> sc(ps, kWalk);  // walk 0: no masks, no BVH, no lists
+  for (size_t k = k0; k < k1; ++k) {
+    const unsigned x = (unsigned)(k % W), y = (unsigned)(k / W);
+    V3 pix = v3(0.f, 0.f, 0.f);
+    for (int i = 0; i < cam.nAA; ++i) {
+      for (int j = 0; j < cam.nAA; ++j) {
+        const V3 d = camera_dir(cam, pose, x, y, i, j);
+        V3 c;
+        if constexpr (kWalk)
+          c = trace_sample<S, 2, kCL, RayPath<kBvh>>(sc, d, sc.frames(), false, ~0ull, pose.eye,
+                                                     RayPath<kBvh>{box});
+        else
+          c = trace_sample<S, 0, kCL>(sc, d, sc.frames(), false, ~0ull, pose.eye);
+        c = vsmul(cam.inv, c);
+        pix = vadd(pix, c);
+      }
+    }
+    const unsigned w[3] = {nan_bits(pix.x), nan_bits(pix.y), nan_bits(pix.z)};
+    memcpy(dst + k, w, sizeof w);
+  }
+}
+
+typedef void (*CamHostFn)(const PackedScene&, const RayBox&, const Camera&, const CamPose&,
+                          unsigned, size_t, size_t, rtg_vec*);
+template <int S>
+static CamHostFn cam_host_fn(bool cl, bool walk, bool bvh) {
+  if (!walk)
+    return cl ? camera_host_range<S, true, false, false>
+              : camera_host_range<S, false, false, false>;
+  if (bvh)
+    return cl ? camera_host_range<S, true, true, true> : camera_host_range<S, false, true, true>;
+  return cl ? camera_host_range<S, true, true, false> : camera_host_range<S, false, true, false>;
+}
+static CamHostFn pick_cam_host(int S, bool cl, bool walk, bool bvh) {
+  switch (S) {
+#define RTG_CASE(k) case k: return cam_host_fn<k>(cl, walk, bvh);
+    RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
+    RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
+    RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
+#undef RTG_CASE
+    default: return nullptr;
+  }
+}
+
+static V3 vcross(V3 a, V3 b) {
+  return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+
+}  // namespace rtg
+
+using namespace rtg;
+
+// The frame's camera constants, or RTG_ERR_INVALID for a null pointer or with
+// make_camera's message (an empty frame, an aliasFactor out of range).
+static int check_frame(const char* what, const rtg_camera* cam, const void* dst, unsigned W,
+                       unsigned H, float zoom, float aa, Camera* out) {
+  if (!cam || !dst) {
+    rtg_set_error("%s: null %s", what, cam ? "destination" : "camera");
+    return RTG_ERR_INVALID;
+  }
+  return make_camera(W, H, zoom, aa, out);
+}
+
+static int check_stack(int stackSize) {
+  if (stackSize < 1 || stackSize > RTG_MAX_STACK) {
+    rtg_set_error("render_camera: stackSize %d outside [1, %d]", stackSize, RTG_MAX_STACK);
+    return RTG_ERR_INVALID;
+  }
+  return RTG_OK;
+}
+
+// Workgroups of the fused kernel for a W x H frame; 0 when more than 2^31-1.
+static size_t camera_blocks(unsigned W, unsigned H, unsigned* tilesX) {
+  const size_t tx = ((size_t)W + kCamTileW - 1) / kCamTileW;
+  const size_t ty = ((size_t)H + kCamTileH - 1) / kCamTileH;
+  *tilesX = (unsigned)tx;
+  return (ty && tx > 0x7FFFFFFFu / ty) ? 0 : tx * ty;
+}
+
+extern "C" {
+
+void rtg_camera_identity(rtg_camera* out) {
+  if (!out) return;
+  const rtg_camera c = {{0.f, 0.f, 0.f}, {1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
+  *out = c;
+}
+
+int rtg_camera_look_at(const rtg_vec* eye, const rtg_vec* target, const rtg_vec* up,
+                       rtg_camera* out) {
+  rtg_clear_error();
+  if (!eye || !target || !up || !out) {
+    rtg_set_error("camera_look_at: null pointer");
+    return RTG_ERR_INVALID;
+  }
+  const V3 e = v3(eye->x, eye->y, eye->z);
+  const V3 back = vnorm(vsub(e, v3(target->x, target->y, target->z)));
+  const V3 right = vnorm(vcross(v3(up->x, up->y, up->z), back));
+  const V3 u = vcross(back, right);
+  const rtg_camera c = {{e.x, e.y, e.z},
+                        {right.x, right.y, right.z},
+                        {u.x, u.y, u.z},
+                        {back.x, back.y, back.z}};
+  *out = c;
+  return RTG_OK;
+}
+
+int rtg_camera_sample_count(float aliasFactor, unsigned* nAA) {
+  rtg_clear_error();
+  if (!nAA) {
+    rtg_set_error("camera_sample_count: null pointer");
+    return RTG_ERR_INVALID;
+  }
+  Camera cam;
+  const int rc = make_camera(1, 1, 0.f, aliasFactor, &cam);  // its range check and its loop
+  if (rc) return rc;
+  *nAA = (unsigned)cam.nAA;
+  return RTG_OK;
+}
+
+int rtg_camera_rays_host(const rtg_camera* cam, unsigned width, unsigned height, float zoom,
+                         float aliasFactor, rtg_ray* raysHost, int nthreads) {
+  rtg_clear_error();
+  Camera c;
+  const int rc = check_frame("camera_rays", cam, raysHost, width, height, zoom, aliasFactor, &c);
+  if (rc) return rc;
+  const size_t n = (size_t)width * height * c.nAA * c.nAA;
+  if (n == 0) return RTG_OK;
+  const CamPose pose = cam_pose(*cam);
+  host_bands(n, nthreads, [&](size_t k0, size_t k1) {
+    for (size_t k = k0; k < k1; ++k) {
+      float r[6];
+      camera_ray(c, pose, width, k, r);
+      memcpy(raysHost + k, r, sizeof r);
+    }
+  });
+  return RTG_OK;
+}
+
+int rtg_camera_rays_device(rtg_context* ctx, const rtg_camera* cam, unsigned width,
+                           unsigned height, float zoom, float aliasFactor, rtg_ray* raysDevice,
+                           void* stream) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  int device = 0;
+  if (!rtg_context_device(ctx, &device)) {
+    rtg_set_error("camera_rays: no context");
+    return RTG_ERR_INVALID;
+  }
+  Camera c;
+  const int rc = check_frame("camera_rays", cam, raysDevice, width, height, zoom, aliasFactor, &c);
+  if (rc) return rc;
+  const size_t n = (size_t)width * height * c.nAA * c.nAA;
+  if (n == 0) return RTG_OK;
+  const size_t blocks = (n + 63) / 64;  // one-wave workgroups
+  if (blocks > 0x7FFFFFFFu) {
+    rtg_set_error("camera_rays: frame too large (%zu workgroups)", blocks);
+    return RTG_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream,
+                     c, cam_pose(*cam), width, n, raysDevice);
+  HIP_TRY(hipGetLastError());
+  return RTG_OK;
+}
+
+int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+                           unsigned lgtNum, const rtg_camera* cam, unsigned width,
+                           unsigned height, float zoom, float aliasFactor, int stackSize,
+                           int semantics, rtg_vec* dstHost, int walk, int nthreads) {
+  rtg_clear_error();
+  Camera c;
+  int rc = check_frame("render_camera", cam, dstHost, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_stack(stackSize);
+  if (rc) return rc;
+  if ((sphNum && !spheres) || (lgtNum && !lights)) {
+    rtg_set_error("render_camera: null scene array");
+    return RTG_ERR_INVALID;
+  }
+  if (semantics != RTG_SEMANTICS_CPU && semantics != RTG_SEMANTICS_OPENCL) {
+    rtg_set_error("render_camera: semantics %d (0: CPU, 1: OpenCL)", semantics);
+    return RTG_ERR_INVALID;
+  }
+  if (walk != 0 && walk != 1) {
+    rtg_set_error("render_camera: walk %d (0: plain loops, 1: the kernel's query path)", walk);
+    return RTG_ERR_INVALID;
+  }
+  if (sphNum >= RTG_MAX_SPHERES) {
+    rtg_set_error("render_camera: %u spheres (at most %u)", sphNum, RTG_MAX_SPHERES - 1);
+    return RTG_ERR_INVALID;
+  }
+  PackedScene ps;
+  pack_scene(spheres, sphNum, lights, lgtNum, &ps);  // as rtg_context_set_scene
+  const bool bvh = walk == 1 && !ps.bvhNodes.empty();
+  const RayBox box = bvh ? ray_box(ps.originBox) : RayBox{};
+  const CamHostFn fn = pick_cam_host(stackSize, semantics == RTG_SEMANTICS_OPENCL, walk == 1, bvh);
+  const CamPose pose = cam_pose(*cam);
+  host_bands((size_t)width * height, nthreads,
+             [&](size_t k0, size_t k1) { fn(ps, box, c, pose, width, k0, k1, dstHost); });
+  return RTG_OK;
+}
+
+int rtg_render_camera_device(rtg_context* ctx, const rtg_camera* cam, unsigned width,
+                             unsigned height, float zoom, float aliasFactor, int stackSize,
+                             rtg_vec* dstDevice, void* stream) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  SceneTables a{};
+  RayBox box{};
+  int device = 0, semantics = RTG_SEMANTICS_CPU;
+  if (!rtg_context_scene(ctx, &a, &device, &box, &semantics)) {
+    rtg_set_error("render_camera: no context/scene");
+    return RTG_ERR_INVALID;
+  }
+  Camera c;
+  int rc = check_frame("render_camera", cam, dstDevice, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_stack(stackSize);
+  if (rc) return rc;
+  unsigned tilesX = 0;
+  const size_t blocks = camera_blocks(width, height, &tilesX);
+  if (!blocks) {
+    rtg_set_error("render_camera: frame too large (more than 2^31-1 workgroups)");
+    return RTG_ERR_INVALID;
+  }
+  const bool bvh = a.bvhNodes != nullptr;
+  const CameraFn fn = pick_camera(stackSize, bvh, semantics == RTG_SEMANTICS_OPENCL);
+  if (!fn) {  // a missing kernel is an error, never another path
+    rtg_set_error("render_camera: no kernel for stackSize %d", stackSize);
+    return RTG_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64), raytrace_lds_bytes(stackSize, bvh),
+                     (hipStream_t)stream, a, box, c, cam_pose(*cam), width, height, tilesX,
+                     dstDevice);
+  HIP_TRY(hipGetLastError());
+  return RTG_OK;
+}
+
+int rtg_render_camera(int device, const rtg_sphere* spheres, unsigned sphNum,
+                      const rtg_light* lights, unsigned lgtNum, const rtg_camera* cam,
+                      unsigned width, unsigned height, float zoom, float aliasFactor,
+                      int stackSize, rtg_vec* dstHost) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  Camera c;
+  int rc = check_frame("render_camera", cam, dstHost, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_stack(stackSize);
+  if (rc) return rc;
+  if ((sphNum && !spheres) || (lgtNum && !lights)) {
+    rtg_set_error("render_camera: null scene array");
+    return RTG_ERR_INVALID;
+  }
+  unsigned tilesX = 0;
+  if (!camera_blocks(width, height, &tilesX)) {
+    rtg_set_error("render_camera: frame too large (more than 2^31-1 workgroups)");
+    return RTG_ERR_INVALID;
+  }
+  return one_shot(device, spheres, sphNum, lights, lgtNum, nullptr, 0, dstHost,
+                  (size_t)width * height * sizeof(rtg_vec),
+                  [&](rtg_context* ctx, const void*, void* out) {
+                    return rtg_render_camera_device(ctx, cam, width, height, zoom, aliasFactor,
+                                                    stackSize, (rtg_vec*)out, nullptr);
+                  });
+}
+
+}  // extern "C"

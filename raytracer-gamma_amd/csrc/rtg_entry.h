@@ -1,5 +1,5 @@
 // rtg_entry.h — what the C ABI entry points of librtg.so share (rtg_kernel.hip,
-// rtg_gbuffer.hip, rtg_rays.hip): the HIP error return, the records' NaN form
+// rtg_gbuffer.hip, rtg_rays.hip, rtg_raytrace.hip, rtg_camera.hip): the HIP error return, the records' NaN form
 // and 32-byte store, the host forms' plain scene and thread bands, and the
 // one-shot body.  HIP translation units only.
 #pragma once
@@ -76,3 +76,7 @@ int one_shot(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_l
              const std::function<int(rtg_context* ctx, const void* dIn, void* dOut)>& launch);
 
 }  // namespace rtg
+
+// rtg_kernel.hip: a context's device, with or without a scene (the posed
+// camera's ray generator needs no scene); false when the context is null.
+bool rtg_context_device(const rtg_context* ctx, int* device);

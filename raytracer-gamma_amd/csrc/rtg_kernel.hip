@@ -394,6 +394,12 @@ bool rtg_context_scene(const rtg_context* ctx, SceneTables* t, int* device, RayB
   return true;
 }
 
+bool rtg_context_device(const rtg_context* ctx, int* device) {
+  if (!ctx) return false;
+  *device = ctx->device;
+  return true;
+}
+
 int rtg::one_shot(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
                   unsigned lgtNum, const void* in, size_t inBytes, void* out, size_t outBytes,
                   const std::function<int(rtg_context*, const void*, void*)>& launch) {

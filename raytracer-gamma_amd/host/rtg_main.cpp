@@ -48,6 +48,8 @@ static void usage() {
   printf("                           (id, t, point, normal)\n");
   printf("      --radiance   FILE    Write their colours (rayTrace's return at --depth and\n");
   printf("                           --semantics): 12-byte rtg_vec records\n");
+  printf("      --camera     POSE    Render from a posed camera: ex,ey,ez,tx,ty,tz[,ux,uy,uz] (eye,\n");
+  printf("                           target, up; up defaults to 0,1,0), rtg_camera_look_at\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -72,6 +74,8 @@ int main(int argc, char** argv) {
   std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut, radianceOut;
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
+  bool posed = false;
+  rtg_camera camera;
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* opt) -> const char* {
       if (++i >= argc) {
@@ -126,6 +130,15 @@ int main(int argc, char** argv) {
       hitsOut = need(a);
     } else if (!strcmp(a, "--radiance")) {
       radianceOut = need(a);
+    } else if (!strcmp(a, "--camera")) {
+      float v[9] = {0, 0, 0, 0, 0, 0, 0.f, 1.f, 0.f};
+      char tail = 0;
+      const int k = sscanf(need(a), "%f,%f,%f,%f,%f,%f,%f,%f,%f%c", v, v + 1, v + 2, v + 3, v + 4,
+                           v + 5, v + 6, v + 7, v + 8, &tail);
+      if (k != 6 && k != 9) { printf("Invalid camera (ex,ey,ez,tx,ty,tz[,ux,uy,uz])\n"); return 1; }
+      const rtg_vec eye = {v[0], v[1], v[2]}, target = {v[3], v[4], v[5]}, up = {v[6], v[7], v[8]};
+      check(rtg_camera_look_at(&eye, &target, &up, &camera), "rtg_camera_look_at");
+      posed = true;
     } else if (!strcmp(a, "--scene")) {
       sceneIn = need(a);
     } else if (!strcmp(a, "--save-scene")) {
@@ -150,6 +163,11 @@ int main(int argc, char** argv) {
   }
   if (raysIn.empty() && !radianceOut.empty()) {
     printf("--radiance needs --rays\n");
+    return 1;
+  }
+
+  if (posed && gpus) {
+    printf("--camera renders on one device\n");
     return 1;
   }
 
@@ -199,8 +217,12 @@ int main(int argc, char** argv) {
       rtg_vec* d = nullptr;
       if (hipMalloc(&d, pixels.size() * sizeof(rtg_vec)) != hipSuccess)
         check(RTG_ERR_NOMEM, "hipMalloc");
-      check(rtg_render_device(ctx, W, H, zoom, aa, (int)depth + 1, 16, 0, 1, d, nullptr),
-            "rtg_render_device");
+      if (posed)
+        check(rtg_render_camera_device(ctx, &camera, W, H, zoom, aa, (int)depth + 1, d, nullptr),
+              "rtg_render_camera_device");
+      else
+        check(rtg_render_device(ctx, W, H, zoom, aa, (int)depth + 1, 16, 0, 1, d, nullptr),
+              "rtg_render_device");
       if (hipMemcpy(pixels.data(), d, pixels.size() * sizeof(rtg_vec),
                     hipMemcpyDeviceToHost) != hipSuccess)
         check(RTG_ERR_HIP, "readback");
@@ -212,6 +234,10 @@ int main(int argc, char** argv) {
             "rtg_multi_render");
       printf("  %u GPUs: render %.3f ms (slowest device), gather+assemble %.3f ms\n", gpus,
              (double)tm[0], (double)tm[1]);
+    } else if (posed) {
+      check(rtg_render_camera((int)device, spheres.data(), nSph, lights.data(), nLgt, &camera, W, H,
+                              zoom, aa, (int)depth + 1, pixels.data()),
+            "rtg_render_camera");
     } else {
       check(rtg_render((int)device, spheres.data(), nSph, lights.data(), nLgt, W, H, zoom, aa,
                        (int)depth + 1, pixels.data()),

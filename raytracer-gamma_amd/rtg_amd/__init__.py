@@ -53,6 +53,10 @@ RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("dir", "<f4", 3)])
 SEGMENT_DTYPE = np.dtype([("a", "<f4", 3), ("b", "<f4", 3)])
 HIT_DTYPE = np.dtype([("id", "<i4"), ("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3)])
 assert RAY_DTYPE.itemsize == 24 and SEGMENT_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 32
+# rtg_camera (include/rtg.h): the posed camera
+CAMERA_DTYPE = np.dtype([("eye", "<f4", 3), ("right", "<f4", 3), ("up", "<f4", 3),
+                         ("back", "<f4", 3)])
+assert CAMERA_DTYPE.itemsize == 48
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -75,6 +79,9 @@ EXPORTED = [
     "rtg_intersect_device", "rtg_intersect", "rtg_intersect_host",
     "rtg_visible_device", "rtg_visible", "rtg_visible_host",
     "rtg_raytrace_device", "rtg_raytrace", "rtg_raytrace_host",
+    "rtg_camera_identity", "rtg_camera_look_at", "rtg_camera_sample_count",
+    "rtg_camera_rays_host", "rtg_camera_rays_device",
+    "rtg_render_camera_device", "rtg_render_camera", "rtg_render_camera_host",
 ]
 
 
@@ -163,6 +170,15 @@ def lib() -> ctypes.CDLL:
         L.rtg_raytrace_device.argtypes = [vp, vp, sz, i, vp, vp]
         L.rtg_raytrace.argtypes = [i, vp, u, vp, u, vp, sz, i, vp]
         L.rtg_raytrace_host.argtypes = [vp, u, vp, u, vp, sz, i, i, vp, i, i]
+        L.rtg_camera_identity.argtypes = [vp]
+        L.rtg_camera_identity.restype = None
+        L.rtg_camera_look_at.argtypes = [vp, vp, vp, vp]
+        L.rtg_camera_sample_count.argtypes = [f, ctypes.POINTER(u)]
+        L.rtg_camera_rays_host.argtypes = [vp, u, u, f, f, vp, i]
+        L.rtg_camera_rays_device.argtypes = [vp, vp, u, u, f, f, vp, vp]
+        L.rtg_render_camera_device.argtypes = [vp, vp, u, u, f, f, i, vp, vp]
+        L.rtg_render_camera.argtypes = [i, vp, u, vp, u, vp, u, u, f, f, i, vp]
+        L.rtg_render_camera_host.argtypes = [vp, u, vp, u, vp, u, u, f, f, i, i, vp, i, i]
 
         pu = ctypes.POINTER(u)
         L.rtg_scene_load.argtypes = [ctypes.c_char_p, vp, u, pu, vp, u, pu]
@@ -425,6 +441,101 @@ def raytrace_host(spheres, lights, rays, stack_size: int = 6, semantics: int = 0
     return out
 
 
+def _camera(cam) -> np.ndarray:
+    """A pose as one CAMERA_DTYPE record (a record, or 12 floats: eye, right, up, back)."""
+    a = np.asarray(cam)
+    if a.dtype != CAMERA_DTYPE:
+        a = np.ascontiguousarray(a, np.float32).reshape(12).view(CAMERA_DTYPE)
+    return np.ascontiguousarray(a).reshape(1)
+
+
+def camera_identity() -> np.ndarray:
+    """The reference's own camera as a pose (rtg_camera_identity): eye 0, right
+    +x, up +y, back +z."""
+    out = np.zeros(1, CAMERA_DTYPE)
+    lib().rtg_camera_identity(_ptr(out))
+    return out[0]
+
+
+def camera_look_at(eye, target, up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """The pose at `eye` looking at `target` (rtg_camera_look_at), in float32."""
+    e, t, u = (np.ascontiguousarray(v, np.float32).reshape(3) for v in (eye, target, up))
+    out = np.zeros(1, CAMERA_DTYPE)
+    _check(lib().rtg_camera_look_at(_ptr(e), _ptr(t), _ptr(u), _ptr(out)), "rtg_camera_look_at")
+    return out[0]
+
+
+def camera_sample_count(alias_factor: float) -> int:
+    """nAA of rtg_camera_sample_count: a pixel has nAA * nAA samples."""
+    n = ctypes.c_uint(0)
+    _check(lib().rtg_camera_sample_count(float(alias_factor), ctypes.byref(n)),
+           "rtg_camera_sample_count")
+    return n.value
+
+
+def camera_rays_host(cam, width: int, height: int, zoom: float = -4.0,
+                     alias_factor: float = 3.0, threads: int = 1) -> np.ndarray:
+    """The pose's sample rays on the host (rtg_camera_rays_host): (W*H*nAA*nAA, 6)
+    float32 (origin, dir), pixel order, a pixel's samples in the reference's order."""
+    c = _camera(cam)
+    n = width * height * camera_sample_count(alias_factor) ** 2
+    out = np.empty((n, 6), np.float32)
+    dst = out if n else np.zeros((1, 6), np.float32)
+    _check(lib().rtg_camera_rays_host(_ptr(c), width, height, float(zoom), float(alias_factor),
+                                      _ptr(dst), threads), "rtg_camera_rays_host")
+    return out
+
+
+def camera_rays(cam, width: int, height: int, zoom: float = -4.0, alias_factor: float = 3.0,
+                device: int = 0) -> np.ndarray:
+    """The same rays formed on the GPU (rtg_camera_rays_device) into a torch
+    tensor and downloaded; to keep them on the device use Context.camera_rays."""
+    if torch is None:
+        raise RtgError("camera_rays: needs torch for the device buffer")
+    n = width * height * camera_sample_count(alias_factor) ** 2
+    with torch.cuda.device(device):
+        buf = torch.empty((max(n, 1), 6), dtype=torch.float32, device="cuda")
+        ctx = Context(device)
+        try:
+            ctx.camera_rays(cam, width, height, buf.data_ptr(), zoom, alias_factor,
+                            stream=torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        finally:
+            ctx.close()
+    return buf[:n].cpu().numpy()
+
+
+def render_camera(spheres, lights, cam, width: int, height: int, zoom: float = -4.0,
+                  alias_factor: float = 3.0, stack_size: int = 6, device: int = 0) -> np.ndarray:
+    """One-shot frame of a posed camera on the GPU (rtg_render_camera): the
+    (H, W, 3) float32 framebuffer, per pixel the reference's fold of rayTrace
+    over the pose's sample rays, bit for bit."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    c = _camera(cam)
+    out = np.empty((height, width, 3), np.float32)
+    _check(lib().rtg_render_camera(device, _ptr(spheres), len(spheres), _ptr(lights), len(lights),
+                                   _ptr(c), width, height, float(zoom), float(alias_factor),
+                                   stack_size, _ptr(out)), "rtg_render_camera")
+    return out
+
+
+def render_camera_host(spheres, lights, cam, width: int, height: int, zoom: float = -4.0,
+                       alias_factor: float = 3.0, stack_size: int = 6, semantics: int = 0,
+                       walk: int = 0, threads: int = 1) -> np.ndarray:
+    """The same on the host (rtg_render_camera_host; no GPU needed); walk and
+    semantics as raytrace_host."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    c = _camera(cam)
+    out = np.empty((height, width, 3), np.float32)
+    _check(lib().rtg_render_camera_host(_ptr(spheres), len(spheres), _ptr(lights), len(lights),
+                                        _ptr(c), width, height, float(zoom), float(alias_factor),
+                                        stack_size, semantics, _ptr(out), walk, threads),
+           "rtg_render_camera_host")
+    return out
+
+
 class MultiContext:
     """Persistent multi-device handle (rtg_multi_*): RCCL communicator, contexts,
     streams and buffers kept across frames."""
@@ -623,6 +734,29 @@ class Context:
                                          ctypes.c_void_p(dst_ptr),
                                          ctypes.c_void_p(stream) if stream else None),
                "rtg_raytrace_device")
+
+    def render_camera(self, cam, width, height, dst_ptr: int, zoom=-4.0, alias_factor=3.0,
+                      stack_size=6, stream: int = 0):
+        """The posed camera's whole frame of the resident scene into dst_ptr
+        (device, an (H, W, 3) float32 tensor), asynchronously on `stream`, under
+        the context's semantics (rtg_render_camera_device)."""
+        c = _camera(cam)
+        _check(lib().rtg_render_camera_device(self._h, _ptr(c), width, height, float(zoom),
+                                              float(alias_factor), stack_size,
+                                              ctypes.c_void_p(dst_ptr),
+                                              ctypes.c_void_p(stream) if stream else None),
+               "rtg_render_camera_device")
+
+    def camera_rays(self, cam, width, height, dst_ptr: int, zoom=-4.0, alias_factor=3.0,
+                    stream: int = 0):
+        """The posed camera's sample rays into dst_ptr (device, W*H*nAA*nAA 24-byte
+        RAY_DTYPE records: an (N, 6) float32 tensor), asynchronously on `stream`
+        (rtg_camera_rays_device; the context needs no scene)."""
+        c = _camera(cam)
+        _check(lib().rtg_camera_rays_device(self._h, _ptr(c), width, height, float(zoom),
+                                            float(alias_factor), ctypes.c_void_p(dst_ptr),
+                                            ctypes.c_void_p(stream) if stream else None),
+               "rtg_camera_rays_device")
 
     def render_rows_device(self, width, height, rows_ptr: int, n_rows: int, dst_ptr: int,
                            zoom=-4.0, alias_factor=3.0, stack_size=6, stream: int = 0):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE]
+"""tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
 with the scene and the rays resident, on three batches of bench.py's frames:
@@ -30,7 +30,15 @@ camera's cull, the compacted launch and the launch-order feedback, and every
 table keyed to its own rays; the batch call has none of them.  The ratio
 raytrace / render is therefore the price of generality; it is reported, not
 gated.  The ordered colours must be the render's frame and the shuffled ones
-the ordered ones permuted.  GPU only.
+the ordered ones permuted.
+
+The posed camera (csrc/rtg_camera.hip) gets rows under "camera" (camera_rows
+below): the fused render at the identity pose next to the batch call and the
+render, at aa = 1 and aa = 3, the orbit pose, and the generator.
+--only-camera runs these alone; --mapping NAME records the build's lane-to-pixel
+mapping and --mapping-json FILE puts such a run of a build with another
+mapping next to this one's (how the 8 x 8 tile was chosen over 64 x 1).
+GPU only.
 """
 import argparse
 import json
@@ -91,12 +99,89 @@ def measure(fns, rounds, window_ms=300.0):
              "ms_max": round(max(v), 5), "launches_per_round": r} for v, r in zip(t, reps)]
 
 
+def orbit_pose(sph):
+    """The `orbit` pose of tests/test_camera_host.py for a scene: from 1.2
+    extents off the scene's centre, looking at it; zoom -12."""
+    c = sph["pos"].astype(np.float64)
+    r = np.abs(sph["radius"].astype(np.float64))[:, None]
+    lo, hi = (c - r).min(0), (c + r).max(0)
+    mid, s = (lo + hi) * 0.5, float((hi - lo).max())
+    return R.camera_look_at(mid + 1.2 * s * np.array([0.6, 0.35, 0.72]), mid), -12.0
+
+
+def camera_rows(args, W, H, rays, col, fb, stream):
+    """The posed camera (csrc/rtg_camera.hip), C3 and C5 at their stack sizes,
+    round by round in one process: (a) the fused render at the identity pose
+    and aa = 1 next to rtg_raytrace_device of the same pixel-ordered rays and
+    rtg_render_device at alias_factor = 1: the same trees, the fused kernel
+    moving 24 B per ray less than the batch call; (b) the identity pose at
+    aa = 3 next to rtg_render_device at aa = 3: the price of a frame that is
+    exact for any viewpoint; (c) the orbit pose at aa = 3, recorded only; and
+    the generator's time for the aa = 3 frame next to the bytes it writes.
+    The identity frames must be the render's."""
+    n = W * H
+    fc = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    gen = torch.empty((n * 9, 6), dtype=torch.float32, device="cuda")
+    ident = R.camera_identity()
+    out, ok = {"mapping": args.mapping}, True
+
+    def same(a, b):
+        return bool((a.view(torch.int32) == b.view(torch.int32)).all())
+
+    for name in ("c3", "c5"):
+        S = CONFIGS[name][4] + 1
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        orbit, ozoom = orbit_pose(sph)
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        c1, b1, r1 = measure(
+            [lambda: ctx.render_camera(ident, W, H, fc.data_ptr(), -4.0, 1.0, S, stream),
+             lambda: ctx.raytrace_device(rays.data_ptr(), n, col.data_ptr(), S, stream),
+             lambda: ctx.render_device(W, H, fb.data_ptr(), alias_factor=1.0, stack_size=S,
+                                       stream=stream)], args.rounds)
+        eq1 = same(fc, fb) and same(col, fb.view(-1, 3))
+        c3, r3, o3, g3 = measure(
+            [lambda: ctx.render_camera(ident, W, H, fc.data_ptr(), -4.0, 3.0, S, stream),
+             lambda: ctx.render_device(W, H, fb.data_ptr(), alias_factor=3.0, stack_size=S,
+                                       stream=stream),
+             lambda: ctx.render_camera(orbit, W, H, col.data_ptr(), ozoom, 3.0, S, stream),
+             lambda: ctx.camera_rays(orbit, W, H, gen.data_ptr(), ozoom, 3.0, stream)],
+            args.rounds)
+        ctx.close()
+        eq3 = same(fc, fb)
+        ok = ok and eq1 and eq3
+        g3["bytes"] = n * 9 * 24
+        g3["GB_per_s"] = round(g3["bytes"] / (g3["ms_median"] * 1e-3) / 1e9, 1)
+        out[name] = {
+            "stack_size": S, "camera_aa1": c1, "raytrace_aa1": b1, "render_aa1": r1,
+            "camera_over_raytrace_aa1": round(c1["ms_median"] / b1["ms_median"], 3),
+            "camera_over_render_aa1": round(c1["ms_median"] / r1["ms_median"], 3),
+            "camera_aa3": c3, "render_aa3": r3, "orbit_aa3": o3,
+            "camera_over_render_aa3": round(c3["ms_median"] / r3["ms_median"], 3),
+            "generator_aa3": g3,
+            "identity_aa1_equals_render_and_raytrace": eq1, "identity_aa3_equals_render": eq3}
+    return out, ok
+
+
+def finish(args, res, ok):
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res), flush=True)
+    sys.exit(0 if ok else 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rays", "bench.json"))
     ap.add_argument("--parent-json", default="")
     ap.add_argument("--commit", default="", help="recorded as the commit the numbers are of")
+    ap.add_argument("--only-camera", action="store_true", help="the posed camera's rows alone")
+    ap.add_argument("--mapping", default="8x8", help="recorded as the library's lane-to-pixel mapping")
+    ap.add_argument("--mapping-json", default="",
+                    help="a --only-camera file of a build with another mapping, for the side-by-side")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_rays: needs a GPU")
@@ -113,6 +198,13 @@ def main():
     stream = torch.cuda.current_stream().cuda_stream
     res = {"W": W, "H": H, "rays": n, "device": R.device_info(0), "rounds": args.rounds,
            "commit": args.commit, "batches": {}}
+
+    if args.only_camera:
+        del hits, hits2, gb, shuffled
+        col = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        fb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+        res["camera"], ok = camera_rows(args, W, H, rays, col, fb, stream)
+        finish(args, res, ok)
 
     def rate(m):
         m["Mrays_per_s"] = round(n / (m["ms_median"] * 1e-3) / 1e6, 1)
@@ -177,15 +269,19 @@ def main():
             "shuffled_over_ordered": round(s["ms_median"] / o["ms_median"], 3),
             "ordered_colours_equal_render": frame,
             "shuffled_colours_are_ordered_permuted": permuted}
+    del col2, shuffled
+    res["camera"], cam_ok = camera_rows(args, W, H, rays, col, fb, stream)
+    ok = ok and cam_ok
+    if args.mapping_json:
+        with open(args.mapping_json) as f:
+            other = json.load(f)["camera"]
+        for name in ("c3", "c5"):
+            res["camera"][name]["mapping_" + other["mapping"]] = {
+                k: other[name][k]["ms_median"] for k in ("camera_aa1", "camera_aa3", "orbit_aa3")}
     if args.parent_json:
         with open(args.parent_json) as f:
             res["parent_commit"] = json.load(f)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res), flush=True)
-    sys.exit(0 if same and res["c5_shuffled_hits_are_ordered_permuted"] and ok else 1)
+    finish(args, res, same and res["c5_shuffled_hits_are_ordered_permuted"] and ok)
 
 
 if __name__ == "__main__":
