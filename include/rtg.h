@@ -355,8 +355,8 @@ int rtg_visible_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_segme
  * than 2^31-1 workgroups (64 rays each).
  *
  * Out of scope: a per-ray intensity, a caller-chosen refractive material for
- * the ray's medium, multi-GPU batches, and sorting a batch for coherence.
- * (A frame's rays and its fold: the posed camera, below.) */
+ * the ray's medium, and multi-GPU batches.  (Ordering a batch for coherence:
+ * the ray order, below.  A frame's rays and its fold: the posed camera.) */
 int rtg_raytrace_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
                         int stackSize, rtg_vec* dstDevice, void* stream);
 /* One-shot: uploads the scene and the rays, runs on `device`, downloads n colours. */
@@ -372,6 +372,88 @@ int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum,
                       const rtg_light* lights, unsigned lgtNum, const rtg_ray* rays,
                       size_t n, int stackSize, int semantics, rtg_vec* dstHost,
                       int walk, int nthreads);
+
+/* ---- ray order: coherence ordering of a batch, and indexed launches ----
+ * The 64 rays of a wave walk the scene together, so a batch in no particular
+ * order (ambient occlusion, light baking, probes, secondary rays) costs several
+ * times what the same rays cost in a coherent order (README).  Rays are
+ * independent, so launching them in another order changes no output bit.
+ * rtg_ray_order* computes such an order; the _indexed launches take it (or
+ * any other index list) and still write every result at its ray's own place.
+ *
+ * THE KEY of ray (origin o, direction d), 50 used bits of 64, bit 0 lowest:
+ *   bits 49..20  the origin's cell, 10 bits per axis, Morton-interleaved: bit
+ *                i of the x, y, z cell index at bit 20 + 3 i, + 3 i + 1, + 3 i + 2
+ *   bits 19..0   the direction's octahedral bin, 10 bits per axis, Morton-
+ *                interleaved: bit i of u, v at bit 2 i, 2 i + 1
+ * all in float arithmetic without contraction (the same bits on host and
+ * device):
+ *   key box   per axis lo = min(c - |r|), hi = max(c + |r|) over the scene's
+ *             spheres (a sphere with a non-finite centre component or radius
+ *             is skipped; no sphere left: [-1, 1]^3), computed when the scene
+ *             is set; scale = 1024 / (hi - lo), or 0 when hi <= lo or either
+ *             the width or the quotient is not finite.
+ *   cell      per axis (int)clamp((o - lo) * scale, 0, 1023), the clamp done
+ *             in float with NaN going to 0 (so a NaN or -inf coordinate is in
+ *             cell 0, +inf in cell 1023; origins outside the box clamp to its
+ *             faces).
+ *   bin       s = (|dx| + |dy|) + |dz|; s zero, NaN or infinite: (0, 0).
+ *             Otherwise p = (dx / s, dy / s), and for dz < 0 the fold p =
+ *             ((1 - |py|) sign(dx), (1 - |px|) sign(dy)) (sign(0) = +1);
+ *             u = (int)clamp((px + 1) * 512, 0, 1023), v likewise of py.
+ * A segment (a, b) of rtg_visible has the key of the ray (a, b - a), the
+ * difference taken in float.
+ *
+ * order[k] is the index of the ray at position k of the batch sorted by key;
+ * the sort is stable (equal keys keep index order), so the device and the host
+ * form give the same words.  keys, when not NULL, receives key(ray i) at
+ * keys[i], in batch order.
+ *
+ * rtg_ray_order_device: asynchronous on `stream`; allocates nothing, takes
+ * none of the context's render scratch, may be mixed with every other call on
+ * the context; needs the context's scene (the key box).  scratchDevice: at
+ * least rtg_ray_order_scratch(n) bytes of device memory, 16-byte aligned,
+ * owned by the call until it has finished on the stream.  The sort is a radix
+ * sort by 8-bit digits in tiles of RTG_ORDER_TILE_RAYS rays, with a scan over
+ * RTG_ORDER_SCAN_TILES tiles a step; a digit position on which every key
+ * agrees costs nothing.  n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID
+ * with a message, before any GPU call, for a null ray, order or scratch
+ * buffer, an unknown kind, n > 2^32 - 1, a scratch that is too small or not
+ * 16-byte aligned, or a context without a scene.
+ *
+ * The _indexed launches: lane k of the launch takes ray order[k] and writes
+ * its result at order[k], so the outputs are in the caller's order and, for
+ * any permutation, bit for bit those of the un-indexed call.  `order` is any
+ * list of n indices; an entry >= n is skipped and never dereferenced, a
+ * repeated entry writes the same record twice, a record no entry names is not
+ * written.  Arguments are checked as in the un-indexed calls; a null order is
+ * RTG_ERR_INVALID.
+ *
+ * Out of scope: reordering inside the un-indexed calls, re-sorting secondary
+ * rays between bounces, multi-GPU batches. */
+#define RTG_ORDER_RAYS 0      /* the batch holds rtg_ray records */
+#define RTG_ORDER_SEGMENTS 1  /* the batch holds rtg_segment records */
+#define RTG_ORDER_TILE_RAYS 1024
+#define RTG_ORDER_SCAN_TILES 256
+int rtg_ray_order_scratch(size_t n, size_t* bytes);
+int rtg_ray_order_device(rtg_context* ctx, const void* raysDevice, size_t n, int kind,
+                         unsigned* orderDevice, unsigned long long* keysDevice /* may be NULL */,
+                         void* scratchDevice, size_t scratchBytes, void* stream);
+/* The same on the host, no GPU call: the same key function and
+ * std::stable_sort.  nthreads <= 0: 1 (the keys; the result does not depend
+ * on it). */
+int rtg_ray_order_host(const rtg_sphere* spheres, unsigned sphNum, const void* rays, size_t n,
+                       int kind, unsigned* orderHost, unsigned long long* keysHost /* may be NULL */,
+                       int nthreads);
+int rtg_intersect_indexed_device(rtg_context* ctx, const rtg_ray* raysDevice,
+                                 const unsigned* orderDevice, size_t n, rtg_hit* hitsDevice,
+                                 void* stream);
+int rtg_visible_indexed_device(rtg_context* ctx, const rtg_segment* segsDevice,
+                               const unsigned* orderDevice, size_t n, unsigned char* outDevice,
+                               void* stream);
+int rtg_raytrace_indexed_device(rtg_context* ctx, const rtg_ray* raysDevice,
+                                const unsigned* orderDevice, size_t n, int stackSize,
+                                rtg_vec* dstDevice, void* stream);
 
 /* ---- posed camera: rays and frames from any viewpoint ----
  * The reference keeps its camera at the origin looking down -z (main.cpp:

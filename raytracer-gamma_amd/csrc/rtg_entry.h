@@ -1,5 +1,6 @@
 // rtg_entry.h — what the C ABI entry points of librtg.so share (rtg_kernel.hip,
-// rtg_gbuffer.hip, rtg_rays.hip, rtg_raytrace.hip, rtg_camera.hip): the HIP error return, the records' NaN form
+// rtg_gbuffer.hip, rtg_rays.hip, rtg_raytrace.hip, rtg_order.hip, rtg_camera.hip): the HIP error
+// return, the records' NaN form
 // and 32-byte store, the host forms' plain scene and thread bands, and the
 // one-shot body.  HIP translation units only.
 #pragma once

@@ -24,6 +24,7 @@
 #include "rtg.h"
 #include "rtg_entry.h"
 #include "rtg_trace_kernels.h"
+#include "rtg_order.h"
 #include "rtg_rays.h"
 #include "rtg_scene_pack.h"
 
@@ -264,6 +265,7 @@ struct rtg_context {
   int device = 0;
   alignas(8) rtg::SceneTables scene{};  // the resident scene's tables (kSceneTables)
   rtg::RayBox rayBox{};  // the BVH's origin box, for the batch ray queries (rtg_rays.hip)
+  rtg::KeyBox keyBox{};  // the sphere bounds, for the ray order's sort key (rtg_order.hip)
   unsigned* maxScratch = nullptr;
   unsigned long long* diag = nullptr;  // probe counters of diagnostic variants
   unsigned long long* counts = nullptr;  // unit counters of the counting build (variant 120)
@@ -385,12 +387,13 @@ static void free_scene(rtg_context* c) {
 }
 
 bool rtg_context_scene(const rtg_context* ctx, SceneTables* t, int* device, RayBox* box,
-                       int* semantics) {
+                       int* semantics, KeyBox* keyBox) {
   if (!ctx || !ctx->hasScene) return false;
   *t = ctx->scene;
   *device = ctx->device;
   if (box) *box = ctx->rayBox;
   if (semantics) *semantics = ctx->semantics;
+  if (keyBox) *keyBox = ctx->keyBox;
   return true;
 }
 
@@ -754,6 +757,9 @@ int rtg_context_set_scene(rtg_context* ctx, const rtg_sphere* spheres, unsigned 
   ctx->scene.m = lgtNum;
   ctx->scene.n4 = ps.n4;
   ctx->rayBox = ray_box(ps.originBox);
+  float keyLo[3], keyHi[3];
+  key_bounds(spheres, sphNum, keyLo, keyHi);
+  ctx->keyBox = key_box(keyLo, keyHi);
   ctx->hasScene = true;
   ++ctx->sceneGen;  // new geometry keys: no launch-order feedback from the old scene
   const auto tEnd = clk::now();

@@ -7,7 +7,11 @@
 // the end of the batch stay in the wave as inactive queries (they load the
 // batch's last ray, store nothing): the BVH walk is wave-uniform, no lane
 // returns early from it.  One translation unit, no instantiation per stack
-// size; the launches take none of rtg_context's render scratch.
+// size; the launches take none of rtg_context's render scratch.  The _indexed
+// forms (rtg.h, the ray order) are the same kernel bodies with an index list:
+// lane k works on record order[k] (ray_slot).  They are kernels of their own
+// (two more instantiations each, in this one translation unit), so that the
+// un-indexed kernels keep the code they had (DESIGN).
 //
 // The two queries themselves (ray_delta, ray_closest, ray_blocked) are in
 // rtg_rays.h, shared with the batch ray tracer (rtg_raytrace.hip), which asks
@@ -242,17 +246,34 @@ static void visible_host_range(const HostRayJob& j, const rtg_segment* segs, siz
 template <bool kBvh>
 using RayScene = DevScene<false, 64, kBvh, 0>;
 
-// One lane per ray; n > 0.  Lanes past n take the last ray and stay inactive.
+// Which record lane k of a launch works on: k itself (order null, a constant
+// of the un-indexed kernels), or order[k] of an _indexed launch.
+// Lanes past n, and lanes whose entry is not an index of the batch (>= n:
+// never dereferenced), are not `active`: they take the last record and store
+// nothing.
+__device__ __forceinline__ size_t ray_slot(const unsigned* __restrict__ order, size_t k, size_t n,
+                                           bool& active) {
+  active = k < n;
+  size_t at = active ? k : n - 1;
+  if (order) {
+    const unsigned e = order[at];  // at < n: inside the index list
+    active = active && e < n;
+    at = active ? (size_t)e : n - 1;
+  }
+  return at;
+}
+
+// One lane per ray; n > 0.  Inactive lanes (ray_slot) take the last ray.
 template <bool kBvh>
-__global__ __launch_bounds__(64) void intersect_kernel(const SceneTables a, const RayBox box,
-                                                       const rtg_ray* __restrict__ rays, size_t n,
-                                                       rtg_hit* __restrict__ hits) {
-  __shared__ int stk[kBvh ? 64 : 1];
+__device__ __forceinline__ void intersect_body(const SceneTables& a, const RayBox& box,
+                                               const rtg_ray* __restrict__ rays,
+                                               const unsigned* __restrict__ order, size_t n,
+                                               rtg_hit* __restrict__ hits, int* stk) {
   RayScene<kBvh> sc;
   bind_scene_no_frames(sc, a, stk);  // stk: the wave's BVH traversal stack
-  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
-  const bool active = k < n;
-  const float* r = reinterpret_cast<const float*>(rays + (active ? k : n - 1));  // 24 B
+  bool active;
+  const size_t k = ray_slot(order, (size_t)blockIdx.x * 64 + threadIdx.x, n, active);
+  const float* r = reinterpret_cast<const float*>(rays + k);  // k < n: 24 B of the batch
   const V3 o = v3(r[0], r[1], r[2]);
   const V3 d = v3(r[3], r[4], r[5]);
   float t;
@@ -268,21 +289,53 @@ __global__ __launch_bounds__(64) void intersect_kernel(const SceneTables a, cons
 }
 
 template <bool kBvh>
-__global__ __launch_bounds__(64) void visible_kernel(const SceneTables a, const RayBox box,
-                                                     const rtg_segment* __restrict__ segs,
-                                                     size_t n, unsigned char* __restrict__ out) {
+__global__ __launch_bounds__(64) void intersect_kernel(const SceneTables a, const RayBox box,
+                                                       const rtg_ray* __restrict__ rays, size_t n,
+                                                       rtg_hit* __restrict__ hits) {
   __shared__ int stk[kBvh ? 64 : 1];
+  intersect_body<kBvh>(a, box, rays, nullptr, n, hits, stk);
+}
+
+template <bool kBvh>
+__global__ __launch_bounds__(64) void intersect_indexed_kernel(
+    const SceneTables a, const RayBox box, const rtg_ray* __restrict__ rays,
+    const unsigned* __restrict__ order, size_t n, rtg_hit* __restrict__ hits) {
+  __shared__ int stk[kBvh ? 64 : 1];
+  intersect_body<kBvh>(a, box, rays, order, n, hits, stk);
+}
+
+template <bool kBvh>
+__device__ __forceinline__ void visible_body(const SceneTables& a, const RayBox& box,
+                                             const rtg_segment* __restrict__ segs,
+                                             const unsigned* __restrict__ order, size_t n,
+                                             unsigned char* __restrict__ out, int* stk) {
   RayScene<kBvh> sc;
   bind_scene_no_frames(sc, a, stk);  // stk: the wave's BVH traversal stack
-  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
-  const bool active = k < n;
-  const float* r = reinterpret_cast<const float*>(segs + (active ? k : n - 1));  // 24 B
+  bool active;
+  const size_t k = ray_slot(order, (size_t)blockIdx.x * 64 + threadIdx.x, n, active);
+  const float* r = reinterpret_cast<const float*>(segs + k);  // k < n: 24 B of the batch
   const V3 pa = v3(r[0], r[1], r[2]);
   const V3 pb = v3(r[3], r[4], r[5]);
   float gap;
   const V3 d = segment_ray(pa, pb, gap);
   const bool blk = ray_blocked<kBvh>(sc, box, pa, d, gap, active);
   if (active) out[k] = blk ? 0 : 1;  // k < n
+}
+
+template <bool kBvh>
+__global__ __launch_bounds__(64) void visible_kernel(const SceneTables a, const RayBox box,
+                                                     const rtg_segment* __restrict__ segs,
+                                                     size_t n, unsigned char* __restrict__ out) {
+  __shared__ int stk[kBvh ? 64 : 1];
+  visible_body<kBvh>(a, box, segs, nullptr, n, out, stk);
+}
+
+template <bool kBvh>
+__global__ __launch_bounds__(64) void visible_indexed_kernel(
+    const SceneTables a, const RayBox box, const rtg_segment* __restrict__ segs,
+    const unsigned* __restrict__ order, size_t n, unsigned char* __restrict__ out) {
+  __shared__ int stk[kBvh ? 64 : 1];
+  visible_body<kBvh>(a, box, segs, order, n, out, stk);
 }
 
 }  // namespace rtg
@@ -368,8 +421,9 @@ int rtg_visible_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_segme
   return RTG_OK;
 }
 
-int rtg_intersect_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
-                         rtg_hit* hitsDevice, void* stream) {
+// The device launch of rtg_intersect_device (order null) and of its _indexed form.
+static int intersect_launch(rtg_context* ctx, const rtg_ray* raysDevice, const unsigned* order,
+                            bool indexed, size_t n, rtg_hit* hitsDevice, void* stream) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
   SceneTables a{};
@@ -387,21 +441,32 @@ int rtg_intersect_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
     rtg_set_error("intersect: hits not 16-byte aligned");
     return RTG_ERR_INVALID;
   }
+  if (indexed && !order) {
+    rtg_set_error("intersect: null order buffer");
+    return RTG_ERR_INVALID;
+  }
   if (n == 0) return RTG_OK;
   unsigned blocks;
   const int rc = ray_blocks("intersect", n, &blocks);
   if (rc) return rc;
-  void (*fn)(const SceneTables, const RayBox, const rtg_ray*, size_t, rtg_hit*) =
-      a.bvhNodes ? intersect_kernel<true> : intersect_kernel<false>;
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, raysDevice, n,
-                     hitsDevice);
+  if (indexed) {
+    void (*fn)(const SceneTables, const RayBox, const rtg_ray*, const unsigned*, size_t,
+               rtg_hit*) = a.bvhNodes ? intersect_indexed_kernel<true> : intersect_indexed_kernel<false>;
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, raysDevice,
+                       order, n, hitsDevice);
+  } else {
+    void (*fn)(const SceneTables, const RayBox, const rtg_ray*, size_t, rtg_hit*) =
+        a.bvhNodes ? intersect_kernel<true> : intersect_kernel<false>;
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, raysDevice, n,
+                       hitsDevice);
+  }
   HIP_TRY(hipGetLastError());
   return RTG_OK;
 }
 
-int rtg_visible_device(rtg_context* ctx, const rtg_segment* segsDevice, size_t n,
-                       unsigned char* outDevice, void* stream) {
+static int visible_launch(rtg_context* ctx, const rtg_segment* segsDevice, const unsigned* order,
+                          bool indexed, size_t n, unsigned char* outDevice, void* stream) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
   SceneTables a{};
@@ -415,17 +480,51 @@ int rtg_visible_device(rtg_context* ctx, const rtg_segment* segsDevice, size_t n
     rtg_set_error("visible: null %s buffer", segsDevice ? "output" : "segment");
     return RTG_ERR_INVALID;
   }
+  if (indexed && !order) {
+    rtg_set_error("visible: null order buffer");
+    return RTG_ERR_INVALID;
+  }
   if (n == 0) return RTG_OK;
   unsigned blocks;
   const int rc = ray_blocks("visible", n, &blocks);
   if (rc) return rc;
-  void (*fn)(const SceneTables, const RayBox, const rtg_segment*, size_t, unsigned char*) =
-      a.bvhNodes ? visible_kernel<true> : visible_kernel<false>;
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, segsDevice, n,
-                     outDevice);
+  if (indexed) {
+    void (*fn)(const SceneTables, const RayBox, const rtg_segment*, const unsigned*, size_t,
+               unsigned char*) =
+        a.bvhNodes ? visible_indexed_kernel<true> : visible_indexed_kernel<false>;
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, segsDevice,
+                       order, n, outDevice);
+  } else {
+    void (*fn)(const SceneTables, const RayBox, const rtg_segment*, size_t, unsigned char*) =
+        a.bvhNodes ? visible_kernel<true> : visible_kernel<false>;
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, box, segsDevice, n,
+                       outDevice);
+  }
   HIP_TRY(hipGetLastError());
   return RTG_OK;
+}
+
+int rtg_intersect_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n,
+                         rtg_hit* hitsDevice, void* stream) {
+  return intersect_launch(ctx, raysDevice, nullptr, false, n, hitsDevice, stream);
+}
+
+int rtg_intersect_indexed_device(rtg_context* ctx, const rtg_ray* raysDevice,
+                                 const unsigned* orderDevice, size_t n, rtg_hit* hitsDevice,
+                                 void* stream) {
+  return intersect_launch(ctx, raysDevice, orderDevice, true, n, hitsDevice, stream);
+}
+
+int rtg_visible_device(rtg_context* ctx, const rtg_segment* segsDevice, size_t n,
+                       unsigned char* outDevice, void* stream) {
+  return visible_launch(ctx, segsDevice, nullptr, false, n, outDevice, stream);
+}
+
+int rtg_visible_indexed_device(rtg_context* ctx, const rtg_segment* segsDevice,
+                               const unsigned* orderDevice, size_t n, unsigned char* outDevice,
+                               void* stream) {
+  return visible_launch(ctx, segsDevice, orderDevice, true, n, outDevice, stream);
 }
 
 int rtg_intersect(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_ray* rays,

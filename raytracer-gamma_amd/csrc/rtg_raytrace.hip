@@ -87,7 +87,9 @@
 // whose tree is done has left, and the wave-level tests of the queries
 // (all / any, the wave-uniform BVH walk and its LDS stack) are over the lanes
 // present, as in the render kernels.  Lanes past the end of the batch leave
-// before the trace.
+// before the trace.  rtg_raytrace_indexed_device (the ray order, rtg.h) is the
+// same kernel with an index list: lane k traces ray order[k] and writes
+// dst[order[k]]; a lane whose entry is not an index of the batch leaves too.
 //
 // FP contract: the Makefile's FPFLAGS, as every kernel.
 //
@@ -225,8 +227,10 @@ int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_ligh
   return RTG_OK;
 }
 
-int rtg_raytrace_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n, int stackSize,
-                        rtg_vec* dstDevice, void* stream) {
+// The device launch of rtg_raytrace_device (order null) and of its _indexed form.
+static int raytrace_launch(rtg_context* ctx, const rtg_ray* raysDevice, const unsigned* order,
+                           bool indexed, size_t n, int stackSize, rtg_vec* dstDevice,
+                           void* stream) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
   SceneTables a{};
@@ -244,6 +248,10 @@ int rtg_raytrace_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n, i
     rtg_set_error("raytrace: stackSize %d outside [1, %d]", stackSize, RTG_MAX_STACK);
     return RTG_ERR_INVALID;
   }
+  if (indexed && !order) {
+    rtg_set_error("raytrace: null order buffer");
+    return RTG_ERR_INVALID;
+  }
   if (n == 0) return RTG_OK;
   const size_t blocks = (n + 63) / 64;  // one-wave workgroups
   if (blocks > 0x7FFFFFFFu) {
@@ -258,9 +266,20 @@ int rtg_raytrace_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n, i
   }
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64), raytrace_lds_bytes(stackSize, bvh),
-                     (hipStream_t)stream, a, box, raysDevice, n, dstDevice);
+                     (hipStream_t)stream, a, box, raysDevice, order, n, dstDevice);
   HIP_TRY(hipGetLastError());
   return RTG_OK;
+}
+
+int rtg_raytrace_device(rtg_context* ctx, const rtg_ray* raysDevice, size_t n, int stackSize,
+                        rtg_vec* dstDevice, void* stream) {
+  return raytrace_launch(ctx, raysDevice, nullptr, false, n, stackSize, dstDevice, stream);
+}
+
+int rtg_raytrace_indexed_device(rtg_context* ctx, const rtg_ray* raysDevice,
+                                const unsigned* orderDevice, size_t n, int stackSize,
+                                rtg_vec* dstDevice, void* stream) {
+  return raytrace_launch(ctx, raysDevice, orderDevice, true, n, stackSize, dstDevice, stream);
 }
 
 int rtg_raytrace(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,

@@ -9,7 +9,8 @@
 
 namespace rtg {
 
-typedef void (*RayTraceFn)(const SceneTables, const RayBox, const rtg_ray*, size_t, rtg_vec*);
+typedef void (*RayTraceFn)(const SceneTables, const RayBox, const rtg_ray*, const unsigned*, size_t,
+                           rtg_vec*);
 
 // The kernel's LDS image, one wave: the lanes' frame colours as in the render
 // kernels (frame_lds_levels), then the wave's 64-entry BVH traversal stack.
@@ -19,19 +20,28 @@ constexpr size_t raytrace_lds_bytes(int S, bool bvh) {
 
 // One lane per ray, one-wave workgroups; n > 0.  Lanes past n trace nothing
 // and store nothing (the queries' wave-level tests are over the lanes in
-// them).  dst[k] = rayTrace(ray k) before main.cpp:442-445 scales it.
+// them).  dst[k] = rayTrace(ray k) before main.cpp:442-445 scales it.  With an
+// index list (`order` not null, the _indexed launch: a kernel argument, so the
+// select is wave-uniform) lane k works on ray order[k] instead; a lane whose
+// entry is not an index of the batch (>= n, never dereferenced) leaves like a
+// lane past n.
 template <int S, bool kBvh, bool kCL>
 __global__ __launch_bounds__(64) void raytrace_kernel(const SceneTables a, const RayBox box,
-                                                      const rtg_ray* __restrict__ rays, size_t n,
-                                                      rtg_vec* __restrict__ dst) {
+                                                      const rtg_ray* __restrict__ rays,
+                                                      const unsigned* __restrict__ order,
+                                                      size_t n, rtg_vec* __restrict__ dst) {
   extern __shared__ float4 lds4[];
   constexpr int NFL = frame_lds_levels(S, kBvh);
   DevScene<false, 64, kBvh, 0> sc;
   sc.lfr = reinterpret_cast<FrameC*>(lds4) + threadIdx.x;
   sc.nfl = NFL;
   bind_scene(sc, a, reinterpret_cast<int*>(lds4 + NFL * 64));  // the stack: kBvh only
-  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+  size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (k >= n) return;
+  if (order) {
+    k = order[k];  // k < n: inside the index list
+    if (k >= n) return;
+  }
   const float* r = reinterpret_cast<const float*>(rays + k);  // k < n: 24 B of the batch
   const V3 o = v3(r[0], r[1], r[2]);
   const V3 d = v3(r[3], r[4], r[5]);

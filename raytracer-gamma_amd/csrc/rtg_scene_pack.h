@@ -652,6 +652,33 @@ inline void cone_masks(const rtg_sphere* spheres, unsigned n, std::vector<unsign
 // hold sphere slots only.  Returns false (no BVH) for non-finite scenes,
 // coordinates beyond 2^56 or an implausibly deep tree.
 
+// The key box of a ray batch's coherence sort key (rtg_order.h, rtg.h): the
+// scene's sphere bounds per axis, lo = min(c - |r|) and hi = max(c + |r|) in
+// float arithmetic.  A sphere with a non-finite centre component or radius is
+// skipped; with no sphere left the box is [-1, 1]^3.  Every scene has one,
+// with or without a BVH.  The one place it is computed: the context
+// (rtg_context_set_scene) and the host form (rtg_ray_order_host) both call it.
+inline void key_bounds(const rtg_sphere* spheres, unsigned n, float lo[3], float hi[3]) {
+  bool any = false;
+  for (unsigned i = 0; i < n; ++i) {
+    const float c[3] = {spheres[i].pos.x, spheres[i].pos.y, spheres[i].pos.z};
+    const float r = fabsf(spheres[i].radius);
+    const float inf = __builtin_inff();
+    if (!(fabsf(c[0]) < inf && fabsf(c[1]) < inf && fabsf(c[2]) < inf && r < inf)) continue;
+    for (int a = 0; a < 3; ++a) {
+      const float l = c[a] - r, h = c[a] + r;
+      lo[a] = (!any || l < lo[a]) ? l : lo[a];
+      hi[a] = (!any || h > hi[a]) ? h : hi[a];
+    }
+    any = true;
+  }
+  if (!any)
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = -1.f;
+      hi[a] = 1.f;
+    }
+}
+
 // The origin box B* of a scene: every ray origin the kernel queries — the
 // camera at 0 (main.cpp:417), hit points (within r_h + mu_h of their sphere,
 // mu_h = 2^-8 (|p| + |r_h|) <= 2^-8 (diam B* + r_max), rtg_trace.h) and the

@@ -1201,12 +1201,14 @@ RTG_DECL(14) RTG_DECL(15) RTG_DECL(16)
 #undef RTG_DECL
 
 struct RayBox;  // rtg_rays.h
+struct KeyBox;  // rtg_order.h
 
 }  // namespace rtg
 
 // rtg_kernel.hip: a context's device, its scene tables and, when asked for,
-// the BVH's origin box (the batch ray queries) and its semantics
-// (rtg_context_set_semantics: the batch ray tracer); false when the context
-// is null or has no scene.
+// the BVH's origin box (the batch ray queries), its semantics
+// (rtg_context_set_semantics: the batch ray tracer) and the sort key's box
+// (the ray order); false when the context is null or has no scene.
 bool rtg_context_scene(const rtg_context* ctx, rtg::SceneTables* t, int* device,
-                       rtg::RayBox* box = nullptr, int* semantics = nullptr);
+                       rtg::RayBox* box = nullptr, int* semantics = nullptr,
+                       rtg::KeyBox* keyBox = nullptr);

@@ -44,6 +44,9 @@ static void usage() {
   printf("      --rays       FILE    Also intersect the rays of FILE with the scene: raw little-endian\n");
   printf("                           24-byte rtg_ray records (origin, dir); needs --hits and/or\n");
   printf("                           --radiance\n");
+  printf("      --sort-rays          With --rays: order the batch for coherence on the device\n");
+  printf("                           (rtg_ray_order_device) and run it through the indexed\n");
+  printf("                           launches; the files written are the same bytes\n");
   printf("      --hits       FILE    Write their closest hits: 32-byte rtg_hit records\n");
   printf("                           (id, t, point, normal)\n");
   printf("      --radiance   FILE    Write their colours (rayTrace's return at --depth and\n");
@@ -75,6 +78,7 @@ int main(int argc, char** argv) {
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   bool posed = false;
+  bool sortRays = false;
   rtg_camera camera;
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* opt) -> const char* {
@@ -126,6 +130,8 @@ int main(int argc, char** argv) {
       gbufOut = need(a);
     } else if (!strcmp(a, "--rays")) {
       raysIn = need(a);
+    } else if (!strcmp(a, "--sort-rays")) {
+      sortRays = true;
     } else if (!strcmp(a, "--hits")) {
       hitsOut = need(a);
     } else if (!strcmp(a, "--radiance")) {
@@ -159,6 +165,10 @@ int main(int argc, char** argv) {
 
   if (raysIn.empty() ? !hitsOut.empty() : (hitsOut.empty() && radianceOut.empty())) {
     printf("--rays and --hits go together\n");
+    return 1;
+  }
+  if (raysIn.empty() && sortRays) {
+    printf("--sort-rays needs --rays\n");
     return 1;
   }
   if (raysIn.empty() && !radianceOut.empty()) {
@@ -289,9 +299,64 @@ int main(int argc, char** argv) {
               sizeof(rtg_ray));
       exit(EXIT_FAILURE);
     }
+    // --sort-rays: one context, the batch's order on the device, both outputs
+    // through the indexed launches (results land at each ray's own place)
+    std::vector<rtg_hit> sortedHits;
+    std::vector<rtg_vec> sortedCols;
+    const bool sorted = sortRays && !rays.empty();
+    if (sorted) {
+      const size_t n = rays.size();
+      rtg_context* ctx = nullptr;
+      check(rtg_context_create((int)device, &ctx), "rtg_context_create");
+      check(rtg_context_set_semantics(ctx, semantics), "rtg_context_set_semantics");
+      check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
+            "rtg_context_set_scene");
+      size_t scratchBytes = 0;
+      check(rtg_ray_order_scratch(n, &scratchBytes), "rtg_ray_order_scratch");
+      rtg_ray* dr = nullptr;
+      unsigned* dOrder = nullptr;
+      void* dScratch = nullptr;
+      rtg_hit* dh = nullptr;
+      rtg_vec* dc = nullptr;
+      if (hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
+          hipMalloc(&dOrder, n * sizeof(unsigned)) != hipSuccess ||
+          hipMalloc(&dScratch, scratchBytes) != hipSuccess ||
+          hipMalloc(&dh, n * sizeof(rtg_hit)) != hipSuccess ||
+          hipMalloc(&dc, n * sizeof(rtg_vec)) != hipSuccess)
+        check(RTG_ERR_NOMEM, "hipMalloc");
+      if (hipMemcpy(dr, rays.data(), n * sizeof(rtg_ray), hipMemcpyHostToDevice) != hipSuccess)
+        check(RTG_ERR_HIP, "upload");
+      check(rtg_ray_order_device(ctx, dr, n, RTG_ORDER_RAYS, dOrder, nullptr, dScratch,
+                                 scratchBytes, nullptr),
+            "rtg_ray_order_device");
+      if (!hitsOut.empty()) {
+        sortedHits.resize(n);
+        check(rtg_intersect_indexed_device(ctx, dr, dOrder, n, dh, nullptr),
+              "rtg_intersect_indexed_device");
+        if (hipMemcpy(sortedHits.data(), dh, n * sizeof(rtg_hit), hipMemcpyDeviceToHost) !=
+            hipSuccess)
+          check(RTG_ERR_HIP, "readback");
+      }
+      if (!radianceOut.empty()) {
+        sortedCols.resize(n);
+        check(rtg_raytrace_indexed_device(ctx, dr, dOrder, n, (int)depth + 1, dc, nullptr),
+              "rtg_raytrace_indexed_device");
+        if (hipMemcpy(sortedCols.data(), dc, n * sizeof(rtg_vec), hipMemcpyDeviceToHost) !=
+            hipSuccess)
+          check(RTG_ERR_HIP, "readback");
+      }
+      (void)hipFree(dr);
+      (void)hipFree(dOrder);
+      (void)hipFree(dScratch);
+      (void)hipFree(dh);
+      (void)hipFree(dc);
+      rtg_context_destroy(ctx);
+      printf("Ordered %zu rays on the device (--sort-rays)\n", n);
+    }
     if (!hitsOut.empty()) {
       std::vector<rtg_hit> hits(rays.size());
-      if (!rays.empty())
+      if (sorted) hits.swap(sortedHits);
+      else if (!rays.empty())
         check(rtg_intersect((int)device, spheres.data(), nSph, rays.data(), rays.size(),
                             hits.data()),
               "rtg_intersect");
@@ -306,7 +371,9 @@ int main(int argc, char** argv) {
     }
     if (!radianceOut.empty()) {
       std::vector<rtg_vec> cols(rays.size());
-      if (!rays.empty() && semantics == RTG_SEMANTICS_CPU) {
+      if (sorted) {
+        cols.swap(sortedCols);
+      } else if (!rays.empty() && semantics == RTG_SEMANTICS_CPU) {
         check(rtg_raytrace((int)device, spheres.data(), nSph, lights.data(), nLgt, rays.data(),
                            rays.size(), (int)depth + 1, cols.data()),
               "rtg_raytrace");

@@ -79,6 +79,8 @@ EXPORTED = [
     "rtg_intersect_device", "rtg_intersect", "rtg_intersect_host",
     "rtg_visible_device", "rtg_visible", "rtg_visible_host",
     "rtg_raytrace_device", "rtg_raytrace", "rtg_raytrace_host",
+    "rtg_ray_order_scratch", "rtg_ray_order_device", "rtg_ray_order_host",
+    "rtg_intersect_indexed_device", "rtg_visible_indexed_device", "rtg_raytrace_indexed_device",
     "rtg_camera_identity", "rtg_camera_look_at", "rtg_camera_sample_count",
     "rtg_camera_rays_host", "rtg_camera_rays_device",
     "rtg_render_camera_device", "rtg_render_camera", "rtg_render_camera_host",
@@ -170,6 +172,12 @@ def lib() -> ctypes.CDLL:
         L.rtg_raytrace_device.argtypes = [vp, vp, sz, i, vp, vp]
         L.rtg_raytrace.argtypes = [i, vp, u, vp, u, vp, sz, i, vp]
         L.rtg_raytrace_host.argtypes = [vp, u, vp, u, vp, sz, i, i, vp, i, i]
+        L.rtg_ray_order_scratch.argtypes = [sz, ctypes.POINTER(sz)]
+        L.rtg_ray_order_device.argtypes = [vp, vp, sz, i, vp, vp, vp, sz, vp]
+        L.rtg_ray_order_host.argtypes = [vp, u, vp, sz, i, vp, vp, i]
+        L.rtg_intersect_indexed_device.argtypes = [vp, vp, vp, sz, vp, vp]
+        L.rtg_visible_indexed_device.argtypes = [vp, vp, vp, sz, vp, vp]
+        L.rtg_raytrace_indexed_device.argtypes = [vp, vp, vp, sz, i, vp, vp]
         L.rtg_camera_identity.argtypes = [vp]
         L.rtg_camera_identity.restype = None
         L.rtg_camera_look_at.argtypes = [vp, vp, vp, vp]
@@ -441,6 +449,39 @@ def raytrace_host(spheres, lights, rays, stack_size: int = 6, semantics: int = 0
     return out
 
 
+# The ray order (include/rtg.h): RTG_ORDER_RAYS / RTG_ORDER_SEGMENTS, and the
+# device sort's geometry: rays per tile (RTG_ORDER_TILE_RAYS) and tiles per
+# scan step (RTG_ORDER_SCAN_TILES).
+ORDER_RAYS, ORDER_SEGMENTS = 0, 1
+ORDER_TILE_RAYS = 1024
+ORDER_SCAN_TILES = 256
+ORDER_ORIGIN_BITS, ORDER_DIR_BITS = 10, 10  # key bits per origin axis / direction axis
+ORDER_KEY_BITS = 3 * ORDER_ORIGIN_BITS + 2 * ORDER_DIR_BITS  # the key's used bits
+
+
+def ray_order_scratch(n: int) -> int:
+    """Bytes of device scratch Context.ray_order needs for n rays (rtg_ray_order_scratch)."""
+    b = ctypes.c_size_t(0)
+    _check(lib().rtg_ray_order_scratch(n, ctypes.byref(b)), "rtg_ray_order_scratch")
+    return b.value
+
+
+def ray_order_host(spheres, rays, kind: int = 0, threads: int = 1, keys: bool = False):
+    """The coherence order of a batch on the host (rtg_ray_order_host; no GPU
+    needed): uint32 order with order[k] = the index of the ray at position k of
+    the batch stably sorted by key.  rays: RAY_DTYPE records, SEGMENT_DTYPE
+    records with kind = ORDER_SEGMENTS, or (N, 6) float32.  keys=True: returns
+    (order, keys), keys[i] the uint64 key of ray i."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    dtype = SEGMENT_DTYPE if kind == ORDER_SEGMENTS else RAY_DTYPE
+    src, n, order, dst = _batch(rays, dtype, np.uint32)
+    k = np.zeros(n, np.uint64)
+    kp = _ptr(k) if keys and n else None
+    _check(lib().rtg_ray_order_host(_ptr(spheres), len(spheres), _ptr(src), n, kind, _ptr(dst),
+                                    kp, threads), "rtg_ray_order_host")
+    return (order, k) if keys else order
+
+
 def _camera(cam) -> np.ndarray:
     """A pose as one CAMERA_DTYPE record (a record, or 12 floats: eye, right, up, back)."""
     a = np.asarray(cam)
@@ -708,28 +749,71 @@ class Context:
                                         ctypes.c_void_p(stream) if stream else None),
                "rtg_gbuffer_device")
 
-    def intersect_device(self, rays_ptr: int, n: int, dst_ptr: int, stream: int = 0):
+    def ray_order(self, rays_ptr: int, n: int, order_ptr: int, scratch_ptr: int,
+                  scratch_bytes: int, kind: int = 0, keys_ptr: int = 0, stream: int = 0):
+        """The coherence order of n rays (kind ORDER_RAYS) or segments
+        (ORDER_SEGMENTS) at rays_ptr (device, 24-byte records) into order_ptr
+        (device, n uint32) and, when keys_ptr is given, their keys (device, n
+        uint64, batch order), asynchronously on `stream` (rtg_ray_order_device).
+        scratch_ptr: ray_order_scratch(n) bytes of device memory, 16-byte
+        aligned.  Pass the order as order= to intersect_device, visible_device
+        or raytrace_device."""
+        _check(lib().rtg_ray_order_device(self._h, ctypes.c_void_p(rays_ptr), n, kind,
+                                          ctypes.c_void_p(order_ptr),
+                                          ctypes.c_void_p(keys_ptr) if keys_ptr else None,
+                                          ctypes.c_void_p(scratch_ptr), scratch_bytes,
+                                          ctypes.c_void_p(stream) if stream else None),
+               "rtg_ray_order_device")
+
+    def intersect_device(self, rays_ptr: int, n: int, dst_ptr: int, stream: int = 0,
+                         order: int = 0):
         """Closest hits of n rays at rays_ptr (device, 24-byte RAY_DTYPE records:
         an (N, 6) float32 tensor) into dst_ptr (device, 32-byte HIT_DTYPE records,
-        16-byte aligned: an (N, 8) int32 tensor), asynchronously on `stream`."""
+        16-byte aligned: an (N, 8) int32 tensor), asynchronously on `stream`.
+        order: a device pointer to n uint32 indices (rtg_intersect_indexed_device:
+        lane k takes ray order[k]; the results stay in the caller's order)."""
+        if order:
+            _check(lib().rtg_intersect_indexed_device(self._h, ctypes.c_void_p(rays_ptr),
+                                                      ctypes.c_void_p(order), n,
+                                                      ctypes.c_void_p(dst_ptr),
+                                                      ctypes.c_void_p(stream) if stream else None),
+                   "rtg_intersect_indexed_device")
+            return
         _check(lib().rtg_intersect_device(self._h, ctypes.c_void_p(rays_ptr), n,
                                           ctypes.c_void_p(dst_ptr),
                                           ctypes.c_void_p(stream) if stream else None),
                "rtg_intersect_device")
 
-    def visible_device(self, segs_ptr: int, n: int, dst_ptr: int, stream: int = 0):
+    def visible_device(self, segs_ptr: int, n: int, dst_ptr: int, stream: int = 0,
+                       order: int = 0):
         """Line of sight of n segments at segs_ptr (device, 24-byte SEGMENT_DTYPE
-        records) into dst_ptr (device, one uint8 per segment: 1 visible)."""
+        records) into dst_ptr (device, one uint8 per segment: 1 visible).
+        order: as intersect_device (rtg_visible_indexed_device)."""
+        if order:
+            _check(lib().rtg_visible_indexed_device(self._h, ctypes.c_void_p(segs_ptr),
+                                                    ctypes.c_void_p(order), n,
+                                                    ctypes.c_void_p(dst_ptr),
+                                                    ctypes.c_void_p(stream) if stream else None),
+                   "rtg_visible_indexed_device")
+            return
         _check(lib().rtg_visible_device(self._h, ctypes.c_void_p(segs_ptr), n,
                                         ctypes.c_void_p(dst_ptr),
                                         ctypes.c_void_p(stream) if stream else None),
                "rtg_visible_device")
 
     def raytrace_device(self, rays_ptr: int, n: int, dst_ptr: int, stack_size: int = 6,
-                        stream: int = 0):
+                        stream: int = 0, order: int = 0):
         """rayTrace's colours of n rays at rays_ptr (device, 24-byte RAY_DTYPE
         records) into dst_ptr (device, an (N, 3) float32 tensor), asynchronously
-        on `stream`, under the context's semantics."""
+        on `stream`, under the context's semantics.  order: as intersect_device
+        (rtg_raytrace_indexed_device)."""
+        if order:
+            _check(lib().rtg_raytrace_indexed_device(self._h, ctypes.c_void_p(rays_ptr),
+                                                     ctypes.c_void_p(order), n, stack_size,
+                                                     ctypes.c_void_p(dst_ptr),
+                                                     ctypes.c_void_p(stream) if stream else None),
+                   "rtg_raytrace_indexed_device")
+            return
         _check(lib().rtg_raytrace_device(self._h, ctypes.c_void_p(rays_ptr), n, stack_size,
                                          ctypes.c_void_p(dst_ptr),
                                          ctypes.c_void_p(stream) if stream else None),

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
+                       [--only-order] [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
 with the scene and the rays resident, on three batches of bench.py's frames:
@@ -38,6 +39,20 @@ render, at aa = 1 and aa = 3, the orbit pose, and the generator.
 --only-camera runs these alone; --mapping NAME records the build's lane-to-pixel
 mapping and --mapping-json FILE puts such a run of a build with another
 mapping next to this one's (how the 8 x 8 tile was chosen over 64 x 1).
+
+The ray order (csrc/rtg_order.hip) gets rows under "order" (order_rows below)
+for the shuffled batches above: C5 intersect, C3 and C5 raytrace.  Each times,
+round by round in one process, rtg_ray_order_device of the shuffled batch, the
+indexed launch with that order, the plain launch of the same shuffled batch
+and the plain launch of the pixel-ordered batch; it records the sum order +
+indexed per round, the digit passes the sort executed and skipped, whether
+the indexed outputs are the plain ones word for word, and, as a yardstick
+outside the library, torch.sort of the same keys (a library radix sort of all
+64 bits with indices).  The speed claim is gated on the two raytrace rows: the
+sum must be below the plain shuffled launch by more than either's min-max
+spread.  --only-order runs these rows alone (--order-label NAME is recorded:
+the key layout or bit counts of the library under RTG_LIB / RTG_ORDER_LAYOUT);
+--order-alt-json FILE puts such runs of other layouts next to this one's.
 GPU only.
 """
 import argparse
@@ -82,8 +97,9 @@ def timed(fn, stream, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def measure(fns, rounds, window_ms=300.0):
-    """Median, min and max ms per launch of each fn, interleaved round by round."""
+def measure(fns, rounds, window_ms=300.0, raw=None):
+    """Median, min and max ms per launch of each fn, interleaved round by round
+    (raw: a list that receives each fn's per-round times)."""
     s = torch.cuda.current_stream()
     reps = []
     for fn in fns:
@@ -95,6 +111,8 @@ def measure(fns, rounds, window_ms=300.0):
     for _ in range(rounds):
         for k, fn in enumerate(fns):
             t[k].append(timed(fn, s, reps[k]))
+    if raw is not None:
+        raw.extend(t)
     return [{"ms_median": round(float(np.median(v)), 5), "ms_min": round(min(v), 5),
              "ms_max": round(max(v), 5), "launches_per_round": r} for v, r in zip(t, reps)]
 
@@ -163,6 +181,71 @@ def camera_rows(args, W, H, rays, col, fb, stream):
     return out, ok
 
 
+def order_rows(args, n, rays, shuffled, stream):
+    """The ray order (csrc/rtg_order.hip) on the shuffled 8.3 M primary rays:
+    order, indexed launch, plain shuffled launch and pixel-ordered launch, round
+    by round; see the module text.  Returns (rows, ok): ok is the gate of the
+    two raytrace rows and the word-for-word equality of all three."""
+    nbytes = R.ray_order_scratch(n)
+    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device="cuda")
+    order = torch.empty((n,), dtype=torch.int32, device="cuda")
+    keys = torch.empty((n,), dtype=torch.int64, device="cuda")
+    out, ok = {"label": args.order_label, "scratch_bytes": nbytes}, True
+    for row, name, call in (("c5_intersect", "c5", "intersect"), ("c3_raytrace", "c3", "raytrace"),
+                            ("c5_raytrace", "c5", "raytrace")):
+        S = CONFIGS[name][4] + 1
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        if call == "intersect":
+            shape, dt = (n, 8), torch.int32
+            run = lambda src, dst, o: ctx.intersect_device(src.data_ptr(), n, dst.data_ptr(),  # noqa: E731
+                                                           stream, order=o)
+        else:
+            shape, dt = (n, 3), torch.float32
+            run = lambda src, dst, o: ctx.raytrace_device(src.data_ptr(), n, dst.data_ptr(), S,  # noqa: E731
+                                                          stream, order=o)
+        d_idx = torch.empty(shape, dtype=dt, device="cuda")
+        d_plain = torch.empty(shape, dtype=dt, device="cuda")
+        d_pix = torch.empty(shape, dtype=dt, device="cuda")
+        ctx.ray_order(shuffled.data_ptr(), n, order.data_ptr(), scratch.data_ptr(), nbytes,
+                      keys_ptr=keys.data_ptr(), stream=stream)  # once with the keys, for the counts
+        sort = lambda: ctx.ray_order(shuffled.data_ptr(), n, order.data_ptr(), scratch.data_ptr(),  # noqa: E731
+                                     nbytes, stream=stream)
+        raw = []
+        so, ix, pl, px, ts = measure(
+            [sort, lambda: run(shuffled, d_idx, order.data_ptr()),
+             lambda: run(shuffled, d_plain, 0), lambda: run(rays, d_pix, 0),
+             lambda: torch.sort(keys, stable=True)], args.rounds, raw=raw)
+        ctx.close()
+        equal = bool((d_idx.view(torch.int32) == d_plain.view(torch.int32)).all())
+        k = keys.cpu().numpy().view(np.uint64)
+        ran = [bool(np.ptp((k >> np.uint64(8 * p)) & np.uint64(0xFF)) > 0)
+               for p in range(-(-R.ORDER_KEY_BITS // 8))]
+        is_sorted = bool((np.diff(k[order.cpu().numpy().view(np.uint32)].astype(np.int64)) >= 0).all())
+        both = [a + b for a, b in zip(raw[0], raw[1])]
+        spread = max(max(both) - min(both), pl["ms_max"] - pl["ms_min"])
+        gain = pl["ms_median"] - float(np.median(both))
+        faster = bool(gain > spread)
+        out[row] = {
+            "stack_size": S if call == "raytrace" else None,
+            "order": so, "indexed": ix, "plain_shuffled": pl, "pixel_order": px,
+            "order_plus_indexed": {"ms_median": round(float(np.median(both)), 5),
+                                   "ms_min": round(min(both), 5), "ms_max": round(max(both), 5)},
+            "plain_shuffled_over_order_plus_indexed":
+                round(pl["ms_median"] / float(np.median(both)), 3),
+            "indexed_over_pixel_order": round(ix["ms_median"] / px["ms_median"], 3),
+            "faster_by_more_than_the_spread": faster,
+            "gated": call == "raytrace",
+            "digit_passes_executed": int(sum(ran)), "digit_passes_skipped": int(len(ran) - sum(ran)),
+            "distinct_keys": int(len(np.unique(k))),
+            "indexed_equals_plain_shuffled": equal, "keys_sorted_by_order": is_sorted,
+            "torch_sort_64bit_pairs": ts}
+        ok = ok and equal and is_sorted and (faster or call != "raytrace")
+        del d_idx, d_plain, d_pix
+    return out, ok
+
+
 def finish(args, res, ok):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -179,6 +262,11 @@ def main():
     ap.add_argument("--parent-json", default="")
     ap.add_argument("--commit", default="", help="recorded as the commit the numbers are of")
     ap.add_argument("--only-camera", action="store_true", help="the posed camera's rows alone")
+    ap.add_argument("--only-order", action="store_true", help="the ray order's rows alone")
+    ap.add_argument("--order-label", default="origin-major b=10 c=10",
+                    help="recorded as the library's key layout and bit counts")
+    ap.add_argument("--order-alt-json", default=[], action="append",
+                    help="an --only-order file of another key layout, for the side-by-side")
     ap.add_argument("--mapping", default="8x8", help="recorded as the library's lane-to-pixel mapping")
     ap.add_argument("--mapping-json", default="",
                     help="a --only-camera file of a build with another mapping, for the side-by-side")
@@ -198,6 +286,11 @@ def main():
     stream = torch.cuda.current_stream().cuda_stream
     res = {"W": W, "H": H, "rays": n, "device": R.device_info(0), "rounds": args.rounds,
            "commit": args.commit, "batches": {}}
+
+    if args.only_order:
+        del hits, hits2, gb
+        res["order"], ok = order_rows(args, n, rays, shuffled, stream)
+        finish(args, res, ok)
 
     if args.only_camera:
         del hits, hits2, gb, shuffled
@@ -269,9 +362,15 @@ def main():
             "shuffled_over_ordered": round(s["ms_median"] / o["ms_median"], 3),
             "ordered_colours_equal_render": frame,
             "shuffled_colours_are_ordered_permuted": permuted}
-    del col2, shuffled
+    del col2
+    res["order"], order_ok = order_rows(args, n, rays, shuffled, stream)
+    for path in args.order_alt_json:
+        with open(path) as f:
+            other = json.load(f)["order"]
+        res["order"].setdefault("alternatives", {})[other["label"]] = other
+    del shuffled
     res["camera"], cam_ok = camera_rows(args, W, H, rays, col, fb, stream)
-    ok = ok and cam_ok
+    ok = ok and cam_ok and order_ok
     if args.mapping_json:
         with open(args.mapping_json) as f:
             other = json.load(f)["camera"]
