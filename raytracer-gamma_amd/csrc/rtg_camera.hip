@@ -11,17 +11,19 @@
 //
 // The fused render (camera_kernel, rtg_camera_kernels.h, per S in
 // rtg_trace_s.hip) forms each sample ray in registers, runs rayTrace on it as
-// rtg_raytrace_device does (trace_sample with the query path RayPath,
-// rtg_rays.h: exact for any origin at every level of the tree; none of the
-// renders' table paths, for the reasons at the head of rtg_raytrace.hip) and
-// folds the pixel as shade_pixel does.  The posed frame is therefore, bit for
+// rtg_raytrace_device does (trace_ray, rtg_rays.h: exact for any origin at
+// every level of the tree; none of the renders' table paths, for the reasons
+// there and at the head of rtg_raytrace.hip) and folds the pixel as
+// shade_pixel does.  The posed frame is therefore, bit for
 // bit, the host fold of rtg_raytrace_host(walk 0) over rtg_camera_rays_host's
 // rays: no ray buffer, no colour buffer and no fold on the caller's side.
 //
 // This file holds the pose helpers, the generator (kernel and host form), the
-// launcher of the fused kernel, the argument checks and the host forms of the
-// render (walk 0: trace_sample<S, 0> with plain loops, the yardstick; walk 1:
-// the kernel's own path over the packed tables, one pixel per "wave").
+// launcher of the fused kernel (picked from stack_kernels, rtg_trace_kernels.h),
+// the pose's own argument checks (the rest are rtg_entry.h's) and the host
+// forms of the render (walk 0: trace_ray_plain, the yardstick; walk 1:
+// trace_ray, the kernel's own path over the packed tables, one pixel per
+// "wave"; host_trace_fn, rtg_host_scene.h, picks the instantiation).
 //
 // FP contract: the Makefile's FPFLAGS, as every kernel.
 #include <hip/hip_runtime.h>
@@ -42,17 +44,6 @@ static_assert(sizeof(rtg_camera) == 48 && sizeof(rtg::CamPose) == 48, "the pose 
 static_assert(sizeof(rtg_ray) == 24 && sizeof(rtg_vec) == 12, "24 B per ray, 12 B per pixel");
 
 namespace rtg {
-
-static CameraFn pick_camera(int S, bool bvh, bool cl) {
-  switch (S) {
-#define RTG_CASE(k) case k: return camera_fn_s##k(bvh, cl);
-    RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
-    RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
-    RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
-#undef RTG_CASE
-    default: return nullptr;
-  }
-}
 
 // ---- the generator ----
 
@@ -91,41 +82,18 @@ static void camera_host_range(const PackedScene& ps, const RayBox& box, const Ca
       for (int j = 0; j < cam.nAA; ++j) {
         const V3 d = camera_dir(cam, pose, x, y, i, j);
         V3 c;
-        if constexpr (kWalk)
-          c = trace_sample<S, 2, kCL, RayPath<kBvh>>(sc, d, sc.frames(), false, ~0ull, pose.eye,
-                                                     RayPath<kBvh>{box});
-        else
-          c = trace_sample<S, 0, kCL>(sc, d, sc.frames(), false, ~0ull, pose.eye);
+        if constexpr (kWalk) c = trace_ray<S, kCL, kBvh>(sc, box, pose.eye, d);
+        else c = trace_ray_plain<S, kCL>(sc, pose.eye, d);
         c = vsmul(cam.inv, c);
         pix = vadd(pix, c);
       }
     }
-    const unsigned w[3] = {nan_bits(pix.x), nan_bits(pix.y), nan_bits(pix.z)};
-    memcpy(dst + k, w, sizeof w);
+    store_colour(dst + k, pix);
   }
 }
 
 typedef void (*CamHostFn)(const PackedScene&, const RayBox&, const Camera&, const CamPose&,
                           unsigned, size_t, size_t, rtg_vec*);
-template <int S>
-static CamHostFn cam_host_fn(bool cl, bool walk, bool bvh) {
-  if (!walk)
-    return cl ? camera_host_range<S, true, false, false>
-              : camera_host_range<S, false, false, false>;
-  if (bvh)
-    return cl ? camera_host_range<S, true, true, true> : camera_host_range<S, false, true, true>;
-  return cl ? camera_host_range<S, true, true, false> : camera_host_range<S, false, true, false>;
-}
-static CamHostFn pick_cam_host(int S, bool cl, bool walk, bool bvh) {
-  switch (S) {
-#define RTG_CASE(k) case k: return cam_host_fn<k>(cl, walk, bvh);
-    RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
-    RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
-    RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
-#undef RTG_CASE
-    default: return nullptr;
-  }
-}
 
 static V3 vcross(V3 a, V3 b) {
   return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
@@ -144,14 +112,6 @@ static int check_frame(const char* what, const rtg_camera* cam, const void* dst,
     return RTG_ERR_INVALID;
   }
   return make_camera(W, H, zoom, aa, out);
-}
-
-static int check_stack(int stackSize) {
-  if (stackSize < 1 || stackSize > RTG_MAX_STACK) {
-    rtg_set_error("render_camera: stackSize %d outside [1, %d]", stackSize, RTG_MAX_STACK);
-    return RTG_ERR_INVALID;
-  }
-  return RTG_OK;
 }
 
 // Workgroups of the fused kernel for a W x H frame; 0 when more than 2^31-1.
@@ -232,18 +192,16 @@ int rtg_camera_rays_device(rtg_context* ctx, const rtg_camera* cam, unsigned wid
     return RTG_ERR_INVALID;
   }
   Camera c;
-  const int rc = check_frame("camera_rays", cam, raysDevice, width, height, zoom, aliasFactor, &c);
+  int rc = check_frame("camera_rays", cam, raysDevice, width, height, zoom, aliasFactor, &c);
   if (rc) return rc;
   const size_t n = (size_t)width * height * c.nAA * c.nAA;
   if (n == 0) return RTG_OK;
-  const size_t blocks = (n + 63) / 64;  // one-wave workgroups
-  if (blocks > 0x7FFFFFFFu) {
-    rtg_set_error("camera_rays: frame too large (%zu workgroups)", blocks);
-    return RTG_ERR_INVALID;
-  }
+  unsigned blocks;
+  rc = ray_blocks("camera_rays", "frame", n, &blocks);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream,
-                     c, cam_pose(*cam), width, n, raysDevice);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, c,
+                     cam_pose(*cam), width, n, raysDevice);
   HIP_TRY(hipGetLastError());
   return RTG_OK;
 }
@@ -255,29 +213,21 @@ int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg
   rtg_clear_error();
   Camera c;
   int rc = check_frame("render_camera", cam, dstHost, width, height, zoom, aliasFactor, &c);
-  if (!rc) rc = check_stack(stackSize);
+  if (!rc) rc = check_stack("render_camera", stackSize);
+  if (!rc) rc = check_scene_arrays("render_camera", spheres, sphNum, lights, lgtNum);
+  if (!rc) rc = check_semantics("render_camera", semantics);
+  if (!rc) rc = check_walk("render_camera", walk);
+  if (!rc) rc = check_sphere_count("render_camera", sphNum);
   if (rc) return rc;
-  if ((sphNum && !spheres) || (lgtNum && !lights)) {
-    rtg_set_error("render_camera: null scene array");
-    return RTG_ERR_INVALID;
-  }
-  if (semantics != RTG_SEMANTICS_CPU && semantics != RTG_SEMANTICS_OPENCL) {
-    rtg_set_error("render_camera: semantics %d (0: CPU, 1: OpenCL)", semantics);
-    return RTG_ERR_INVALID;
-  }
-  if (walk != 0 && walk != 1) {
-    rtg_set_error("render_camera: walk %d (0: plain loops, 1: the kernel's query path)", walk);
-    return RTG_ERR_INVALID;
-  }
-  if (sphNum >= RTG_MAX_SPHERES) {
-    rtg_set_error("render_camera: %u spheres (at most %u)", sphNum, RTG_MAX_SPHERES - 1);
-    return RTG_ERR_INVALID;
-  }
   PackedScene ps;
   pack_scene(spheres, sphNum, lights, lgtNum, &ps);  // as rtg_context_set_scene
   const bool bvh = walk == 1 && !ps.bvhNodes.empty();
   const RayBox box = bvh ? ray_box(ps.originBox) : RayBox{};
-  const CamHostFn fn = pick_cam_host(stackSize, semantics == RTG_SEMANTICS_OPENCL, walk == 1, bvh);
+  const CamHostFn fn = host_trace_fn(
+      stackSize, semantics == RTG_SEMANTICS_OPENCL, walk == 1, bvh,
+      [](auto s, auto cl, auto wk, auto bv) -> CamHostFn {
+        return camera_host_range<s.value, cl.value, wk.value, bv.value>;
+      });
   const CamPose pose = cam_pose(*cam);
   host_bands((size_t)width * height, nthreads,
              [&](size_t k0, size_t k1) { fn(ps, box, c, pose, width, k0, k1, dstHost); });
@@ -298,7 +248,7 @@ int rtg_render_camera_device(rtg_context* ctx, const rtg_camera* cam, unsigned w
   }
   Camera c;
   int rc = check_frame("render_camera", cam, dstDevice, width, height, zoom, aliasFactor, &c);
-  if (!rc) rc = check_stack(stackSize);
+  if (!rc) rc = check_stack("render_camera", stackSize);
   if (rc) return rc;
   unsigned tilesX = 0;
   const size_t blocks = camera_blocks(width, height, &tilesX);
@@ -307,7 +257,8 @@ int rtg_render_camera_device(rtg_context* ctx, const rtg_camera* cam, unsigned w
     return RTG_ERR_INVALID;
   }
   const bool bvh = a.bvhNodes != nullptr;
-  const CameraFn fn = pick_camera(stackSize, bvh, semantics == RTG_SEMANTICS_OPENCL);
+  const StackKernels* sk = stack_kernels(stackSize);
+  const CameraFn fn = sk ? sk->camera(bvh, semantics == RTG_SEMANTICS_OPENCL) : nullptr;
   if (!fn) {  // a missing kernel is an error, never another path
     rtg_set_error("render_camera: no kernel for stackSize %d", stackSize);
     return RTG_ERR_INVALID;
@@ -328,12 +279,9 @@ int rtg_render_camera(int device, const rtg_sphere* spheres, unsigned sphNum,
   rtg_clear_error();
   Camera c;
   int rc = check_frame("render_camera", cam, dstHost, width, height, zoom, aliasFactor, &c);
-  if (!rc) rc = check_stack(stackSize);
+  if (!rc) rc = check_stack("render_camera", stackSize);
+  if (!rc) rc = check_scene_arrays("render_camera", spheres, sphNum, lights, lgtNum);
   if (rc) return rc;
-  if ((sphNum && !spheres) || (lgtNum && !lights)) {
-    rtg_set_error("render_camera: null scene array");
-    return RTG_ERR_INVALID;
-  }
   unsigned tilesX = 0;
   if (!camera_blocks(width, height, &tilesX)) {
     rtg_set_error("render_camera: frame too large (more than 2^31-1 workgroups)");

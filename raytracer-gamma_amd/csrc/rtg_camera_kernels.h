@@ -19,9 +19,6 @@ namespace rtg {
 constexpr unsigned kCamTileW = 8, kCamTileH = 8;
 static_assert(kCamTileW * kCamTileH == 64, "one lane per pixel of the tile");
 
-typedef void (*CameraFn)(const SceneTables, const RayBox, const Camera, const CamPose, unsigned,
-                         unsigned, unsigned, rtg_vec*);
-
 // One lane per pixel, one-wave workgroups, workgroup b the tile (b % tilesX,
 // b / tilesX); the LDS image and the scene binding are raytrace_kernel's.  A
 // lane whose pixel lies outside the frame leaves before the trace (the
@@ -35,11 +32,8 @@ __global__ __launch_bounds__(64) void camera_kernel(const SceneTables a, const R
                                                     unsigned W, unsigned H, unsigned tilesX,
                                                     rtg_vec* __restrict__ dst) {
   extern __shared__ float4 lds4[];
-  constexpr int NFL = frame_lds_levels(S, kBvh);
-  DevScene<false, 64, kBvh, 0> sc;
-  sc.lfr = reinterpret_cast<FrameC*>(lds4) + threadIdx.x;
-  sc.nfl = NFL;
-  bind_scene(sc, a, reinterpret_cast<int*>(lds4 + NFL * 64));  // the stack: kBvh only
+  RayScene<kBvh> sc;
+  bind_raytrace_scene<S>(sc, a, lds4);
   const size_t px = (size_t)(blockIdx.x % tilesX) * kCamTileW + threadIdx.x % kCamTileW;
   const size_t py = (size_t)(blockIdx.x / tilesX) * kCamTileH + threadIdx.x / kCamTileW;
   if (px >= W || py >= H) return;
@@ -48,16 +42,12 @@ __global__ __launch_bounds__(64) void camera_kernel(const SceneTables a, const R
   for (int i = 0; i < cam.nAA; ++i) {
     for (int j = 0; j < cam.nAA; ++j) {
       const V3 d = camera_dir(cam, pose, x, y, i, j);
-      V3 c = trace_sample<S, 2, kCL, RayPath<kBvh>>(sc, d, sc.frames(), false, ~0ull, pose.eye,
-                                                    RayPath<kBvh>{box});
+      V3 c = trace_ray<S, kCL, kBvh>(sc, box, pose.eye, d);
       c = vsmul(cam.inv, c);
       pix = vadd(pix, c);
     }
   }
-  float* w = reinterpret_cast<float*>(dst + (py * W + px));  // px < W, py < H: 12 B of the frame
-  w[0] = canon_nan(pix.x);
-  w[1] = canon_nan(pix.y);
-  w[2] = canon_nan(pix.z);
+  store_colour_dev(dst + (py * W + px), pix);  // px < W, py < H: 12 B of the frame
 }
 
 // bvh: the scene has a BVH (SceneTables::bvhNodes); cl: RTG_SEMANTICS_OPENCL.
@@ -66,12 +56,5 @@ static CameraFn camera_fn(bool bvh, bool cl) {
   if (bvh) return cl ? camera_kernel<S, true, true> : camera_kernel<S, true, false>;
   return cl ? camera_kernel<S, false, true> : camera_kernel<S, false, false>;
 }
-
-// One per stack size, defined in rtg_trace_s<S>.hip.
-#define RTG_DECL(k) CameraFn camera_fn_s##k(bool bvh, bool cl);
-RTG_DECL(1) RTG_DECL(2) RTG_DECL(3) RTG_DECL(4) RTG_DECL(5) RTG_DECL(6) RTG_DECL(7)
-RTG_DECL(8) RTG_DECL(9) RTG_DECL(10) RTG_DECL(11) RTG_DECL(12) RTG_DECL(13)
-RTG_DECL(14) RTG_DECL(15) RTG_DECL(16)
-#undef RTG_DECL
 
 }  // namespace rtg

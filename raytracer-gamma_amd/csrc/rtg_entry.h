@@ -1,8 +1,9 @@
 // rtg_entry.h — what the C ABI entry points of librtg.so share (rtg_kernel.hip,
 // rtg_gbuffer.hip, rtg_rays.hip, rtg_raytrace.hip, rtg_order.hip, rtg_camera.hip): the HIP error
-// return, the records' NaN form
-// and 32-byte store, the host forms' plain scene and thread bands, and the
-// one-shot body.  HIP translation units only.
+// return, the records' NaN form, the colour and 32-byte record stores, the
+// host forms' plain scene and thread bands, the argument checks that differ
+// between entry points only in their prefix, and the one-shot body.  HIP
+// translation units only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,6 +38,12 @@ RTG_HD unsigned nan_bits(float v) {
   return (v != v) ? 0xFFC00000u : u;
 }
 
+// A colour of the host forms (rtg_raytrace_host, rtg_render_camera_host).
+inline void store_colour(rtg_vec* dst, V3 c) {
+  const unsigned w[3] = {nan_bits(c.x), nan_bits(c.y), nan_bits(c.z)};
+  memcpy(dst, w, sizeof w);
+}
+
 // A 32-byte record (rtg_gbuf_px, rtg_hit) as two 16-byte stores; `rec` is
 // 16-byte aligned (the device entry points check their destination).
 __device__ __forceinline__ void store_record(void* rec, const unsigned* w) {
@@ -67,6 +74,57 @@ inline void host_bands(size_t n, int nthreads, const std::function<void(size_t, 
   std::vector<std::thread> pool;
   for (size_t k = 0; k < nt; ++k) pool.emplace_back(fn, n * k / nt, n * (k + 1) / nt);
   for (auto& th : pool) th.join();
+}
+
+// ---- argument checks ----
+// Each sets the entry point's message, "<what>: ...", and returns
+// RTG_ERR_INVALID, or returns RTG_OK.  An entry point calls them in the order
+// it reports in: the first bad argument is the one named.
+
+inline int check_stack(const char* what, int stackSize) {
+  if (stackSize >= 1 && stackSize <= RTG_MAX_STACK) return RTG_OK;
+  rtg_set_error("%s: stackSize %d outside [1, %d]", what, stackSize, RTG_MAX_STACK);
+  return RTG_ERR_INVALID;
+}
+
+inline int check_semantics(const char* what, int semantics) {
+  if (semantics == RTG_SEMANTICS_CPU || semantics == RTG_SEMANTICS_OPENCL) return RTG_OK;
+  rtg_set_error("%s: semantics %d (0: CPU, 1: OpenCL)", what, semantics);
+  return RTG_ERR_INVALID;
+}
+
+// The host forms' walk: 0 the plain loops, 1 the kernel's own path.
+inline int check_walk(const char* what, int walk) {
+  if (walk == 0 || walk == 1) return RTG_OK;
+  rtg_set_error("%s: walk %d (0: plain loops, 1: the kernel's query path)", what, walk);
+  return RTG_ERR_INVALID;
+}
+
+// What pack_scene takes (rtg_context_set_scene has its own message).
+inline int check_sphere_count(const char* what, unsigned sphNum) {
+  if (sphNum < RTG_MAX_SPHERES) return RTG_OK;
+  rtg_set_error("%s: %u spheres (at most %u)", what, sphNum, RTG_MAX_SPHERES - 1);
+  return RTG_ERR_INVALID;
+}
+
+// The caller's scene arrays; an entry point without lights passes none.
+inline int check_scene_arrays(const char* what, const rtg_sphere* spheres, unsigned sphNum,
+                              const rtg_light* lights = nullptr, unsigned lgtNum = 0) {
+  if (!(sphNum && !spheres) && !(lgtNum && !lights)) return RTG_OK;
+  rtg_set_error("%s: null scene array", what);
+  return RTG_ERR_INVALID;
+}
+
+// The grid of n > 0 lanes in one-wave workgroups; `noun`: what the caller
+// calls the n ("batch", "frame").
+inline int ray_blocks(const char* what, const char* noun, size_t n, unsigned* blocks) {
+  const size_t b = (n + 63) / 64;
+  if (b > 0x7FFFFFFFu) {
+    rtg_set_error("%s: %s too large (%zu workgroups)", what, noun, b);
+    return RTG_ERR_INVALID;
+  }
+  *blocks = (unsigned)b;
+  return RTG_OK;
 }
 
 // One-shot body (rtg_kernel.hip): a context on `device` with the scene,

@@ -265,11 +265,8 @@ static int check_gbuffer_args(const rtg_sphere* spheres, unsigned sphNum, unsign
     rtg_set_error("gbuffer: null destination");
     return RTG_ERR_INVALID;
   }
-  if (sphNum && !spheres) {
-    rtg_set_error("gbuffer: null scene array");
-    return RTG_ERR_INVALID;
-  }
-  return make_camera(width, height, zoom, aliasFactor, cam);
+  const int rc = check_scene_arrays("gbuffer", spheres, sphNum);
+  return rc ? rc : make_camera(width, height, zoom, aliasFactor, cam);
 }
 
 extern "C" {
@@ -305,7 +302,7 @@ int rtg_gbuffer_device(rtg_context* ctx, unsigned width, unsigned height, float 
                             : "gbuffer: null destination");
     return RTG_ERR_INVALID;
   }
-  const int rc = make_camera(width, height, zoom, aliasFactor, &a.cam);
+  int rc = make_camera(width, height, zoom, aliasFactor, &a.cam);
   if (rc) return rc;
   if (rowBlock == 0 || nShards == 0 || shard >= nShards) {
     rtg_set_error("gbuffer: bad sharding %u/%u block %u", shard, nShards, rowBlock);
@@ -329,18 +326,15 @@ int rtg_gbuffer_device(rtg_context* ctx, unsigned width, unsigned height, float 
   // one-wave workgroups: 64 pixel groups each (sample kernel), or 64 pixels
   const unsigned ppw = sampleKernel ? 64u / (unsigned)(a.cam.nAA * a.cam.nAA) : 1u;
   const size_t groups = (total + ppw - 1) / ppw;
-  const size_t blocks = (groups + 63) / 64;
-  if (blocks > 0x7FFFFFFFu) {
-    rtg_set_error("gbuffer: frame too large (%zu workgroups)", blocks);
-    return RTG_ERR_INVALID;
-  }
+  unsigned blocks;
+  rc = ray_blocks("gbuffer", "frame", groups, &blocks);
+  if (rc) return rc;
   const bool bvh = a.scene.bvhNodes != nullptr;
   void (*fn)(const KernelArgs, size_t, rtg_gbuf_px*) =
       sampleKernel ? (bvh ? gbuffer_samples_kernel<true> : gbuffer_samples_kernel<false>)
                    : (bvh ? gbuffer_pixels_kernel<true> : gbuffer_pixels_kernel<false>);
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, a, groups,
-                     dstDevice);
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), 0, (hipStream_t)stream, a, groups, dstDevice);
   HIP_TRY(hipGetLastError());
   return RTG_OK;
 }

@@ -2,15 +2,21 @@
 // a one-lane Scene of rtg_trace.h's functions on the host: every accessor the
 // device scene (DevScene, rtg_trace_kernels.h) has, a "wave" of one ray, the
 // frame colours in a member array.  The host forms of the batch ray tracer
-// (rtg_raytrace_host) run trace_sample over it.  kBvh: as DevScene's.
+// and the posed camera run trace_sample over it (rtg_raytrace_host,
+// rtg_render_camera_host: with_stack and host_trace_fn below pick their
+// instantiation), the walk-1 host queries ray_closest / ray_blocked
+// (rtg_intersect_host, rtg_visible_host).  kBvh: as DevScene's.
 #pragma once
 
 #include <stdint.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "rtg.h"
 #include "rtg_scene_pack.h"
 #include "rtg_trace.h"
+#include "rtg_trace_kernels.h"
 
 namespace rtg {
 
@@ -196,5 +202,35 @@ struct HostScene {
     col = v3(p[3], p[4], p[5]);
   }
 };
+
+// A run-time stack capacity as a compile-time one: f(integral_constant<int, S>)
+// for S in 1..RTG_MAX_STACK, a value-initialised result (a null function
+// pointer) outside it.
+template <class F>
+auto with_stack(int S, F&& f) -> decltype(f(std::integral_constant<int, 1>{})) {
+  switch (S) {
+#define RTG_X(k) case k: return f(std::integral_constant<int, k>{});
+    RTG_FOR_EACH_S(RTG_X)
+#undef RTG_X
+    default: return {};
+  }
+}
+
+// The instantiations a host form has per S, THE ladder: {cl} x {walk 0, walk 1
+// flat, walk 1 BVH} (walk 0 has no BVH).  f(S, cl, walk, bvh) gets them as
+// integral constants and returns the host form's range function.
+template <class F>
+auto host_trace_fn(int S, bool cl, bool walk, bool bvh, F&& f) {
+  using std::false_type;
+  using std::true_type;
+  return with_stack(S, [&](auto s) {
+    if (!walk) return cl ? f(s, true_type{}, false_type{}, false_type{})
+                         : f(s, false_type{}, false_type{}, false_type{});
+    if (bvh) return cl ? f(s, true_type{}, true_type{}, true_type{})
+                       : f(s, false_type{}, true_type{}, true_type{});
+    return cl ? f(s, true_type{}, true_type{}, false_type{})
+              : f(s, false_type{}, true_type{}, false_type{});
+  });
+}
 
 }  // namespace rtg

@@ -248,13 +248,11 @@ __global__ __launch_bounds__(256) void cull_groups_kernel(const KernelArgs a, si
   }
 }
 
-static TraceFn pick_trace(int S, int variant, bool bvh, int list) {
+const StackKernels* stack_kernels(int S) {
   switch (S) {
-#define RTG_CASE(k) case k: return trace_fn_s##k(variant, bvh, list);
-    RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
-    RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
-    RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
-#undef RTG_CASE
+#define RTG_X(k) case k: return stack_kernels_s##k();
+    RTG_FOR_EACH_S(RTG_X)
+#undef RTG_X
     default: return nullptr;
   }
 }
@@ -1012,7 +1010,8 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
   // the compacted default kernel of a scene with shadow/overlap and cone masks
   // takes them as compile-time facts (kMasks)
   const int listKind = !listed ? 0 : (ctx->scene.smask && ctx->scene.cone) ? 2 : 1;
-  TraceFn fn = pick_trace(stackSize, variant, ctx->scene.bvhNodes != nullptr, listKind);
+  const StackKernels* sk = stack_kernels(stackSize);
+  TraceFn fn = sk ? sk->trace(variant, ctx->scene.bvhNodes != nullptr, listKind) : nullptr;
   if (!fn) {
     rtg_set_error("no kernel for stackSize %d (valid: 1..%d), variant %d", stackSize,
                   RTG_MAX_STACK, variant);

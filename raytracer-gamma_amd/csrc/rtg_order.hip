@@ -381,11 +381,8 @@ int rtg_ray_order_host(const rtg_sphere* spheres, unsigned sphNum, const void* r
     rtg_set_error("ray_order: null %s buffer", rays ? "order" : "ray");
     return RTG_ERR_INVALID;
   }
-  if (sphNum && !spheres) {
-    rtg_set_error("ray_order: null scene array");
-    return RTG_ERR_INVALID;
-  }
-  int rc = check_kind(kind);
+  int rc = check_scene_arrays("ray_order", spheres, sphNum);
+  if (!rc) rc = check_kind(kind);
   if (!rc) rc = check_count(n);
   if (rc) return rc;
   if (n == 0) return RTG_OK;

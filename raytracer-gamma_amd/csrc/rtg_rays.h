@@ -2,8 +2,9 @@
 // tracer (rtg_raytrace.hip, the per-S raytrace kernels) share with each other
 // and with the context (rtg_kernel.hip): the BVH's origin box as a kernel
 // argument of the ray kernels alone (KernelArgs and the trace kernels do not
-// know it), and the two queries that are exact for any origin (the argument is
-// at the head of rtg_rays.hip).
+// know it), the two queries that are exact for any origin (the argument is
+// at the head of rtg_rays.hip), and the one call that runs rayTrace over them
+// for a caller's own ray (trace_ray, with its plain-loop twin).
 #pragma once
 
 #include <math.h>
@@ -37,6 +38,11 @@ inline RayBox ray_box(const double ob[7]) {
   b.omax = down(ob[6]);
   return b;
 }
+
+// The device scene of the ray kernels (the queries', the batch ray tracer's,
+// the posed camera's): one-wave workgroups over the context's tables.
+template <bool kBvh>
+using RayScene = DevScene<false, 64, kBvh, 0>;
 
 // The extra half-width every BVH box gets for a ray from o (rtg_rays.hip's
 // header); `odd`: the origin is outside the slab arithmetic's range.
@@ -113,5 +119,30 @@ struct RayPath {
     return ray_blocked<kBvh>(sc, box, o, d, gap, true);
   }
 };
+
+// rayTrace of a caller's own ray (o, d): THE call of the batch ray tracer and
+// the posed camera, kernels and walk-1 host forms alike.  Its constants are
+// what makes such a ray exact, whatever its origin and direction:
+//  * Q == 2 and RayPath: the shading path that asks no table keyed to the
+//    renderer's own rays (guardOK stays false, so no cone, shadow or overlap
+//    mask and no sphere list is read), every query ray_closest / ray_blocked
+//    with the delta of its own origin (rtg_raytrace.hip's header has the table
+//    of shortcuts this leaves out);
+//  * usePrim false, primSel ~0: no primary-ray mask, which holds only for a
+//    camera at 0 inside the wave's direction bundle.
+// Forced inline, so each caller keeps the code it had with the call written out.
+template <int S, bool kCL, bool kBvh, class Scene>
+RTG_HD V3 trace_ray(const Scene& sc, const RayBox& box, V3 o, V3 d) {
+  return trace_sample<S, 2, kCL, RayPath<kBvh>>(sc, d, sc.frames(), false, ~0ull, o,
+                                                RayPath<kBvh>{box});
+}
+
+// Its plain-loop twin, the yardstick of the host forms' walk 0: Q == 0, every
+// query a loop over every sphere (closest_hit, blocked, the flat
+// primary_container), no table, no BVH.
+template <int S, bool kCL, class Scene>
+RTG_HD V3 trace_ray_plain(const Scene& sc, V3 o, V3 d) {
+  return trace_sample<S, 0, kCL>(sc, d, sc.frames(), false, ~0ull, o);
+}
 
 }  // namespace rtg

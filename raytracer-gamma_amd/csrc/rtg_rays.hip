@@ -107,8 +107,10 @@
 //
 // rtg_intersect_host / rtg_visible_host: walk 0 = plain loops (closest_hit /
 // blocked over the caller's array), the yardstick; walk 1 = the functions the
-// kernels call (ray_closest / ray_blocked) over the packed scene tables,
-// one ray per "wave".
+// kernels call (ray_closest / ray_blocked) over the packed scene tables
+// (HostScene, rtg_host_scene.h: the scene of every walk-1 host form), one ray
+// per "wave".  The argument checks shared with the other entry points, and
+// the batch grid (ray_blocks), are rtg_entry.h's.
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
@@ -117,6 +119,7 @@
 
 #include "rtg.h"
 #include "rtg_entry.h"
+#include "rtg_host_scene.h"
 #include "rtg_trace_kernels.h"
 #include "rtg_rays.h"
 #include "rtg_scene_pack.h"
@@ -155,33 +158,8 @@ RTG_HD V3 segment_ray(V3 a, V3 b, float& gap) {
 
 // ---- host forms ----
 
-// The packed tables (pack_scene) as a one-lane Scene of the kernels' queries.
-struct PackedRayScene {
-  const float* geom;
-  const float* bvhNodes;
-  unsigned n, n4;
-  void count(int, long) const {}
-  bool all(bool b) const { return b; }
-  bool any(bool b) const { return b; }
-  V3 first_lane(V3 v) const { return v; }
-  int* bvh_stack() const { return nullptr; }
-  void bvh_rec(unsigned nd, BvhRec& r) const {
-    const float* g = bvhNodes + (size_t)kBvhWords * nd;
-    memcpy(r.s, g, 24 * 4);
-    memcpy(r.ch, g + 24, 4 * 4);
-    memcpy(r.cr, g + 28, 4 * 4);
-  }
-  V3 sphere(unsigned i, float& r2) const {
-    const float* g = geom + 4 * (size_t)i;
-    r2 = g[3];
-    return v3(g[0], g[1], g[2]);
-  }
-  V3 sphere_lane(unsigned i, float& r2) const { return sphere(i, r2); }
-  void sphere4(unsigned i, V3* c, float* r2) const {
-    for (int k = 0; k < 4; ++k) c[k] = sphere(i + k, r2[k]);
-  }
-};
-
+// A host query's scene: the caller's array for the plain loops (walk 0), or
+// the packed tables with the origin box of their BVH, if any (walk 1).
 struct HostRayJob {
   const rtg_sphere* spheres;
   unsigned n;
@@ -194,57 +172,60 @@ static V3 host_centre(const HostRayJob& j, int id) {
   return v3(j.spheres[id].pos.x, j.spheres[id].pos.y, j.spheres[id].pos.z);
 }
 
+// The two queries over either scene: the plain loops, or the functions the
+// kernels call, with every lane of the one-ray "wave" active.
+static int host_closest(const HostSpheres& sc, const RayBox&, V3 o, V3 d, float& t) {
+  return closest_hit(sc, o, d, t);
+}
+template <bool kBvh>
+static int host_closest(const HostScene<kBvh>& sc, const RayBox& box, V3 o, V3 d, float& t) {
+  return ray_closest<kBvh>(sc, box, o, d, true, t);
+}
+static bool host_blocked(const HostSpheres& sc, const RayBox&, V3 o, V3 d, float gap) {
+  return blocked(sc, o, d, gap);
+}
+template <bool kBvh>
+static bool host_blocked(const HostScene<kBvh>& sc, const RayBox& box, V3 o, V3 d, float gap) {
+  return ray_blocked<kBvh>(sc, box, o, d, gap, true);
+}
+
+// body(sc) with the job's scene: the setup of both range functions.
+template <class Body>
+static void with_host_scene(const HostRayJob& j, Body&& body) {
+  if (!j.ps) body(HostSpheres{j.spheres, j.n});
+  else if (!j.ps->bvhNodes.empty()) body(HostScene<true>(*j.ps, true));
+  else body(HostScene<false>(*j.ps, true));
+}
+
 static void intersect_host_range(const HostRayJob& j, const rtg_ray* rays, size_t k0, size_t k1,
                                  rtg_hit* hits) {
-  const HostSpheres plain{j.spheres, j.n};
-  PackedRayScene sc{nullptr, nullptr, 0, 0};
-  bool bvh = false;
-  if (j.ps) {
-    sc = PackedRayScene{j.ps->geom.data(), j.ps->bvhNodes.data(), j.ps->n, j.ps->n4};
-    bvh = !j.ps->bvhNodes.empty();
-  }
-  for (size_t k = k0; k < k1; ++k) {
-    const V3 o = v3(rays[k].origin.x, rays[k].origin.y, rays[k].origin.z);
-    const V3 d = v3(rays[k].dir.x, rays[k].dir.y, rays[k].dir.z);
-    float t;
-    int id;
-    if (!j.ps) id = closest_hit(plain, o, d, t);
-    else if (bvh) id = ray_closest<true>(sc, j.box, o, d, true, t);
-    else id = ray_closest<false>(sc, j.box, o, d, true, t);
-    unsigned w[8];
-    hit_record(o, d, id, t, host_centre(j, id), w);
-    memcpy(&hits[k], w, sizeof w);
-  }
+  with_host_scene(j, [&](const auto& sc) {
+    for (size_t k = k0; k < k1; ++k) {
+      const V3 o = v3(rays[k].origin.x, rays[k].origin.y, rays[k].origin.z);
+      const V3 d = v3(rays[k].dir.x, rays[k].dir.y, rays[k].dir.z);
+      float t;
+      const int id = host_closest(sc, j.box, o, d, t);
+      unsigned w[8];
+      hit_record(o, d, id, t, host_centre(j, id), w);
+      memcpy(&hits[k], w, sizeof w);
+    }
+  });
 }
 
 static void visible_host_range(const HostRayJob& j, const rtg_segment* segs, size_t k0, size_t k1,
                                unsigned char* out) {
-  const HostSpheres plain{j.spheres, j.n};
-  PackedRayScene sc{nullptr, nullptr, 0, 0};
-  bool bvh = false;
-  if (j.ps) {
-    sc = PackedRayScene{j.ps->geom.data(), j.ps->bvhNodes.data(), j.ps->n, j.ps->n4};
-    bvh = !j.ps->bvhNodes.empty();
-  }
-  for (size_t k = k0; k < k1; ++k) {
-    const V3 a = v3(segs[k].a.x, segs[k].a.y, segs[k].a.z);
-    const V3 b = v3(segs[k].b.x, segs[k].b.y, segs[k].b.z);
-    float gap;
-    const V3 d = segment_ray(a, b, gap);
-    bool blk;
-    if (!j.ps) blk = blocked(plain, a, d, gap);
-    else if (bvh) blk = ray_blocked<true>(sc, j.box, a, d, gap, true);
-    else blk = ray_blocked<false>(sc, j.box, a, d, gap, true);
-    out[k] = blk ? 0 : 1;
-  }
+  with_host_scene(j, [&](const auto& sc) {
+    for (size_t k = k0; k < k1; ++k) {
+      const V3 a = v3(segs[k].a.x, segs[k].a.y, segs[k].a.z);
+      const V3 b = v3(segs[k].b.x, segs[k].b.y, segs[k].b.z);
+      float gap;
+      const V3 d = segment_ray(a, b, gap);
+      out[k] = host_blocked(sc, j.box, a, d, gap) ? 0 : 1;
+    }
+  });
 }
 
 // ---- device side ----
-
-// The trace kernels' scene over the context's tables (bind_scene), without
-// frames.
-template <bool kBvh>
-using RayScene = DevScene<false, 64, kBvh, 0>;
 
 // Which record lane k of a launch works on: k itself (order null, a constant
 // of the un-indexed kernels), or order[k] of an _indexed launch.
@@ -349,39 +330,20 @@ static int check_ray_args(const char* what, const rtg_sphere* spheres, unsigned 
     rtg_set_error("%s: null %s buffer", what, in ? "output" : "input");
     return RTG_ERR_INVALID;
   }
-  if (sphNum && !spheres) {
-    rtg_set_error("%s: null scene array", what);
-    return RTG_ERR_INVALID;
-  }
-  return RTG_OK;
-}
-
-// The launch geometry of a batch of n > 0 rays: one-wave workgroups.
-static int ray_blocks(const char* what, size_t n, unsigned* blocks) {
-  const size_t b = (n + 63) / 64;
-  if (b > 0x7FFFFFFFu) {
-    rtg_set_error("%s: batch too large (%zu workgroups)", what, b);
-    return RTG_ERR_INVALID;
-  }
-  *blocks = (unsigned)b;
-  return RTG_OK;
+  return check_scene_arrays(what, spheres, sphNum);
 }
 
 static int host_job(const char* what, const rtg_sphere* spheres, unsigned sphNum, int walk,
                     PackedScene* ps, HostRayJob* job) {
-  if (walk != 0 && walk != 1) {
-    rtg_set_error("%s: walk %d (0: plain loops, 1: the kernel's query path)", what, walk);
-    return RTG_ERR_INVALID;
-  }
+  int rc = check_walk(what, walk);
+  if (rc) return rc;
   job->spheres = spheres;
   job->n = sphNum;
   job->ps = nullptr;
   job->box = RayBox{};
   if (walk == 1) {
-    if (sphNum >= RTG_MAX_SPHERES) {
-      rtg_set_error("%s: %u spheres (at most %u)", what, sphNum, RTG_MAX_SPHERES - 1);
-      return RTG_ERR_INVALID;
-    }
+    rc = check_sphere_count(what, sphNum);
+    if (rc) return rc;
     pack_scene(spheres, sphNum, nullptr, 0, ps);  // as rtg_context_set_scene
     job->ps = ps;
     job->box = ray_box(ps->originBox);
@@ -447,7 +409,7 @@ static int intersect_launch(rtg_context* ctx, const rtg_ray* raysDevice, const u
   }
   if (n == 0) return RTG_OK;
   unsigned blocks;
-  const int rc = ray_blocks("intersect", n, &blocks);
+  const int rc = ray_blocks("intersect", "batch", n, &blocks);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   if (indexed) {
@@ -486,7 +448,7 @@ static int visible_launch(rtg_context* ctx, const rtg_segment* segsDevice, const
   }
   if (n == 0) return RTG_OK;
   unsigned blocks;
-  const int rc = ray_blocks("visible", n, &blocks);
+  const int rc = ray_blocks("visible", "batch", n, &blocks);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   if (indexed) {

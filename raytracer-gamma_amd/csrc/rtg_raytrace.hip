@@ -8,7 +8,8 @@
 // workgroups, 24 bytes in, 12 bytes out) is instantiated per stack size next
 // to the render kernels (rtg_trace_s.hip), for BVH or not and CPU or OpenCL
 // semantics.  The stack machine is the renders' trace_sample (rtg_trace.h)
-// with a start origin and the query path RayPath (rtg_rays.h) switched on.
+// with a start origin and the query path RayPath switched on: trace_ray
+// (rtg_rays.h).
 //
 // WHICH RAYS TAKE WHICH PATH.  The render kernels shorten their queries with
 // tables that were proved for the renderer's own rays: a camera at 0, hit
@@ -93,10 +94,15 @@
 //
 // FP contract: the Makefile's FPFLAGS, as every kernel.
 //
-// rtg_raytrace_host: walk 0 = trace_sample<S, 0> with plain loops over every
-// sphere for every query (closest_hit, blocked, the flat primary_container;
-// no table), the yardstick; walk 1 = the kernel's own path (trace_sample<S, 2>
-// with RayPath) over the packed tables, one ray per "wave".
+// The one call that takes this path is trace_ray (rtg_rays.h, where its
+// constants are explained); the kernel and walk 1 of the host form make it.
+//
+// rtg_raytrace_host: walk 0 = trace_ray_plain, plain loops over every sphere
+// for every query, the yardstick; walk 1 = the kernel's own path (trace_ray)
+// over the packed tables (HostScene), one ray per "wave".  Its instantiation
+// per stack size comes from host_trace_fn (rtg_host_scene.h), the kernel's
+// from stack_kernels (rtg_trace_kernels.h); the argument checks shared with
+// the other entry points are rtg_entry.h's.
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
@@ -114,23 +120,7 @@ static_assert(sizeof(rtg_ray) == 24 && sizeof(rtg_vec) == 12, "24 B in, 12 B out
 
 namespace rtg {
 
-static RayTraceFn pick_raytrace(int S, bool bvh, bool cl) {
-  switch (S) {
-#define RTG_CASE(k) case k: return raytrace_fn_s##k(bvh, cl);
-    RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
-    RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
-    RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
-#undef RTG_CASE
-    default: return nullptr;
-  }
-}
-
 // ---- host forms ----
-
-static void store_colour(rtg_vec* dst, V3 c) {
-  const unsigned w[3] = {nan_bits(c.x), nan_bits(c.y), nan_bits(c.z)};
-  memcpy(dst, w, sizeof w);
-}
 
 // Rays [k0, k1) of the batch; kWalk 1: the kernel's path, else plain loops.
 template <int S, bool kCL, bool kWalk, bool kBvh>
@@ -140,39 +130,13 @@ static void raytrace_host_range(const PackedScene& ps, const RayBox& box, const 
   for (size_t k = k0; k < k1; ++k) {
     const V3 o = v3(rays[k].origin.x, rays[k].origin.y, rays[k].origin.z);
     const V3 d = v3(rays[k].dir.x, rays[k].dir.y, rays[k].dir.z);
-    V3 c;
-    if constexpr (kWalk)
-      c = trace_sample<S, 2, kCL, RayPath<kBvh>>(sc, d, sc.frames(), false, ~0ull, o,
-                                                 RayPath<kBvh>{box});
-    else
-      c = trace_sample<S, 0, kCL>(sc, d, sc.frames(), false, ~0ull, o);
-    store_colour(dst + k, c);
+    if constexpr (kWalk) store_colour(dst + k, trace_ray<S, kCL, kBvh>(sc, box, o, d));
+    else store_colour(dst + k, trace_ray_plain<S, kCL>(sc, o, d));
   }
 }
 
 typedef void (*HostRangeFn)(const PackedScene&, const RayBox&, const rtg_ray*, size_t, size_t,
                             rtg_vec*);
-template <int S>
-static HostRangeFn host_range_fn(bool cl, bool walk, bool bvh) {
-  if (!walk)
-    return cl ? raytrace_host_range<S, true, false, false>
-              : raytrace_host_range<S, false, false, false>;
-  if (bvh)
-    return cl ? raytrace_host_range<S, true, true, true>
-              : raytrace_host_range<S, false, true, true>;
-  return cl ? raytrace_host_range<S, true, true, false>
-            : raytrace_host_range<S, false, true, false>;
-}
-static HostRangeFn pick_host_range(int S, bool cl, bool walk, bool bvh) {
-  switch (S) {
-#define RTG_CASE(k) case k: return host_range_fn<k>(cl, walk, bvh);
-    RTG_CASE(1) RTG_CASE(2) RTG_CASE(3) RTG_CASE(4) RTG_CASE(5) RTG_CASE(6) RTG_CASE(7)
-    RTG_CASE(8) RTG_CASE(9) RTG_CASE(10) RTG_CASE(11) RTG_CASE(12) RTG_CASE(13)
-    RTG_CASE(14) RTG_CASE(15) RTG_CASE(16)
-#undef RTG_CASE
-    default: return nullptr;
-  }
-}
 
 }  // namespace rtg
 
@@ -185,15 +149,8 @@ static int check_raytrace_args(const rtg_sphere* spheres, unsigned sphNum, const
     rtg_set_error("raytrace: null %s buffer", rays ? "colour" : "ray");
     return RTG_ERR_INVALID;
   }
-  if ((sphNum && !spheres) || (lgtNum && !lights)) {
-    rtg_set_error("raytrace: null scene array");
-    return RTG_ERR_INVALID;
-  }
-  if (stackSize < 1 || stackSize > RTG_MAX_STACK) {
-    rtg_set_error("raytrace: stackSize %d outside [1, %d]", stackSize, RTG_MAX_STACK);
-    return RTG_ERR_INVALID;
-  }
-  return RTG_OK;
+  const int rc = check_scene_arrays("raytrace", spheres, sphNum, lights, lgtNum);
+  return rc ? rc : check_stack("raytrace", stackSize);
 }
 
 extern "C" {
@@ -202,27 +159,21 @@ int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_ligh
                       unsigned lgtNum, const rtg_ray* rays, size_t n, int stackSize, int semantics,
                       rtg_vec* dstHost, int walk, int nthreads) {
   rtg_clear_error();
-  const int rc = check_raytrace_args(spheres, sphNum, lights, lgtNum, rays, dstHost, stackSize);
+  int rc = check_raytrace_args(spheres, sphNum, lights, lgtNum, rays, dstHost, stackSize);
+  if (!rc) rc = check_semantics("raytrace", semantics);
+  if (!rc) rc = check_walk("raytrace", walk);
+  if (!rc) rc = check_sphere_count("raytrace", sphNum);
   if (rc) return rc;
-  if (semantics != RTG_SEMANTICS_CPU && semantics != RTG_SEMANTICS_OPENCL) {
-    rtg_set_error("raytrace: semantics %d (0: CPU, 1: OpenCL)", semantics);
-    return RTG_ERR_INVALID;
-  }
-  if (walk != 0 && walk != 1) {
-    rtg_set_error("raytrace: walk %d (0: plain loops, 1: the kernel's query path)", walk);
-    return RTG_ERR_INVALID;
-  }
-  if (sphNum >= RTG_MAX_SPHERES) {
-    rtg_set_error("raytrace: %u spheres (at most %u)", sphNum, RTG_MAX_SPHERES - 1);
-    return RTG_ERR_INVALID;
-  }
   if (n == 0) return RTG_OK;
   PackedScene ps;
   pack_scene(spheres, sphNum, lights, lgtNum, &ps);  // as rtg_context_set_scene
   const bool bvh = walk == 1 && !ps.bvhNodes.empty();
   const RayBox box = bvh ? ray_box(ps.originBox) : RayBox{};
-  const HostRangeFn fn =
-      pick_host_range(stackSize, semantics == RTG_SEMANTICS_OPENCL, walk == 1, bvh);
+  const HostRangeFn fn = host_trace_fn(
+      stackSize, semantics == RTG_SEMANTICS_OPENCL, walk == 1, bvh,
+      [](auto s, auto cl, auto wk, auto bv) -> HostRangeFn {
+        return raytrace_host_range<s.value, cl.value, wk.value, bv.value>;
+      });
   host_bands(n, nthreads, [&](size_t k0, size_t k1) { fn(ps, box, rays, k0, k1, dstHost); });
   return RTG_OK;
 }
@@ -244,28 +195,25 @@ static int raytrace_launch(rtg_context* ctx, const rtg_ray* raysDevice, const un
     rtg_set_error("raytrace: null %s buffer", raysDevice ? "colour" : "ray");
     return RTG_ERR_INVALID;
   }
-  if (stackSize < 1 || stackSize > RTG_MAX_STACK) {
-    rtg_set_error("raytrace: stackSize %d outside [1, %d]", stackSize, RTG_MAX_STACK);
-    return RTG_ERR_INVALID;
-  }
+  int rc = check_stack("raytrace", stackSize);
+  if (rc) return rc;
   if (indexed && !order) {
     rtg_set_error("raytrace: null order buffer");
     return RTG_ERR_INVALID;
   }
   if (n == 0) return RTG_OK;
-  const size_t blocks = (n + 63) / 64;  // one-wave workgroups
-  if (blocks > 0x7FFFFFFFu) {
-    rtg_set_error("raytrace: batch too large (%zu workgroups)", blocks);
-    return RTG_ERR_INVALID;
-  }
+  unsigned blocks;
+  rc = ray_blocks("raytrace", "batch", n, &blocks);
+  if (rc) return rc;
   const bool bvh = a.bvhNodes != nullptr;
-  const RayTraceFn fn = pick_raytrace(stackSize, bvh, semantics == RTG_SEMANTICS_OPENCL);
+  const StackKernels* sk = stack_kernels(stackSize);
+  const RayTraceFn fn = sk ? sk->raytrace(bvh, semantics == RTG_SEMANTICS_OPENCL) : nullptr;
   if (!fn) {  // a missing kernel is an error, never another path
     rtg_set_error("raytrace: no kernel for stackSize %d", stackSize);
     return RTG_ERR_INVALID;
   }
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64), raytrace_lds_bytes(stackSize, bvh),
+  hipLaunchKernelGGL(fn, dim3(blocks), dim3(64), raytrace_lds_bytes(stackSize, bvh),
                      (hipStream_t)stream, a, box, raysDevice, order, n, dstDevice);
   HIP_TRY(hipGetLastError());
   return RTG_OK;

@@ -9,13 +9,31 @@
 
 namespace rtg {
 
-typedef void (*RayTraceFn)(const SceneTables, const RayBox, const rtg_ray*, const unsigned*, size_t,
-                           rtg_vec*);
-
 // The kernel's LDS image, one wave: the lanes' frame colours as in the render
 // kernels (frame_lds_levels), then the wave's 64-entry BVH traversal stack.
 constexpr size_t raytrace_lds_bytes(int S, bool bvh) {
   return (size_t)frame_lds_levels(S, bvh) * 64 * 16 + (bvh ? 64 * sizeof(int) : 0);
+}
+
+// The scene of a ray-trace kernel (raytrace_kernel, camera_kernel): one wave,
+// the LDS image above (`lds4`, the workgroup's dynamic LDS) and the context's
+// tables.
+template <int S, bool kBvh>
+__device__ __forceinline__ void bind_raytrace_scene(RayScene<kBvh>& sc, const SceneTables& a,
+                                                    float4* lds4) {
+  constexpr int NFL = frame_lds_levels(S, kBvh);
+  sc.lfr = reinterpret_cast<FrameC*>(lds4) + threadIdx.x;
+  sc.nfl = NFL;
+  bind_scene(sc, a, reinterpret_cast<int*>(lds4 + NFL * 64));  // the stack: kBvh only
+}
+
+// A colour into the caller's array, NaN as the frame's NaNs; `dst` is 12 B the
+// lane owns.
+__device__ __forceinline__ void store_colour_dev(rtg_vec* dst, V3 c) {
+  float* w = reinterpret_cast<float*>(dst);
+  w[0] = canon_nan(c.x);
+  w[1] = canon_nan(c.y);
+  w[2] = canon_nan(c.z);
 }
 
 // One lane per ray, one-wave workgroups; n > 0.  Lanes past n trace nothing
@@ -31,11 +49,8 @@ __global__ __launch_bounds__(64) void raytrace_kernel(const SceneTables a, const
                                                       const unsigned* __restrict__ order,
                                                       size_t n, rtg_vec* __restrict__ dst) {
   extern __shared__ float4 lds4[];
-  constexpr int NFL = frame_lds_levels(S, kBvh);
-  DevScene<false, 64, kBvh, 0> sc;
-  sc.lfr = reinterpret_cast<FrameC*>(lds4) + threadIdx.x;
-  sc.nfl = NFL;
-  bind_scene(sc, a, reinterpret_cast<int*>(lds4 + NFL * 64));  // the stack: kBvh only
+  RayScene<kBvh> sc;
+  bind_raytrace_scene<S>(sc, a, lds4);
   size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (k >= n) return;
   if (order) {
@@ -45,12 +60,7 @@ __global__ __launch_bounds__(64) void raytrace_kernel(const SceneTables a, const
   const float* r = reinterpret_cast<const float*>(rays + k);  // k < n: 24 B of the batch
   const V3 o = v3(r[0], r[1], r[2]);
   const V3 d = v3(r[3], r[4], r[5]);
-  const V3 c = trace_sample<S, 2, kCL, RayPath<kBvh>>(sc, d, sc.frames(), false, ~0ull, o,
-                                                      RayPath<kBvh>{box});
-  float* w = reinterpret_cast<float*>(dst + k);  // k < n: 12 B of the destination
-  w[0] = canon_nan(c.x);
-  w[1] = canon_nan(c.y);
-  w[2] = canon_nan(c.z);
+  store_colour_dev(dst + k, trace_ray<S, kCL, kBvh>(sc, box, o, d));  // k < n: 12 B of dst
 }
 
 // bvh: the scene has a BVH (SceneTables::bvhNodes); cl: RTG_SEMANTICS_OPENCL.
@@ -59,12 +69,5 @@ static RayTraceFn raytrace_fn(bool bvh, bool cl) {
   if (bvh) return cl ? raytrace_kernel<S, true, true> : raytrace_kernel<S, true, false>;
   return cl ? raytrace_kernel<S, false, true> : raytrace_kernel<S, false, false>;
 }
-
-// One per stack size, defined in rtg_trace_s<S>.hip.
-#define RTG_DECL(k) RayTraceFn raytrace_fn_s##k(bool bvh, bool cl);
-RTG_DECL(1) RTG_DECL(2) RTG_DECL(3) RTG_DECL(4) RTG_DECL(5) RTG_DECL(6) RTG_DECL(7)
-RTG_DECL(8) RTG_DECL(9) RTG_DECL(10) RTG_DECL(11) RTG_DECL(12) RTG_DECL(13)
-RTG_DECL(14) RTG_DECL(15) RTG_DECL(16)
-#undef RTG_DECL
 
 }  // namespace rtg

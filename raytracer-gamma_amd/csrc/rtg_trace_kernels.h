@@ -2,7 +2,9 @@
 // templates over the stack capacity S (RTSTACK_MAXSIZE, raytraceStack.h:10)
 // and the kernel variant.  Each rtg_trace_s<S>.hip translation unit
 // instantiates one S (trace_fn<S>), so the 16 stack sizes compile in
-// parallel; rtg_kernel.hip holds the launch code and the C ABI.
+// parallel, and exports its kernels as one record (StackKernels, at the end of
+// this file with the list of stack sizes, RTG_FOR_EACH_S); rtg_kernel.hip
+// holds the launch code and the C ABI.
 //
 // Replaces the OpenCL kernel `raytrace` (raytrace_kernel.cl:870-973),
 // computing the reference CPU path's framebuffer (raytracer.h) bit for bit;
@@ -212,7 +214,7 @@ struct DevScene {
   }
   // BVH node nd: four slots {centre, screen radius^2}, their children and
   // containment radii^2 (wave-uniform nd: scalar loads).
-  // (the kBvh kernels run only for scenes with a BVH: pick_trace)
+  // (the kBvh kernels run only for scenes with a BVH: trace_fn)
   __device__ __forceinline__ bool has_bvh() const { return kBvh; }
   __device__ __forceinline__ int* bvh_stack() const { return bvhStk; }
   // Sphere lists (BVH scenes): ranges and 32-byte records (one scalar load).
@@ -1193,15 +1195,42 @@ static TraceFn trace_fn(int variant, bool bvh, int list) {
   }
 }
 
-// One per stack size, defined in rtg_trace_s<S>.hip.
-#define RTG_DECL(k) TraceFn trace_fn_s##k(int variant, bool bvh, int list);
-RTG_DECL(1) RTG_DECL(2) RTG_DECL(3) RTG_DECL(4) RTG_DECL(5) RTG_DECL(6) RTG_DECL(7)
-RTG_DECL(8) RTG_DECL(9) RTG_DECL(10) RTG_DECL(11) RTG_DECL(12) RTG_DECL(13)
-RTG_DECL(14) RTG_DECL(15) RTG_DECL(16)
-#undef RTG_DECL
+struct RayBox;   // rtg_rays.h
+struct KeyBox;   // rtg_order.h
+struct CamPose;  // rtg_camera.h
 
-struct RayBox;  // rtg_rays.h
-struct KeyBox;  // rtg_order.h
+// THE list of stack capacities: X(k) for every k an object rtg_trace_s<k>.o is
+// built for (the Makefile's SVALS).
+#define RTG_FOR_EACH_S(X) \
+  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+// RTG_MAX_STACK entries, each in 1..RTG_MAX_STACK (and distinct: they are the
+// case labels of stack_kernels), so the list is 1..RTG_MAX_STACK.
+#define RTG_X(k) +(k >= 1 && k <= RTG_MAX_STACK ? 1 : RTG_MAX_STACK + 1)
+static_assert(0 RTG_FOR_EACH_S(RTG_X) == RTG_MAX_STACK, "RTG_FOR_EACH_S is 1..RTG_MAX_STACK");
+#undef RTG_X
+
+// The batch ray tracer's kernel (rtg_raytrace_kernels.h) and the posed
+// camera's fused render kernel (rtg_camera_kernels.h).
+typedef void (*RayTraceFn)(const SceneTables, const RayBox, const rtg_ray*, const unsigned*, size_t,
+                           rtg_vec*);
+typedef void (*CameraFn)(const SceneTables, const RayBox, const Camera, const CamPose, unsigned,
+                         unsigned, unsigned, rtg_vec*);
+
+// What one per-S object (rtg_trace_s<S>.hip) exports: its kernels by variant
+// (trace_fn<S>, raytrace_fn<S>, camera_fn<S>).
+struct StackKernels {
+  TraceFn (*trace)(int variant, bool bvh, int list);
+  RayTraceFn (*raytrace)(bool bvh, bool cl);
+  CameraFn (*camera)(bool bvh, bool cl);
+};
+#define RTG_X(k) const StackKernels* stack_kernels_s##k();
+RTG_FOR_EACH_S(RTG_X)
+#undef RTG_X
+
+// The record of stack capacity S (rtg_kernel.hip); null outside
+// 1..RTG_MAX_STACK.  A launcher that gets null, or a null kernel from the
+// record, reports it: a missing kernel is an error, never another path.
+const StackKernels* stack_kernels(int S);
 
 }  // namespace rtg
 

@@ -9,7 +9,9 @@ csrc/rtg_camera.hip): rays and frames from any viewpoint.
      golden small frame;
   4. posed frames: walk 0 is the fold of rtg_raytrace_host(walk 0) over the
      restated rays (the normative yardstick), walk 1 equals walk 0, with
-     conditions that keep both from passing on black frames;
+     conditions that keep both from passing on black frames; and a 9 x 9
+     frame at every stack size 1 .. 16, each size pinned to the plain loops
+     and the oracle at that size;
   5. picking from a pose: the generator plus rtg_intersect_host;
   6. the argument errors of the contract;
   7. aliasFactor <= 0: a +0 frame and no rays.
@@ -28,7 +30,8 @@ import pytest
 
 import raygen
 from conftest import GOLDEN, bits_equal, first_mismatch, load_f32, load_scene
-from test_raytrace_host import THREADS, fold, sample_rays, scene_with_lights
+from test_raytrace_host import (STACK_H, STACK_SCENES, STACK_SIZES, STACK_W, THREADS, fold,
+                                sample_rays, scene_with_lights)
 
 F = np.float32
 
@@ -264,6 +267,44 @@ def test_posed_frame_is_the_fold_of_the_batch_call(rtg, scene, name):
     ident = identity_frame(scene, zoom)
     differ = float((fb.view(np.uint32) != ident.view(np.uint32)).any(-1).mean())
     assert differ >= 0.05, differ
+
+
+# ---- 4b. every stack size (the dispatch by S is a table: stack_kernels, with_stack) ----
+
+STACK_POSE, STACK_AA = "in_clearest", 1.0  # from inside the clearest sphere: deep trees
+# Neighbouring sizes S = k and k + 1 whose posed walk-0 frames differ in at
+# least one word (as STACK_TOLD_APART of test_raytrace_host.py; looked up when
+# the pose was chosen: scene 12 k = 1 .. 9, scene 65 k = 1 .. 12).  Above that
+# every size is still pinned to the plain loops and the oracle, but the test
+# cannot catch a swap of two sizes that trace these 81 pixels alike.
+STACK_FRAMES_TOLD_APART = range(1, 10)
+
+
+@functools.lru_cache(maxsize=None)
+def stack_frame(scene, S, sem=0):
+    """render_camera_host(walk 0) of the 9 x 9 posed frame at stack size S,
+    computed once and left unchanged (test_gpu_camera.py compares the device
+    against it): four 8 x 8 tiles on the device, three of them ragged."""
+    return posed_frame(scene, STACK_POSE, sem, STACK_W, STACK_H, STACK_AA, S)
+
+
+@pytest.mark.parametrize("S", STACK_SIZES)
+@pytest.mark.parametrize("scene", STACK_SCENES)
+def test_every_stack_size(rtg, oracle, scene, S):
+    sph, lg = scene_with_lights(scene)
+    cam, zoom = pose(STACK_POSE, scene)
+    want = stack_frame(scene, S)
+    got = rtg.render_camera_host(sph, lg, cam, STACK_W, STACK_H, zoom, STACK_AA, S, walk=1,
+                                 threads=THREADS)
+    assert got.tobytes() == want.tobytes(), (S, first_mismatch(got, want))
+    # the primary rays: the identity pose's frame is the oracle's at that S
+    fb = rtg.render_camera_host(sph, lg, rtg.camera_identity(), STACK_W, STACK_H, -4.0, STACK_AA,
+                                S, walk=0, threads=THREADS)
+    ref = oracle.render(sph, lg, STACK_W, STACK_H, S, aa=1.0)
+    assert bits_equal(fb, ref), (S, first_mismatch(fb, ref))
+    if S in STACK_FRAMES_TOLD_APART:
+        assert want.tobytes() != stack_frame(scene, S + 1).tobytes(), \
+            f"S = {S} and {S + 1} trace this frame alike"
 
 
 # ---- 5. picking from a pose ----

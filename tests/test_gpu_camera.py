@@ -16,8 +16,10 @@ import numpy as np
 import pytest
 
 from conftest import PKG, ROOT, bits_equal, first_mismatch
-from test_camera_host import ODD_BASES, PAA, PH, PS, PW, pose, posed_cases, posed_frame
-from test_raytrace_host import THREADS, mixed_rays, scene_with_lights
+from test_camera_host import (ODD_BASES, PAA, PH, PS, PW, STACK_AA, STACK_POSE, pose, posed_cases,
+                              posed_frame, stack_frame)
+from test_raytrace_host import (STACK_H, STACK_SCENES, STACK_SIZES, STACK_W, THREADS, mixed_rays,
+                                scene_with_lights)
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +90,29 @@ def test_device_equals_plain_loops(R, torch_cuda, scene, name, W, H, aa, S, sem)
     assert got.tobytes() == want.tobytes(), first_mismatch(got, want)  # NaN words canonical
     if len(sph) and W * H >= 64:
         assert (want != 0).any(), "a black frame"
+
+
+@pytest.mark.parametrize("scene", STACK_SCENES)
+def test_every_stack_size(R, torch_cuda, scene):
+    """The 9 x 9 posed frame of test_camera_host.stack_frame (four 8 x 8 tiles,
+    three of them ragged) at every S, CPU semantics, and at S = 2 and 16 with
+    the OpenCL kernel's: the kernel of each S comes from one table.  The host's
+    walk 0 at that S is what tells neighbouring sizes apart
+    (STACK_FRAMES_TOLD_APART there)."""
+    sph, lg = scene_with_lights(scene)
+    cam, zoom = pose(STACK_POSE, scene)
+    ctx = R.Context(0)
+    try:
+        ctx.set_scene(sph, lg)
+        for sem, sizes in ((0, STACK_SIZES), (1, (2, 16))):
+            ctx.set_semantics(sem)
+            for S in sizes:
+                got = _frame(torch_cuda, ctx, cam, STACK_W, STACK_H, zoom, STACK_AA, S)
+                want = stack_frame(scene, S, sem)
+                assert got.tobytes() == want.tobytes(), (sem, S, first_mismatch(got, want))
+    finally:
+        ctx.close()
+    assert stack_frame(scene, 2, 1).tobytes() != stack_frame(scene, 2).tobytes()
 
 
 @pytest.mark.parametrize("scene", ["reference", 12, 200, "c5"])

@@ -17,7 +17,8 @@ import pytest
 import raygen
 from conftest import GOLDEN, PKG, ROOT, bits_equal, first_mismatch, load_f32, load_scene
 from test_gpu_rays import PAD, _intersect, _mixed, _odd_rays
-from test_raytrace_host import THREADS, fold, mixed_rays, sample_rays, scene_with_lights
+from test_raytrace_host import (STACK_SCENES, STACK_SIZES, THREADS, fold, mixed_rays, sample_rays,
+                                scene_with_lights, stack_batch, stack_colours)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,14 +39,17 @@ def torch_cuda():
     return torch
 
 
-def _raytrace(torch, ctx, rays, S):
+def _raytrace(torch, ctx, rays, S, order=None):
     """The context path: colours of `rays` ((N, 6) float32) as (N, 3) float32;
-    the destination is pre-filled and PAD records longer, the tail must stay."""
+    the destination is pre-filled and PAD records longer, the tail must stay.
+    order: N uint32 indices for the _indexed launch."""
     n = len(rays)
     src = torch.from_numpy(np.ascontiguousarray(rays, np.float32).reshape(-1, 6)).cuda()
     dst = torch.full(((n + PAD) * 3,), FILL, dtype=torch.int32, device="cuda")
+    idx = None if order is None else torch.from_numpy(np.asarray(order, np.uint32).view(np.int32)).cuda()
     ctx.raytrace_device(src.data_ptr() if n else dst.data_ptr(), n, dst.data_ptr(), stack_size=S,
-                        stream=torch.cuda.current_stream().cuda_stream)
+                        stream=torch.cuda.current_stream().cuda_stream,
+                        order=0 if idx is None else idx.data_ptr())
     torch.cuda.synchronize()
     out = dst.cpu().numpy()
     assert (out[n * 3:] == FILL).all(), "colours past the batch were written"
@@ -92,6 +96,36 @@ def test_device_equals_plain_loops(R, torch_cuda, name):
         ctx.close()
     if len(sph) >= 2:
         assert (np.nan_to_num(want) > 0).any()
+
+
+# ---- 5b. every stack size (the kernel of each S comes from one table) ----
+
+@pytest.mark.parametrize("name", STACK_SCENES)
+def test_every_stack_size(R, torch_cuda, name):
+    """The 130 rays of test_raytrace_host.stack_batch (two full waves and a
+    two-lane tail) at every S, CPU semantics, and at S = 2 and 16 with the
+    OpenCL kernel's; one _indexed launch with the order reversed.  The host's
+    walk 0 at that S is what tells neighbouring sizes apart (STACK_TOLD_APART
+    there)."""
+    sph, lg, rays = stack_batch(name)
+    assert len(rays) == 130
+    ctx = R.Context(0)
+    ctx.set_scene(sph, lg)
+    try:
+        for S in STACK_SIZES:
+            got = _raytrace(torch_cuda, ctx, rays, S)
+            want = stack_colours(name, S)
+            assert got.tobytes() == want.tobytes(), (S, _diff(got, want, rays))
+        got = _raytrace(torch_cuda, ctx, rays, 6, order=np.arange(len(rays))[::-1])
+        assert got.tobytes() == stack_colours(name, 6).tobytes(), "indexed"
+        ctx.set_semantics(1)  # the OpenCL kernel's semantics
+        for S in (2, 16):
+            got = _raytrace(torch_cuda, ctx, rays, S)
+            want = stack_colours(name, S, 1)
+            assert got.tobytes() == want.tobytes(), ("opencl", S, _diff(got, want, rays))
+    finally:
+        ctx.close()
+    assert stack_colours(name, 2, 1).tobytes() != stack_colours(name, 2).tobytes()
 
 
 # ---- 6. a wave of only `odd` rays ----

@@ -7,7 +7,8 @@ csrc/rtg_raytrace.hip): rayTrace's colour for a caller's own rays.
      folded as main.cpp:442-445 does, is the reference's own frame;
   3. walk 1 (the device kernel's path compiled for the host) equals walk 0 byte
      for byte on rays from anywhere, with conditions that keep it from passing
-     vacuously;
+     vacuously; and for every stack size 1 .. 16 on a small batch, each size
+     pinned to the plain loops and the oracle at that size;
   4. the argument errors of the contract.
 
 All comparisons are bit for bit, NaN canonicalised as conftest.bits_equal does
@@ -212,6 +213,59 @@ def test_kernel_path_equals_plain_loops(rtg, name):
     if len(sph) >= 2:
         assert (deep.view(np.uint32) != cols[2].view(np.uint32)).any(), "no ray went deeper than S = 2"
         assert (np.nan_to_num(deep) > 0).any()
+
+
+# ---- 3b. every stack size (the dispatch by S is a table: stack_kernels, with_stack) ----
+
+STACK_SIZES = tuple(range(1, 17))
+STACK_SCENES = [12, 65]  # flat, and the smallest scene with a BVH
+STACK_N = 130  # on the device: two full waves and a two-lane tail
+STACK_W = STACK_H = 9  # the frame of the primary rays; test_camera_host.py poses the same frame
+# Neighbouring sizes S = k and k + 1 whose walk-0 colours of stack_batch differ
+# in at least one word, so that the batch catches a swap of the two table
+# entries.  A condition on the inputs, looked up when the batches were chosen
+# (scene 12: k = 1 .. 12, scene 65: k = 1 .. 10) and kept by the assert below
+# for k = 1 .. 10 on both; S = 6 is the reference's size.  For larger k every
+# size is still pinned to the plain loops and, on the primary rays, to the
+# oracle at that S, but no ray of these batches goes that deep, so the test
+# cannot catch a swap of two sizes above 11 that trace these rays alike.
+STACK_TOLD_APART = range(1, 11)
+
+
+def stack_batch(name):
+    """(spheres, lights, the first STACK_N rays of the scene's walk batch)."""
+    sph, lg, rays = walk_batch(name)
+    return sph, lg, rays[:STACK_N]
+
+
+@functools.lru_cache(maxsize=None)
+def stack_colours(name, S, sem=0):
+    """walk 0 of stack_batch at stack size S, computed once and left unchanged
+    (test_gpu_raytrace.py compares the device against it)."""
+    import rtg_amd as R
+    sph, lg, rays = stack_batch(name)
+    col = R.raytrace_host(sph, lg, rays, stack_size=S, semantics=sem, walk=0, threads=THREADS)
+    col.setflags(write=False)
+    return col
+
+
+@pytest.mark.parametrize("S", STACK_SIZES)
+@pytest.mark.parametrize("name", STACK_SCENES)
+def test_every_stack_size(rtg, oracle, name, S):
+    sph, lg, rays = stack_batch(name)
+    assert len(rays) == STACK_N
+    want = stack_colours(name, S)
+    got = rtg.raytrace_host(sph, lg, rays, stack_size=S, walk=1, threads=THREADS)
+    assert got.tobytes() == want.tobytes(), (S, first_mismatch(got, want))
+    prim = raygen.primary(STACK_W, STACK_H)
+    col = rtg.raytrace_host(sph, lg, prim, stack_size=S, walk=0, threads=THREADS)
+    with np.errstate(invalid="ignore"):
+        fb = (F(0) + col * F(1)).reshape(STACK_H, STACK_W, 3)
+    ref = oracle.render(sph, lg, STACK_W, STACK_H, S, aa=1.0)
+    assert bits_equal(fb, ref), (S, first_mismatch(fb, ref))
+    if S in STACK_TOLD_APART:
+        assert want.tobytes() != stack_colours(name, S + 1).tobytes(), \
+            f"S = {S} and {S + 1} trace this batch alike"
 
 
 def test_some_colour_of_the_batches_has_a_nan_word(rtg):
