@@ -198,7 +198,7 @@ enum : int { kCntSamples = 0, kCntPrimQ, kCntPrimSel, kCntPrimCand, kCntEnterQ, 
              kCntContainMasked, kCntContainSel, kCntContainFull, kCntRefraction, kCntReflPush,
              kCntBvhNodeTests, kCntBvhSphereTests, kCntConeQ, kCntConeSel,
              kCntBvhShadowQ, kCntBvhShadowNodeTests, kCntBvhShadowSphereTests,
-             kUQuery,       // make_query: a, 4a, 2a, screen factors, 1/2a
+             kUQuery,       // make_query: a, 4a, 2a, screen factors, 1/2a (head and rest)
              kUPrimIter,    // closest_hit_sel_fused: one sphere's primary radicand
              kUPrimExact,   // ... its root test (sqrt, two quotients, accept, best)
              kUSelIter,     // closest_sel_fused: pass-1 screen of one sphere
@@ -206,8 +206,8 @@ enum : int { kCntSamples = 0, kCntPrimQ, kCntPrimSel, kCntPrimCand, kCntEnterQ, 
              kUShdIter,     // blocked_sel_fused: pass-1 screen of one sphere
              kUShdExact,    // ... exact root test + blocking test
              kUEnterHead,   // closest_enter_fused: sphere h's root test + guard tests
-             kUEnterIter,   // ... one overlap sphere, loaded
-             kUEnterExact,  // ... its root test + lexicographic update
+             kUEnterIter,   // ... one overlap sphere: record, own-mask bit, radicand
+             kUEnterExact,  // ... its roots + lexicographic update
              kUFullGroup,   // candidate_mask: pass-1 screens of 4 spheres
              kUFullExact,   // closest_hit_mask / blocked_mask: one candidate's root test
              kUBvhNode,     // BVH node visit: pop, records, front-to-back push
@@ -240,6 +240,9 @@ enum : int { kCntSamples = 0, kCntPrimQ, kCntPrimSel, kCntPrimCand, kCntEnterQ, 
              kUDiagInsig,     // (diagnostic) stage-0 query; lane value: intensity insignificant
              kUDiagInsigAll,  // (diagnostic) stage-0 query whose every active lane is insignificant
              kUWave,        // one wave of the sample kernel: prologue, list walk, epilogue
+             kUQueryHead,   // query_head alone: a query that found its selection empty
+             kUDiagShdEmpty,   // (diagnostic) masked shadow query, selection empty after the own-sphere drop
+             kUDiagConeEmpty,  // (diagnostic) cone query, selection empty after the origin-sphere drop
              kCntSlots };
 enum : int { kProbeClosest = 0, kProbeShadow = 1, kProbeRefraction = 2, kProbeTotal = 3,
              kProbeMatte = 4, kProbePush = 5, kProbeUnwind = 6, kProbeShade = 7,
@@ -294,12 +297,19 @@ struct RayQ {
   bool slow;      // some active lane of the wave is not `fast` (wave-uniform)
 };
 
-RTG_HD RayQ make_query(V3 o, V3 d) {
-  RayQ q;
+// A query in two parts, for the sites that may find nothing left to test
+// (blocked_sel, the cone query of trace_sample): query_head is what no_root
+// reads (o, d, a4) and returns a = d.d; query_rest adds what only a sphere
+// test reads.  Together they are make_query's operations, in its order.
+RTG_HD RayQ query_head(V3 o, V3 d, float& a) {
+  RayQ q{};  // (the rest's fields: defined values until query_rest)
   q.o = o;
   q.d = d;
-  const float a = vdot(d, d);
+  a = vdot(d, d);
   q.a4 = 4.0f * a;
+  return q;
+}
+RTG_HD void query_rest(RayQ& q, float a) {
   q.den = 2.0f * a;
   q.ap = a * (1.0f - 0x1p-16f);
   q.fast = (q.den >= 0x1p-60f) && (q.den <= 0x1p60f);
@@ -307,6 +317,12 @@ RTG_HD RayQ make_query(V3 o, V3 d) {
   // y is used only when q.fast (quot, quot_k<true>); den is then in
   // [2^-60, 2^60], inside rcp_fast's range, so no range check is needed.
   q.y = rcp_fast(q.den);
+}
+
+RTG_HD RayQ make_query(V3 o, V3 d) {
+  float a;
+  RayQ q = query_head(o, d, a);
+  query_rest(q, a);
   return q;
 }
 
@@ -417,6 +433,38 @@ RTG_HD float ray_sphere_k(const RayQ& q, V3 c, float r2, bool& res) {
     if (u1 > 1.0e-5f) { if (u1 < sm) { sm = u1; res = true; } }
   }
   return sm;
+}
+
+// ray_sphere_k in two halves, for a loop that folds a lane condition of its
+// own into the radicand branch (closest_enter_fused): the reference's b and
+// radicand, then the roots of a radicand >= 0.  The same operations.
+RTG_HD float ray_radicand(const RayQ& q, V3 c, float r2, float& b) {
+  const V3 disp = vsub(q.o, c);
+  b = 2.0f * vdot(q.d, disp);
+  const float cc = vdot(disp, disp) - r2;
+  return (b * b) - (q.a4 * cc);
+}
+template <bool kFast>
+RTG_HD float ray_roots_k(const RayQ& q, float b, float radicand, bool& res) {
+  const float root = rtg_sqrtf(radicand);
+  const float u0 = quot_k<kFast>(-b + root, q);
+  const float u1 = quot_k<kFast>(-b - root, q);
+  float sm = 10000.f;
+  res = false;
+  if (u0 > 1.0e-5f) { if (u0 < sm) { sm = u0; res = true; } }
+  if (u1 > 1.0e-5f) { if (u1 < sm) { sm = u1; res = true; } }
+  return sm;
+}
+
+// A wave-uniform index whose value range the compiler does not see: a table
+// offset computed from it stays a 32-bit SGPR offset of the scalar load (one
+// shift) where a known-small index is widened into a 64-bit address (shift,
+// add, add with carry).
+RTG_HD unsigned opaque_index(unsigned i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+s"(i));
+#endif
+  return i;
 }
 
 // Closest hit, raytracer.h:145-194 (first index wins ties; minT starts 1000).
@@ -605,6 +653,9 @@ RTG_HD bool query_blocked(const Scene& sc, V3 o, V3 d, float gap);
 template <class Scene>
 RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, int hit = -1,
                         V3 hc = V3{}, float hr2 = 0.f);
+template <class Scene>
+RTG_HD int closest_sel_lazy(const Scene& sc, RayQ& q, float a, uint64_t sel, float& tOut,
+                            int skip);
 template <class Scene>
 RTG_HD bool blocked_cap(const Scene& sc, const RayQ& q, float gap, unsigned l, int h,
                         unsigned cell);
@@ -1002,7 +1053,8 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
       const int tier = sc.all(cu >= kConeCos[0]) ? 0 : sc.all(cu >= kConeCos[1]) ? 1 : -1;
       if (tier >= 0) {
         uint64_t cm = sc.cone_union(originH, (unsigned)tier, (unsigned)cone_cell(U));
-        const RayQ q = make_query(o, d);
+        float qa;
+        RayQ q = query_head(o, d, qa);
         int skip = -1;
         {
           // the origin sphere (in every cone mask of its own): a ray leaving
@@ -1019,8 +1071,7 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
         }
         sc.count(kCntConeQ, 1);
         sc.count(kCntConeSel, __builtin_popcountll(cm));
-        sc.count(kUQuery, 1);
-        hit = closest_sel(sc, q, cm, t, skip);
+        hit = closest_sel_lazy(sc, q, qa, cm, t, skip);
       } else {  // masked scenes only: a query site of its own
         sc.count(kCntFullQ, 1);
         hit = query_closest<2>(sc, o, d, t);
@@ -2057,8 +2108,8 @@ RTG_HD bool blocked_sel_fused(const Scene& sc, const RayQ& q, float gap, uint64_
 template <class Scene>
 RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, int hit,
                         V3 hc, float hr2) {
-  sc.count(kUQuery, 1);
-  const RayQ q = make_query(o, d);
+  float a;
+  RayQ q = query_head(o, d, a);
   if (sc.fuse & kFuseShadow) {
     // The hit sphere itself (every shadow mask's own sphere): no_root on the
     // reference's own b and cc for it (ray_sphere's operations on the same
@@ -2075,9 +2126,20 @@ RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, in
       const int h0 = sc.first_lane_i(hit);
       if (sc.all(skip == h0)) sel &= ~(1ull << h0);
     }
+    // Nothing left to test (the mask held the hit sphere alone): no sphere can
+    // block, and the rest of the query is never read.
+    if (sel == 0) {
+      sc.count(kUQueryHead, 1);
+      sc.count(kUDiagShdEmpty, 1);
+      return false;
+    }
+    sc.count(kUQuery, 1);
+    query_rest(q, a);
     if (sc.all(q.fast)) return blocked_sel_fused<true>(sc, q, gap, sel, skip);
     return blocked_sel_fused<false>(sc, q, gap, sel, skip);
   }
+  sc.count(kUQuery, 1);
+  query_rest(q, a);
   (void)hit; (void)hc; (void)hr2;
   for (unsigned base = 0; base < 64u; base += 32u) {
     const unsigned u = (unsigned)(sel >> base);
@@ -2133,21 +2195,35 @@ RTG_HD int closest_enter_fused(const Scene& sc, const RayQ& q, int h, float& tOu
   tOut = 1000.f;
   if (!sc.all(ok)) return -1;
   uint64_t own;
-  const uint64_t u = sc.overlap_union(h, own);
+  uint64_t u = sc.overlap_union(h, own);
   own &= ~(1ull << h);
+  {
+    // sphere h is in its own mask and was tested above: a wave whose lanes
+    // all entered one sphere drops it from the loop instead of walking it
+    // for nobody
+    const int h0 = sc.first_lane_i(h);
+    if (sc.all(h == h0)) u &= ~(1ull << h0);
+  }
   float minT = th;
   int best = h;
   for (uint64_t m = u; m;) {  // wave-uniform
-    const unsigned j = (unsigned)__builtin_ctzll(m);
+    const unsigned j = opaque_index((unsigned)__builtin_ctzll(m));
     m &= ~(1ull << j);
     sc.count(kUEnterIter, 1);
     float rj2;
     const V3 cj = sc.sphere(j, rj2);
-    if ((own >> j) & 1ull) {
+    // One divergent region per sphere (blocked_sel_fused): the lane's own-mask
+    // bit and the reference's radicand test combined without short-circuit,
+    // and the lexicographic update as selects.
+    float b;
+    const float radicand = ray_radicand(q, cj, rj2, b);
+    if ((((own >> j) & 1ull) != 0ull) & (radicand >= 0.0f)) {
       sc.count(kUEnterExact, 1);
       bool rj;
-      const float t = ray_sphere_k<kFast>(q, cj, rj2, rj);
-      if (rj && (t < minT || (t == minT && (int)j < best))) { minT = t; best = (int)j; }
+      const float t = ray_roots_k<kFast>(q, b, radicand, rj);
+      const bool take = rj & ((t < minT) | ((t == minT) & ((int)j < best)));
+      minT = take ? t : minT;
+      best = take ? (int)j : best;
     }
   }
   tOut = minT;
@@ -2250,6 +2326,24 @@ RTG_HD int closest_sel(const Scene& sc, const RayQ& q, uint64_t sel, float& tOut
   }
   tOut = minT;
   return best;
+}
+
+// closest_sel for a query that so far is its head only (query_head; a = d.d):
+// the rest is built when `sel` still holds a sphere; an empty `sel` (the cone
+// mask held the origin sphere alone, and the wave dropped it) is a miss, which
+// is closest_sel's own answer for no sphere.
+template <class Scene>
+RTG_HD int closest_sel_lazy(const Scene& sc, RayQ& q, float a, uint64_t sel, float& tOut,
+                            int skip) {
+  if (sel == 0) {
+    sc.count(kUQueryHead, 1);
+    sc.count(kUDiagConeEmpty, 1);
+    tOut = 1000.f;
+    return -1;
+  }
+  sc.count(kUQuery, 1);
+  query_rest(q, a);
+  return closest_sel(sc, q, sel, tOut, skip);
 }
 
 // Closest hit restricted to a wave-uniform subset `sel` of spheres 0..63

@@ -101,6 +101,7 @@ UNIT_NAMES = [
     "U.push", "U.descend", "U.unwind", "U.sample", "U.bvhPass",
     "U.capIter", "U.ovIter", "D.shdSame", "D.enterAll", "D.enterSame", "D.contSame",
     "U.lightDir", "D.insig", "D.insigAll", "U.wave",
+    "U.queryHead", "D.shdEmpty", "D.coneEmpty",
 ]
 
 

@@ -26,6 +26,8 @@ UNIT_COST = {
     # make_query: a = d.d (5), 4a, 2a, a(1-K), a(1-K_B) (4), range test (3),
     # 1/2a = rcp_fast (4)
     "U.query": 16,
+    # query_head alone (a query whose selection turned out empty): a = d.d (5), 4a
+    "U.queryHead": 6,
     # closest_hit_sel_fused: bp = 2 d.c (6), bp^2 - 4a oc (3), >= 0 (1)
     "U.primIter": 10,
     # its root test: sqrt_rn (12), two quotients (2 x (1 + 5)), accept tests and
@@ -42,10 +44,12 @@ UNIT_COST = {
     "U.shdExact": 62,
     # sphere h's ray_sphere_k (51), exit point (9), two guard tests (10 + 7)
     "U.enterHead": 77,
-    # the lane's own-mask bit test
-    "U.enterIter": 3,
-    # ray_sphere_k (51) + lexicographic (t, index) update (7)
-    "U.enterExact": 58,
+    # the lane's own-mask bit test (3) and the sphere's radicand, ahead of the
+    # one branch: p (3), b (6), cc (6), radicand (3), test (1)
+    "U.enterIter": 22,
+    # the roots (sqrt_rn 12, quotients 12, accept 8) + lexicographic (t, index)
+    # update (7)
+    "U.enterExact": 39,
     # candidate_mask: 4 x (pass1_rad 11 + sign shift 1)
     "U.fullGroup": 48,
     # ray_sphere with the per-quotient range select (55) + update (4)
@@ -125,7 +129,10 @@ UNIT_COST.update({
     "U.shdIter": 13.54,
     "U.shdExact": 57.52,
     "U.enterHead": 81.57,
-    "U.enterIter": 2.97,
+    # (the radicand moved from enterExact into enterIter after the fit: its 19
+    # source slots are added to enterIter's fitted 2.97 by hand; enterExact's fit
+    # already priced the roots alone)
+    "U.enterIter": 21.97,
     "U.enterExact": 39.09,
     "U.fullGroup": 50.98,
     "U.fullExact": 81.25,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/asm_mix.py ASM [VARIANT] [BVH] [LIST] [MASKS] — static instruction mix of one
-trace_samples_kernel instantiation in a `make asm` listing (build/rtg_trace_sS.s):
+trace_samples_kernel instantiation in a `make asm` listing (build/rtg_trace_sS.s;
+VARIANT `masked`: trace_samples_kernel_masked, the masked scenes' default kernel):
 instruction classes, f64 opcodes, scratch accesses and the register/occupancy
 summary the compiler prints after the function."""
 import collections
@@ -24,6 +25,8 @@ def main():
     s = re.search(r"_ZN3rtg20trace_samples_kernelILi(\d+)E", text).group(1)
     sym = "_ZN3rtg20trace_samples_kernelILi%sELi%sELb%sELb%sELb%sEEEvNS_10KernelArgsE" % (
         s, variant, bvh, lst, masks)
+    if variant == "masked":  # the masked-scene kernel is a function of its own
+        sym = "_ZN3rtg27trace_samples_kernel_maskedILi%sEEEvNS_10KernelArgsE" % s
     body, tail = kernel_body(text, sym)
     ops = [l.split()[0] for l in body.split("\n")
            if l.startswith("\t") and l.strip() and not l.strip().startswith((".", ";"))]
@@ -52,7 +55,7 @@ def main():
     print(sym)
     print("instructions", len(ops), dict(cls))
     print("f64", dict(f64.most_common()))
-    for k in ("NumVgprs", "NumAgprs", "NumSgprs", "ScratchSize", "Occupancy"):
+    for k in ("NumVgprs", "NumAgprs", "TotalNumSgprs", "ScratchSize", "Occupancy"):
         mm = re.search(r"; %s: (\d+)" % k, tail)
         print(k, mm and mm.group(1))
 
