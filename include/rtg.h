@@ -26,6 +26,8 @@
  *     raytracer.h:410-636
  *   the camera of main.cpp:384-436, moved to a pose   rtg_camera_look_at, rtg_camera_rays[_device|_host],
  *     (fixed at 0 looking down -z in the reference)    rtg_render_camera[_device|_host]
+ *   (hemisphere visibility of a hit point: the caller's  rtg_ao[_device|_host],
+ *     loop over hasClearLineOfSight in the reference)    rtg_ao_segments[_device|_host]
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
  *   output_device_info  device_info.cpp:30             rtg_device_info
  *   parseArguments --list/--device  device_picker.h:70 rtg_device_count / device index args
@@ -535,6 +537,96 @@ int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg
                            unsigned lgtNum, const rtg_camera* cam, unsigned width,
                            unsigned height, float zoom, float aliasFactor, int stackSize,
                            int semantics, rtg_vec* dstHost, int walk, int nthreads);
+
+/* ---- ambient occlusion: hemisphere visibility per hit point ----
+ * Hit points go in, one count of unoccluded probes per point comes out: no
+ * segment buffer, no sort and no fold on the caller's side.  The call takes n
+ * rtg_hit records exactly as rtg_intersect* writes them, and a table of nDirs
+ * local directions `dirs`, samples <= nDirs <= RTG_AO_MAX_DIRS, in the frame
+ * whose z axis is the normal.  The directions are used as given: they are not
+ * normalised, and any length or sign is legal.  The caller owns the table (a
+ * device pointer in the device calls), so no sin or cos is evaluated inside
+ * the defined arithmetic.
+ *
+ * PROBE k of point i (P = point, N = normal), all in float with no contraction
+ * and in this operand order:
+ *   frame    s = copysignf(1, N.z);  a = -1.f / (s + N.z);  b = (N.x * N.y) * a
+ *            T1 = (1.f + s * ((N.x * N.x) * a), s * b, -(s * N.x))
+ *            T2 = (b, s + (N.y * N.y) * a, -N.y)
+ *   window   s_i = (flags & RTG_AO_JITTER) ? mix32(seed + (unsigned)i) % nDirs : 0
+ *            mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ *                      x *= 0x846ca68b; x ^= x >> 16   (32-bit, wrapping)
+ *            j = s_i + k, minus nDirs if j >= nDirs;  l = dirs[j]
+ *   world    per component q: w.q = (l.x * T1.q + l.y * T2.q) + l.z * N.q
+ *            (the posed camera's form)
+ *   segment  a.q = P.q + bias * N.q;  b.q = a.q + radius * w.q
+ * A record with id < 0 (no point) has K all-zero segments.
+ *
+ * out[i] (an unsigned short) is the number of k in 0..K-1 for which
+ * hasClearLineOfSight(a, b) holds, exactly as rtg_visible defines it (a
+ * segment with a == b is visible by its rule): the count of UNOCCLUDED
+ * probes, out[i] / (float)K the usual AO term.  A record with id < 0 gets K
+ * and makes no query.  NaN, infinite and degenerate inputs follow the
+ * arithmetic and the comparisons as written.  The result does not depend on
+ * lights, stackSize or rtg_context_set_semantics.
+ *
+ * rtg_ao_segments* write the n * K segments, point-major (segment k of point
+ * i at i * K + k): the generator that pins the definition.  NaN words are
+ * written as 0xFFC00000, as every record's.  rtg_ao* is, word for word, the
+ * per-point sum of rtg_visible_host(walk 0) over them.
+ *
+ * n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID with a message, before
+ * any GPU call, for a null pointer, samples outside 1..RTG_AO_MAX_SAMPLES,
+ * nDirs outside samples..RTG_AO_MAX_DIRS, an unknown flag, n > 2^32 - 1, an
+ * n * K that overflows size_t (the segments), more than 2^31-1 workgroups (64
+ * lanes each) or, for the fused call only, a context without a scene.
+ *
+ * Out of scope: an _indexed form, bent normals, distance falloff, a
+ * G-buffer-record input, multi-GPU batches. */
+#define RTG_AO_MAX_SAMPLES 1024
+#define RTG_AO_MAX_DIRS    65536
+#define RTG_AO_JITTER 1            /* flags: per-point window into the direction table */
+typedef struct rtg_ao_params {
+  unsigned samples;  /* K probes per point, 1..RTG_AO_MAX_SAMPLES */
+  float radius;      /* probe length factor, used as given */
+  float bias;        /* start offset along the normal, used as given */
+  unsigned seed;     /* RTG_AO_JITTER only */
+  unsigned flags;    /* RTG_AO_* bits; an unknown bit is RTG_ERR_INVALID */
+} rtg_ao_params;
+/* A convenience, host only: the cosine-weighted golden-angle set, u = (k +
+ * 0.5) / nDirs, phi = 2 pi frac(k * 0.6180339887498949), direction k =
+ * (sqrt(u) cos phi, sqrt(u) sin phi, sqrt(1 - u)), computed in double and
+ * rounded to float.  Its bits are NOT part of the contract (libm's sin and
+ * cos are involved): a caller who needs the same counts everywhere keeps the
+ * table it used.  nDirs outside 1..RTG_AO_MAX_DIRS is RTG_ERR_INVALID. */
+int rtg_ao_directions(unsigned nDirs, rtg_vec* out);
+/* The n * K probe segments on the host.  nthreads <= 0: 1. */
+int rtg_ao_segments_host(const rtg_hit* hits, size_t n, const rtg_ao_params* params,
+                         const rtg_vec* dirs, unsigned nDirs, rtg_segment* segsHost,
+                         int nthreads);
+/* The same into device memory, asynchronously on `stream`.  The context names
+ * the device; it needs no scene.  `params` is host memory in every call, read
+ * before the call returns. */
+int rtg_ao_segments_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
+                           const rtg_ao_params* params, const rtg_vec* dirsDevice,
+                           unsigned nDirs, rtg_segment* segsDevice, void* stream);
+/* The fused kernel: n counts into outDevice, asynchronously on `stream`.
+ * Allocates nothing, takes none of the context's render scratch and may be
+ * mixed with every other call on the context. */
+int rtg_ao_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
+                  const rtg_ao_params* params, const rtg_vec* dirsDevice, unsigned nDirs,
+                  unsigned short* outDevice, void* stream);
+/* One-shot: uploads the scene, the hits and the table, runs on `device`,
+ * downloads n counts. */
+int rtg_ao(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_hit* hits,
+           size_t n, const rtg_ao_params* params, const rtg_vec* dirs, unsigned nDirs,
+           unsigned short* outHost);
+/* The same on the host, no GPU call.  walk 0: plain loops over every probe
+ * and sphere (the yardstick).  walk 1: the kernel's own path over the packed
+ * tables, as rtg_visible_host.  nthreads <= 0: 1. */
+int rtg_ao_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_hit* hits, size_t n,
+                const rtg_ao_params* params, const rtg_vec* dirs, unsigned nDirs,
+                unsigned short* outHost, int walk, int nthreads);
 
 /* Semantics of a context's renders.  RTG_SEMANTICS_CPU (default) is the
  * reference CPU path (raytracer.h), bit for bit.  RTG_SEMANTICS_OPENCL is the

@@ -80,7 +80,38 @@ RTG_HD int ray_closest(const Scene& sc, const RayBox& box, V3 o, V3 d, bool acti
   }
 }
 
-// hasClearLineOfSight's blocker search for the ray (o, d) with gap |b - a|^2.
+// A segment's shadow ray (raytracer.h:279-286): gap before normalising.
+RTG_HD V3 segment_ray(V3 a, V3 b, float& gap) {
+  const V3 dist = vsub(b, a);
+  gap = vdot(dist, dist);
+  return vnorm(dist);
+}
+
+// hasClearLineOfSight's blocker search for the ray (o, d) with gap |b - a|^2,
+// for a caller that asks many rays from one origin (the K probes of an
+// ambient-occlusion point, rtg_ao.hip): delta and oddOrigin are ray_delta(box,
+// o, oddOrigin), taken once per origin (a scene without a BVH reads neither).
+// Nothing else of a query depends on the origin alone: make_query's origin
+// half is a copy of o.
+template <bool kBvh, class Scene>
+RTG_HD bool ray_blocked(const Scene& sc, V3 o, V3 d, float gap, bool active, float delta,
+                        bool oddOrigin) {
+  if constexpr (kBvh) {
+    const RayQ q = make_query(o, d);
+    const bool odd = active && (oddOrigin || !q.fast);
+    bool blk = blocked_bvh<true>(sc, q, gap, delta, active && !odd);
+    if (sc.any(odd)) {
+      if (odd) blk = blocked(sc, o, d, gap);
+    }
+    return blk;
+  } else {
+    if (!active) return false;
+    if (sc.n4 <= 64) return blocked64(sc, o, d, gap);
+    return blocked(sc, o, d, gap);
+  }
+}
+
+// The same for one ray: the delta of its own origin.
 template <bool kBvh, class Scene>
 RTG_HD bool ray_blocked(const Scene& sc, const RayBox& box, V3 o, V3 d, float gap, bool active) {
   if constexpr (kBvh) {

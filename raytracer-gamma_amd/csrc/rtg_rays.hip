@@ -13,9 +13,11 @@
 // (two more instantiations each, in this one translation unit), so that the
 // un-indexed kernels keep the code they had (DESIGN).
 //
-// The two queries themselves (ray_delta, ray_closest, ray_blocked) are in
-// rtg_rays.h, shared with the batch ray tracer (rtg_raytrace.hip), which asks
-// them at every level of a ray's tree; the argument below is theirs.
+// The two queries themselves (ray_delta, ray_closest, ray_blocked) and a
+// segment's shadow ray (segment_ray) are in rtg_rays.h, shared with the batch
+// ray tracer (rtg_raytrace.hip), which asks them at every level of a ray's
+// tree, and with the ambient occlusion (rtg_ao.hip); the argument below is
+// theirs.
 //
 // Query per scene kind, all with the device functions of rtg_trace.h:
 //   BVH scene (SceneTables::bvhNodes)  the render kernels' walk, widened
@@ -147,13 +149,6 @@ RTG_HD void hit_record(V3 o, V3 d, int id, float t, V3 c, unsigned* w) {
   w[5] = nan_bits(N.x);
   w[6] = nan_bits(N.y);
   w[7] = nan_bits(N.z);
-}
-
-// A segment's shadow ray (raytracer.h:279-286): gap before normalising.
-RTG_HD V3 segment_ray(V3 a, V3 b, float& gap) {
-  const V3 dist = vsub(b, a);
-  gap = vdot(dist, dist);
-  return vnorm(dist);
 }
 
 // ---- host forms ----

@@ -53,6 +53,11 @@ static void usage() {
   printf("                           --semantics): 12-byte rtg_vec records\n");
   printf("      --camera     POSE    Render from a posed camera: ex,ey,ez,tx,ty,tz[,ux,uy,uz] (eye,\n");
   printf("                           target, up; up defaults to 0,1,0), rtg_camera_look_at\n");
+  printf("      --ao         SPEC    Also write the frame's ambient occlusion: K,radius[,bias[,seed]]\n");
+  printf("                           (K probes of rtg_ao_directions(K) per primary hit at aa 1, from\n");
+  printf("                           --camera or the identity pose; bias defaults to 0.001; a seed\n");
+  printf("                           turns RTG_AO_JITTER on); needs --ao-out\n");
+  printf("      --ao-out     FILE    The 8-bit binary PGM of (255 * count) / K per pixel\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -74,7 +79,9 @@ int main(int argc, char** argv) {
   unsigned device = 0, W = 800, H = 600, nSph = 3, nLgt = 2, depth = 5, repeat = 1;
   unsigned long long seed = 42;
   float aa = 3.f, zoom = -4.f;
-  std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut, radianceOut;
+  std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut, radianceOut, aoOut;
+  bool ao = false;
+  rtg_ao_params aoParams = {0, 0.f, 1.0e-3f, 0, 0};
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   bool posed = false;
@@ -145,6 +152,18 @@ int main(int argc, char** argv) {
       const rtg_vec eye = {v[0], v[1], v[2]}, target = {v[3], v[4], v[5]}, up = {v[6], v[7], v[8]};
       check(rtg_camera_look_at(&eye, &target, &up, &camera), "rtg_camera_look_at");
       posed = true;
+    } else if (!strcmp(a, "--ao")) {
+      char tail = 0;
+      const int k = sscanf(need(a), "%u,%f,%f,%u%c", &aoParams.samples, &aoParams.radius,
+                           &aoParams.bias, &aoParams.seed, &tail);
+      if (k < 2 || k > 4 || aoParams.samples < 1 || aoParams.samples > RTG_AO_MAX_SAMPLES) {
+        printf("Invalid ao (K,radius[,bias[,seed]], K in 1..%d)\n", RTG_AO_MAX_SAMPLES);
+        return 1;
+      }
+      if (k == 4) aoParams.flags = RTG_AO_JITTER;
+      ao = true;
+    } else if (!strcmp(a, "--ao-out")) {
+      aoOut = need(a);
     } else if (!strcmp(a, "--scene")) {
       sceneIn = need(a);
     } else if (!strcmp(a, "--save-scene")) {
@@ -173,6 +192,11 @@ int main(int argc, char** argv) {
   }
   if (raysIn.empty() && !radianceOut.empty()) {
     printf("--radiance needs --rays\n");
+    return 1;
+  }
+
+  if (ao == aoOut.empty()) {
+    printf("--ao and --ao-out go together\n");
     return 1;
   }
 
@@ -278,6 +302,52 @@ int main(int argc, char** argv) {
     }
     printf("Wrote %s (%zu G-buffer records of %zu bytes)\n", gbufOut.c_str(), gbuf.size(),
            sizeof(rtg_gbuf_px));
+  }
+
+  if (ao) {  // pose -> primary rays -> hits -> counts, all on the device; only the counts come back
+    const size_t n = (size_t)W * H;
+    const unsigned K = aoParams.samples;
+    if (!posed) rtg_camera_identity(&camera);
+    std::vector<rtg_vec> table(K);
+    check(rtg_ao_directions(K, table.data()), "rtg_ao_directions");
+    rtg_context* ctx = nullptr;
+    check(rtg_context_create((int)device, &ctx), "rtg_context_create");
+    check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
+          "rtg_context_set_scene");
+    rtg_ray* dr = nullptr;
+    rtg_hit* dh = nullptr;
+    rtg_vec* dd = nullptr;
+    unsigned short* dc = nullptr;
+    if (hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
+        hipMalloc(&dh, n * sizeof(rtg_hit)) != hipSuccess ||
+        hipMalloc(&dd, K * sizeof(rtg_vec)) != hipSuccess ||
+        hipMalloc(&dc, n * sizeof(unsigned short)) != hipSuccess)
+      check(RTG_ERR_NOMEM, "hipMalloc");
+    if (hipMemcpy(dd, table.data(), K * sizeof(rtg_vec), hipMemcpyHostToDevice) != hipSuccess)
+      check(RTG_ERR_HIP, "upload");
+    check(rtg_camera_rays_device(ctx, &camera, W, H, zoom, 1.f, dr, nullptr),
+          "rtg_camera_rays_device");
+    check(rtg_intersect_device(ctx, dr, n, dh, nullptr), "rtg_intersect_device");
+    check(rtg_ao_device(ctx, dh, n, &aoParams, dd, K, dc, nullptr), "rtg_ao_device");
+    std::vector<unsigned short> counts(n);
+    if (hipMemcpy(counts.data(), dc, n * sizeof(unsigned short), hipMemcpyDeviceToHost) !=
+        hipSuccess)
+      check(RTG_ERR_HIP, "readback");
+    (void)hipFree(dr);
+    (void)hipFree(dh);
+    (void)hipFree(dd);
+    (void)hipFree(dc);
+    rtg_context_destroy(ctx);
+    std::vector<unsigned char> grey(n);
+    for (size_t k = 0; k < n; ++k) grey[k] = (unsigned char)((255u * counts[k]) / K);
+    FILE* f = fopen(aoOut.c_str(), "wb");
+    if (!f || fprintf(f, "P5\n%u %u\n255\n", W, H) < 0 ||
+        fwrite(grey.data(), 1, n, f) != n || fclose(f) != 0) {
+      fprintf(stderr, "Error: can't write %s\n", aoOut.c_str());
+      exit(EXIT_FAILURE);
+    }
+    printf("Wrote %s (%ux%u, %u probes of length %.8g per primary hit)\n", aoOut.c_str(), W, H, K,
+           (double)aoParams.radius);
   }
 
   if (!raysIn.empty()) {  // records as they lie in memory, like the G-buffer's

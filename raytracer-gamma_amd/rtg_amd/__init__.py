@@ -57,6 +57,11 @@ assert RAY_DTYPE.itemsize == 24 and SEGMENT_DTYPE.itemsize == 24 and HIT_DTYPE.i
 CAMERA_DTYPE = np.dtype([("eye", "<f4", 3), ("right", "<f4", 3), ("up", "<f4", 3),
                          ("back", "<f4", 3)])
 assert CAMERA_DTYPE.itemsize == 48
+# rtg_ao_params (include/rtg.h): ambient occlusion
+AO_PARAMS_DTYPE = np.dtype([("samples", "<u4"), ("radius", "<f4"), ("bias", "<f4"),
+                            ("seed", "<u4"), ("flags", "<u4")])
+assert AO_PARAMS_DTYPE.itemsize == 20
+AO_MAX_SAMPLES, AO_MAX_DIRS, AO_JITTER = 1024, 65536, 1  # RTG_AO_*
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -84,6 +89,8 @@ EXPORTED = [
     "rtg_camera_identity", "rtg_camera_look_at", "rtg_camera_sample_count",
     "rtg_camera_rays_host", "rtg_camera_rays_device",
     "rtg_render_camera_device", "rtg_render_camera", "rtg_render_camera_host",
+    "rtg_ao_directions", "rtg_ao_segments_host", "rtg_ao_segments_device", "rtg_ao_device",
+    "rtg_ao", "rtg_ao_host",
 ]
 
 
@@ -188,6 +195,12 @@ def lib() -> ctypes.CDLL:
         L.rtg_render_camera_device.argtypes = [vp, vp, u, u, f, f, i, vp, vp]
         L.rtg_render_camera.argtypes = [i, vp, u, vp, u, vp, u, u, f, f, i, vp]
         L.rtg_render_camera_host.argtypes = [vp, u, vp, u, vp, u, u, f, f, i, i, vp, i, i]
+        L.rtg_ao_directions.argtypes = [u, vp]
+        L.rtg_ao_segments_host.argtypes = [vp, sz, vp, vp, u, vp, i]
+        L.rtg_ao_segments_device.argtypes = [vp, vp, sz, vp, vp, u, vp, vp]
+        L.rtg_ao_device.argtypes = [vp, vp, sz, vp, vp, u, vp, vp]
+        L.rtg_ao.argtypes = [i, vp, u, vp, sz, vp, vp, u, vp]
+        L.rtg_ao_host.argtypes = [vp, u, vp, sz, vp, vp, u, vp, i, i]
 
         pu = ctypes.POINTER(u)
         L.rtg_scene_load.argtypes = [ctypes.c_char_p, vp, u, pu, vp, u, pu]
@@ -578,6 +591,70 @@ def render_camera_host(spheres, lights, cam, width: int, height: int, zoom: floa
     return out
 
 
+def ao_params(samples: int, radius: float, bias: float = 1e-3, seed: int = 0,
+              flags: int = 0) -> np.ndarray:
+    """One rtg_ao_params record (flags: AO_JITTER for a per-point window into the table)."""
+    p = np.zeros(1, AO_PARAMS_DTYPE)
+    p[0] = (samples, radius, bias, seed & 0xFFFFFFFF, flags)
+    return p
+
+
+def ao_directions(n_dirs: int) -> np.ndarray:
+    """The cosine-weighted golden-angle direction set (rtg_ao_directions): (n_dirs, 3)
+    float32 in the frame whose z axis is the normal.  A convenience; its bits
+    are not part of the contract."""
+    out = np.zeros((max(n_dirs, 1), 3), np.float32)
+    _check(lib().rtg_ao_directions(n_dirs, _ptr(out)), "rtg_ao_directions")
+    return out[:n_dirs]
+
+
+def _ao_args(hits, dirs, params):
+    """Hit records, direction table and params as contiguous arrays whose
+    pointers are never null (an empty batch is legal), and the two counts."""
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    p = np.ascontiguousarray(params, AO_PARAMS_DTYPE).reshape(1)
+    return (h if len(h) else np.zeros(1, HIT_DTYPE)), len(h), \
+        (d if len(d) else np.zeros((1, 3), np.float32)), len(d), p
+
+
+def ao_segments_host(hits, dirs, params, threads: int = 1) -> np.ndarray:
+    """The probe segments of every hit point on the host (rtg_ao_segments_host):
+    (n * K, 6) float32 (a, b), point-major; params from ao_params()."""
+    h, n, d, nd, p = _ao_args(hits, dirs, params)
+    k = int(p["samples"][0])
+    out = np.empty((n * k, 6), np.float32)
+    dst = out if out.size else np.zeros((1, 6), np.float32)
+    _check(lib().rtg_ao_segments_host(_ptr(h), n, _ptr(p), _ptr(d), nd, _ptr(dst), threads),
+           "rtg_ao_segments_host")
+    return out
+
+
+def ao_host(spheres, hits, dirs, params, walk: int = 0, threads: int = 1) -> np.ndarray:
+    """Ambient occlusion on the host (rtg_ao_host; no GPU needed): per hit point
+    the uint16 count of its K probes with a clear line of sight.  walk 0: plain
+    loops; walk 1: the kernel's own path over the packed tables."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    h, n, d, nd, p = _ao_args(hits, dirs, params)
+    out = np.empty(n, np.uint16)
+    dst = out if n else np.zeros(1, np.uint16)
+    _check(lib().rtg_ao_host(_ptr(spheres), len(spheres), _ptr(h), n, _ptr(p), _ptr(d), nd,
+                             _ptr(dst), walk, threads), "rtg_ao_host")
+    return out
+
+
+def ao(spheres, hits, dirs, params, device: int = 0) -> np.ndarray:
+    """The same on the GPU, one-shot (rtg_ao): HIT_DTYPE records as intersect()
+    returns them in, uint16 counts out; count / K is the usual AO term."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    h, n, d, nd, p = _ao_args(hits, dirs, params)
+    out = np.empty(n, np.uint16)
+    dst = out if n else np.zeros(1, np.uint16)
+    _check(lib().rtg_ao(device, _ptr(spheres), len(spheres), _ptr(h), n, _ptr(p), _ptr(d), nd,
+                        _ptr(dst)), "rtg_ao")
+    return out
+
+
 class MultiContext:
     """Persistent multi-device handle (rtg_multi_*): RCCL communicator, contexts,
     streams and buffers kept across frames."""
@@ -842,6 +919,31 @@ class Context:
                                             float(alias_factor), ctypes.c_void_p(dst_ptr),
                                             ctypes.c_void_p(stream) if stream else None),
                "rtg_camera_rays_device")
+
+    def ao_device(self, hits_ptr: int, n: int, params, dirs_ptr: int, n_dirs: int, dst_ptr: int,
+                  stream: int = 0):
+        """Ambient occlusion of n hit points at hits_ptr (device, 32-byte HIT_DTYPE
+        records as intersect_device writes them) with the direction table at
+        dirs_ptr (device, an (n_dirs, 3) float32 tensor) into dst_ptr (device, n
+        uint16 counts of unoccluded probes), asynchronously on `stream`
+        (rtg_ao_device; params from ao_params())."""
+        p = np.ascontiguousarray(params, AO_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_ao_device(self._h, ctypes.c_void_p(hits_ptr), n, _ptr(p),
+                                   ctypes.c_void_p(dirs_ptr), n_dirs, ctypes.c_void_p(dst_ptr),
+                                   ctypes.c_void_p(stream) if stream else None),
+               "rtg_ao_device")
+
+    def ao_segments_device(self, hits_ptr: int, n: int, params, dirs_ptr: int, n_dirs: int,
+                           dst_ptr: int, stream: int = 0):
+        """The n * K probe segments of those points into dst_ptr (device, 24-byte
+        SEGMENT_DTYPE records, point-major), asynchronously on `stream`
+        (rtg_ao_segments_device; the context needs no scene)."""
+        p = np.ascontiguousarray(params, AO_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_ao_segments_device(self._h, ctypes.c_void_p(hits_ptr), n, _ptr(p),
+                                            ctypes.c_void_p(dirs_ptr), n_dirs,
+                                            ctypes.c_void_p(dst_ptr),
+                                            ctypes.c_void_p(stream) if stream else None),
+               "rtg_ao_segments_device")
 
     def render_rows_device(self, width, height, rows_ptr: int, n_rows: int, dst_ptr: int,
                            zoom=-4.0, alias_factor=3.0, stack_size=6, stream: int = 0):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
-                       [--only-order] [--order-alt-json FILE ...]
+                       [--only-order] [--only-ao] [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
 with the scene and the rays resident, on three batches of bench.py's frames:
@@ -53,6 +53,11 @@ sum must be below the plain shuffled launch by more than either's min-max
 spread.  --only-order runs these rows alone (--order-label NAME is recorded:
 the key layout or bit counts of the library under RTG_LIB / RTG_ORDER_LAYOUT);
 --order-alt-json FILE puts such runs of other layouts next to this one's.
+
+Ambient occlusion (csrc/rtg_ao.hip) gets rows under "ao" (ao_rows below): the
+fused call on the frame's primary hits next to the unfused path (segments,
+visible, a torch sum), with and without the ray order.  --only-ao runs these
+alone and keeps FILE's other sections.
 GPU only.
 """
 import argparse
@@ -246,6 +251,77 @@ def order_rows(args, n, rays, shuffled, stream):
     return out, ok
 
 
+def ao_rows(args, W, H, rays, stream):
+    """Ambient occlusion (csrc/rtg_ao.hip) of the frame's 8.3 M aa = 1 primary
+    hits on C3 and C5: K = 16 probes of rtg_ao_directions(16), radius 2.5 x the
+    scene's largest |radius|, bias 1e-3, jitter off and on.  Round by round in
+    one process: the fused call, and the pieces of the unfused path on the same
+    hits: rtg_ao_segments_device (24 K bytes per point), rtg_visible_device over
+    the n K segments, a torch sum of K bytes per point, and for the sorted form
+    rtg_ray_order_device of the segments plus the indexed launch.  The unfused
+    rows are the per-round sums of their pieces.  Reported, not gated: whether
+    the fused call is slower than the best unfused row by more than that row's
+    own min-max spread.  Gated: the fused counts are the folded ones."""
+    n, K = W * H, 16
+    table = torch.from_numpy(R.ao_directions(K)).cuda()
+    hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+    segs = torch.empty((n * K, 6), dtype=torch.float32, device="cuda")
+    vis = torch.empty((n * K,), dtype=torch.uint8, device="cuda")
+    vis_idx = torch.empty((n * K,), dtype=torch.uint8, device="cuda")
+    cnt = torch.empty((n,), dtype=torch.int16, device="cuda")
+    nbytes = R.ray_order_scratch(n * K)
+    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device="cuda")
+    order = torch.empty((n * K,), dtype=torch.int32, device="cuda")
+    out, ok = {"samples": K, "directions": K, "bias": 1e-3, "segment_bytes": n * K * 24,
+               "order_scratch_bytes": nbytes}, True
+    for name in ("c3", "c5"):
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        radius = float(F(2.5) * np.abs(sph["radius"]).max())
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream)
+        out[name] = {"radius": radius, "hit_points": int((hits[:, 0] >= 0).sum())}
+        for label, flags in (("plain", 0), ("jitter", R.AO_JITTER)):
+            p = R.ao_params(K, radius, 1e-3, 42, flags)
+            raw = []
+            fu, sg, vs, fo, so, vi = measure(
+                [lambda: ctx.ao_device(hits.data_ptr(), n, p, table.data_ptr(), K, cnt.data_ptr(),
+                                       stream),
+                 lambda: ctx.ao_segments_device(hits.data_ptr(), n, p, table.data_ptr(), K,
+                                                segs.data_ptr(), stream),
+                 lambda: ctx.visible_device(segs.data_ptr(), n * K, vis.data_ptr(), stream),
+                 lambda: vis.view(n, K).sum(1, dtype=torch.int32),
+                 lambda: ctx.ray_order(segs.data_ptr(), n * K, order.data_ptr(), scratch.data_ptr(),
+                                       nbytes, kind=R.ORDER_SEGMENTS, stream=stream),
+                 lambda: ctx.visible_device(segs.data_ptr(), n * K, vis_idx.data_ptr(), stream,
+                                            order=order.data_ptr())], args.rounds, raw=raw)
+            folded = vis.view(n, K).sum(1, dtype=torch.int32)
+            equal = bool((cnt.to(torch.int32) == folded).all()) and bool((vis == vis_idx).all())
+            ok = ok and equal
+            sums = {"unfused": [a + b + c for a, b, c in zip(raw[1], raw[2], raw[3])],
+                    "unfused_sorted": [a + b + c + d for a, b, c, d in
+                                       zip(raw[1], raw[4], raw[5], raw[3])]}
+            rows = {k: {"ms_median": round(float(np.median(v)), 5), "ms_min": round(min(v), 5),
+                        "ms_max": round(max(v), 5)} for k, v in sums.items()}
+            best = min(rows, key=lambda k: rows[k]["ms_median"])
+            spread = rows[best]["ms_max"] - rows[best]["ms_min"]
+            out[name][label] = {
+                "fused": fu, "segments": sg, "visible": vs, "fold": fo, "order": so,
+                "visible_indexed": vi, **rows, "best_unfused": best,
+                "best_unfused_over_fused": round(rows[best]["ms_median"] / fu["ms_median"], 3),
+                "fused_slower_than_best_unfused_by_more_than_its_spread":
+                    bool(fu["ms_median"] - rows[best]["ms_median"] > spread),
+                "Mprobes_per_s": round(n * K / (fu["ms_median"] * 1e-3) / 1e6, 1),
+                "blocked_share_of_hit_points": round(
+                    1.0 - float(cnt[hits[:, 0] >= 0].to(torch.float64).sum()) /
+                    (K * max(1, out[name]["hit_points"])), 4),
+                "fused_equals_folded_visible": equal}
+            print(f"ao {name} {label}: fused {fu['ms_median']} ms, {best} "
+                  f"{rows[best]['ms_median']} ms", file=sys.stderr, flush=True)
+        ctx.close()
+    return out, ok
+
+
 def finish(args, res, ok):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -263,6 +339,8 @@ def main():
     ap.add_argument("--commit", default="", help="recorded as the commit the numbers are of")
     ap.add_argument("--only-camera", action="store_true", help="the posed camera's rows alone")
     ap.add_argument("--only-order", action="store_true", help="the ray order's rows alone")
+    ap.add_argument("--only-ao", action="store_true",
+                    help="the ambient occlusion's rows alone, put into FILE next to what it holds")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
     ap.add_argument("--order-alt-json", default=[], action="append",
@@ -290,6 +368,14 @@ def main():
     if args.only_order:
         del hits, hits2, gb
         res["order"], ok = order_rows(args, n, rays, shuffled, stream)
+        finish(args, res, ok)
+
+    if args.only_ao:
+        del hits, hits2, gb, shuffled
+        if os.path.exists(args.out):  # the other sections stay as they were measured
+            with open(args.out) as f:
+                res = dict(json.load(f), ao_commit=args.commit)
+        res["ao"], ok = ao_rows(args, W, H, rays, stream)
         finish(args, res, ok)
 
     if args.only_camera:
@@ -370,7 +456,9 @@ def main():
         res["order"].setdefault("alternatives", {})[other["label"]] = other
     del shuffled
     res["camera"], cam_ok = camera_rows(args, W, H, rays, col, fb, stream)
-    ok = ok and cam_ok and order_ok
+    del col, fb
+    res["ao"], ao_ok = ao_rows(args, W, H, rays, stream)
+    ok = ok and cam_ok and order_ok and ao_ok
     if args.mapping_json:
         with open(args.mapping_json) as f:
             other = json.load(f)["camera"]
