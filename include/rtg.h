@@ -28,6 +28,10 @@
  *     (fixed at 0 looking down -z in the reference)    rtg_render_camera[_device|_host]
  *   (hemisphere visibility of a hit point: the caller's  rtg_ao[_device|_host],
  *     loop over hasClearLineOfSight in the reference)    rtg_ao_segments[_device|_host]
+ *   calculateMatte for a caller's own hit points       rtg_matte[_device|_host]
+ *     raytracer.h:313-367
+ *   primaryContainer for a caller's own points         rtg_contains[_device|_host]
+ *     raytracer.h:245-270
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
  *   output_device_info  device_info.cpp:30             rtg_device_info
  *   parseArguments --list/--device  device_picker.h:70 rtg_device_count / device index args
@@ -627,6 +631,87 @@ int rtg_ao(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_hit
 int rtg_ao_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_hit* hits, size_t n,
                 const rtg_ao_params* params, const rtg_vec* dirs, unsigned nDirs,
                 unsigned short* outHost, int walk, int nthreads);
+
+/* ---- direct light: calculateMatte per hit point ----
+ * Hit points go in, the direct (Lambert) light of the scene's lights at each
+ * point comes out, with a mask of the lights that reach it: lightmaps,
+ * irradiance probes and shadow masks for a caller's own shading in one launch,
+ * with no n x m segment buffer.  The call takes n rtg_hit records exactly as
+ * rtg_intersect* writes them; the lights are the context's (the one-shot and
+ * host forms take them as arguments).  It pairs with rtg_ao* on the same
+ * records.
+ *
+ * For a record with id >= 0, P = point and N = normal, all in float with no
+ * contraction and in this operand order (calculateMatte, raytracer.h:313-367):
+ *   sum = (0, 0, 0)
+ *   for l = 0 .. m-1, in order:
+ *     dist = L_l.pos - P                                   (per component)
+ *     gap  = (dist.x * dist.x + dist.y * dist.y) + dist.z * dist.z
+ *     dir  = (1.f / sqrt(gap)) * dist                      (vec.h:41)
+ *     incidence = (N.x * dir.x + N.y * dir.y) + N.z * dir.z
+ *     if hasClearLineOfSight(P, L_l.pos), rtg_visible's rule for the segment
+ *        (P, L_l.pos) word for word, and incidence > 0.f:
+ *          intensity = incidence / gap
+ *          sum.q = sum.q + intensity * L_l.col.q           (per component q)
+ *          bit l of the mask is set                        (l < 64 only)
+ *   out[i] = sum, NaN words written as 0xFFC00000;  lit[i] = the mask
+ * A record with id < 0 gets (0, 0, 0) and mask 0 and makes no query.  `id` is
+ * read for its sign only (an id >= sphNum is legal and is never used as an
+ * index) and `t` is not read.  The normal is used as given: it is not
+ * normalised, and a flipped or scaled normal is legal.  There is no bias: the
+ * reference starts its shadow ray at P and relies on raySphere's 1e-5 window,
+ * and so does this call.  NaN, infinite and degenerate inputs (P == L, a NaN
+ * or infinite light) follow the arithmetic and the comparisons as written.
+ * Lights from index 64 on add to the sum and set no bit.  The result does not
+ * depend on stackSize or rtg_context_set_semantics.  On a scene whose spheres
+ * are opaque, white and matte, rtg_raytrace* of a ray is rtg_matte* of its
+ * rtg_intersect* record.
+ *
+ * `lit` may be NULL: it exists for callers with their own BRDF, who need the
+ * per-light visibility and not the Lambert sum.
+ *
+ * n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID with a message, before
+ * any GPU call, for a null hit or output buffer, a context without a scene,
+ * n > 2^32 - 1, more than 2^31-1 workgroups (64 lanes each) or an unknown
+ * walk.
+ *
+ * Out of scope: lights other than the context's, an _indexed form, a
+ * per-light colour breakdown beyond the mask, gloss or specular terms, a
+ * generator of surface sample points (a caller's rays through rtg_intersect*
+ * give the records), multi-GPU batches. */
+/* The fused kernel: n sums into outDevice (12 B each) and, when litDevice is
+ * not NULL, n masks (8-byte aligned), asynchronously on `stream`.  Allocates
+ * nothing, takes none of the context's render scratch and may be mixed with
+ * every other call on the context. */
+int rtg_matte_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n, rtg_vec* outDevice,
+                     unsigned long long* litDevice, void* stream);
+/* One-shot: uploads the scene and the hits, runs on `device`, downloads the
+ * sums and (litHost not NULL) the masks. */
+int rtg_matte(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+              unsigned lgtNum, const rtg_hit* hits, size_t n, rtg_vec* outHost,
+              unsigned long long* litHost);
+/* The same on the host, no GPU call.  walk 0: plain loops over every light
+ * and sphere (the yardstick).  walk 1: the kernel's own path over the packed
+ * tables, as rtg_visible_host.  nthreads <= 0: 1. */
+int rtg_matte_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+                   unsigned lgtNum, const rtg_hit* hits, size_t n, rtg_vec* outHost,
+                   unsigned long long* litHost, int walk, int nthreads);
+
+/* ---- containment: primaryContainer per point ----
+ * "Which medium is this point in": out[i] is the lowest sphere index s for
+ * which, all in float (primaryContainer, raytracer.h:245-270),
+ *   r = radius_s + 1e-6f;  d = p - c_s;  (d.x * d.x + d.y * d.y) + d.z * d.z <= r * r
+ * holds for point p = points[i], or -1.  A NaN coordinate gives -1.  It is the
+ * refraction target rayTrace looks up for its test point P + 0.01 d.
+ * The checks are rtg_matte's, with a null point buffer in place of the hits. */
+int rtg_contains_device(rtg_context* ctx, const rtg_vec* pointsDevice, size_t n, int* outDevice,
+                        void* stream);
+int rtg_contains(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_vec* points,
+                 size_t n, int* outHost);
+/* walk 0: the literal loop over the caller's array.  walk 1: the kernel's
+ * path (four containment records per step, or the BVH). */
+int rtg_contains_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_vec* points, size_t n,
+                      int* outHost, int walk, int nthreads);
 
 /* Semantics of a context's renders.  RTG_SEMANTICS_CPU (default) is the
  * reference CPU path (raytracer.h), bit for bit.  RTG_SEMANTICS_OPENCL is the

@@ -149,6 +149,7 @@ struct RayPath {
   RTG_HD bool blocked(const Scene& sc, V3 o, V3 d, float gap) const {
     return ray_blocked<kBvh>(sc, box, o, d, gap, true);
   }
+  RTG_HD void lit(unsigned) const {}  // matte_light's note of a lit light: not kept
 };
 
 // rayTrace of a caller's own ray (o, d): THE call of the batch ray tracer and

@@ -768,6 +768,7 @@ RTG_HD V3 matte_light(const Scene& sc, V3 P, V3 N, int hit = -1, bool guardOK = 
         sc.count(kULit, 1);
         const float intensity = incidence / gap;
         sum = vadd(sum, vsmul(intensity, Lcol));
+        if constexpr (RP::kOn) rp.lit(l);  // (rtg_matte's per-light mask; RayPath: nothing)
       }
     }
   }

@@ -58,6 +58,9 @@ static void usage() {
   printf("                           --camera or the identity pose; bias defaults to 0.001; a seed\n");
   printf("                           turns RTG_AO_JITTER on); needs --ao-out\n");
   printf("      --ao-out     FILE    The 8-bit binary PGM of (255 * count) / K per pixel\n");
+  printf("      --matte      FILE    Also write the frame's direct light (rtg_matte_device of every\n");
+  printf("                           primary hit at aa 1, from --camera or the identity pose) as a\n");
+  printf("                           P6 PPM, scaled by its own largest component like the render\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -80,7 +83,8 @@ int main(int argc, char** argv) {
   unsigned long long seed = 42;
   float aa = 3.f, zoom = -4.f;
   std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut, radianceOut, aoOut;
-  bool ao = false;
+  std::string matteOut;
+  bool ao = false, matte = false;
   rtg_ao_params aoParams = {0, 0.f, 1.0e-3f, 0, 0};
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
@@ -164,6 +168,9 @@ int main(int argc, char** argv) {
       ao = true;
     } else if (!strcmp(a, "--ao-out")) {
       aoOut = need(a);
+    } else if (!strcmp(a, "--matte")) {
+      matteOut = need(a);
+      matte = true;
     } else if (!strcmp(a, "--scene")) {
       sceneIn = need(a);
     } else if (!strcmp(a, "--save-scene")) {
@@ -197,6 +204,11 @@ int main(int argc, char** argv) {
 
   if (ao == aoOut.empty()) {
     printf("--ao and --ao-out go together\n");
+    return 1;
+  }
+
+  if (matte && (matteOut.empty() || matteOut == out || W == 0 || H == 0)) {
+    printf("Invalid matte (a file other than --out, for a frame with pixels)\n");
     return 1;
   }
 
@@ -348,6 +360,50 @@ int main(int argc, char** argv) {
     }
     printf("Wrote %s (%ux%u, %u probes of length %.8g per primary hit)\n", aoOut.c_str(), W, H, K,
            (double)aoParams.radius);
+  }
+
+  if (matte) {  // pose -> primary rays -> hits -> direct light -> bytes, all on the device
+    const size_t n = (size_t)W * H;
+    if (!posed) rtg_camera_identity(&camera);
+    rtg_context* ctx = nullptr;
+    check(rtg_context_create((int)device, &ctx), "rtg_context_create");
+    check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
+          "rtg_context_set_scene");
+    rtg_ray* dr = nullptr;
+    rtg_hit* dh = nullptr;
+    rtg_vec* dl = nullptr;
+    float* dmax = nullptr;
+    unsigned char* db = nullptr;
+    if (hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
+        hipMalloc(&dh, n * sizeof(rtg_hit)) != hipSuccess ||
+        hipMalloc(&dl, n * sizeof(rtg_vec)) != hipSuccess ||
+        hipMalloc(&dmax, sizeof(float)) != hipSuccess || hipMalloc(&db, n * 3) != hipSuccess)
+      check(RTG_ERR_NOMEM, "hipMalloc");
+    check(rtg_camera_rays_device(ctx, &camera, W, H, zoom, 1.f, dr, nullptr),
+          "rtg_camera_rays_device");
+    check(rtg_intersect_device(ctx, dr, n, dh, nullptr), "rtg_intersect_device");
+    check(rtg_matte_device(ctx, dh, n, dl, nullptr, nullptr), "rtg_matte_device");
+    check(rtg_max_colour_device(ctx, dl, n, dmax, nullptr), "rtg_max_colour_device");
+    check(rtg_ppm_bytes_device(ctx, dl, n, dmax, db, nullptr), "rtg_ppm_bytes_device");
+    std::vector<unsigned char> bytes(n * 3);
+    float lightMax = 0.f;
+    if (hipMemcpy(bytes.data(), db, n * 3, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&lightMax, dmax, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      check(RTG_ERR_HIP, "readback");
+    (void)hipFree(dr);
+    (void)hipFree(dh);
+    (void)hipFree(dl);
+    (void)hipFree(dmax);
+    (void)hipFree(db);
+    rtg_context_destroy(ctx);
+    FILE* f = fopen(matteOut.c_str(), "wb");
+    if (!f || fprintf(f, "P6\n%u %u\n255\n", W, H) < 0 ||
+        fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
+      fprintf(stderr, "Error: can't write %s\n", matteOut.c_str());
+      exit(EXIT_FAILURE);
+    }
+    printf("Wrote %s (%ux%u, direct light of %u lights per primary hit, max %.8g)\n",
+           matteOut.c_str(), W, H, nLgt, (double)lightMax);
   }
 
   if (!raysIn.empty()) {  // records as they lie in memory, like the G-buffer's

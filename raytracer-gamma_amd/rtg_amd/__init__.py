@@ -91,6 +91,8 @@ EXPORTED = [
     "rtg_render_camera_device", "rtg_render_camera", "rtg_render_camera_host",
     "rtg_ao_directions", "rtg_ao_segments_host", "rtg_ao_segments_device", "rtg_ao_device",
     "rtg_ao", "rtg_ao_host",
+    "rtg_matte_device", "rtg_matte", "rtg_matte_host",
+    "rtg_contains_device", "rtg_contains", "rtg_contains_host",
 ]
 
 
@@ -201,6 +203,12 @@ def lib() -> ctypes.CDLL:
         L.rtg_ao_device.argtypes = [vp, vp, sz, vp, vp, u, vp, vp]
         L.rtg_ao.argtypes = [i, vp, u, vp, sz, vp, vp, u, vp]
         L.rtg_ao_host.argtypes = [vp, u, vp, sz, vp, vp, u, vp, i, i]
+        L.rtg_matte_device.argtypes = [vp, vp, sz, vp, vp, vp]
+        L.rtg_matte.argtypes = [i, vp, u, vp, u, vp, sz, vp, vp]
+        L.rtg_matte_host.argtypes = [vp, u, vp, u, vp, sz, vp, vp, i, i]
+        L.rtg_contains_device.argtypes = [vp, vp, sz, vp, vp]
+        L.rtg_contains.argtypes = [i, vp, u, vp, sz, vp]
+        L.rtg_contains_host.argtypes = [vp, u, vp, sz, vp, i, i]
 
         pu = ctypes.POINTER(u)
         L.rtg_scene_load.argtypes = [ctypes.c_char_p, vp, u, pu, vp, u, pu]
@@ -655,6 +663,71 @@ def ao(spheres, hits, dirs, params, device: int = 0) -> np.ndarray:
     return out
 
 
+def _matte_args(spheres, lights, hits, mask: bool):
+    """Scene arrays, hit records and the two results, with pointers that are
+    never null for an empty batch (legal: RTG_OK, nothing written)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    n = len(h)
+    out = np.empty((n, 3), np.float32)
+    lit = np.empty(n, np.uint64) if mask else None
+    src = h if n else np.zeros(1, HIT_DTYPE)
+    dst = out if n else np.zeros((1, 3), np.float32)
+    lp = None if lit is None else ctypes.c_void_p((lit if n else np.zeros(1, np.uint64)).ctypes.data)
+    return spheres, lights, src, n, out, dst, lit, lp
+
+
+def matte_host(spheres, lights, hits, walk: int = 0, threads: int = 1, mask: bool = False):
+    """Direct light on the host (rtg_matte_host; no GPU needed): per HIT_DTYPE
+    record calculateMatte's sum over the lights, (n, 3) float32, the reference's
+    bits.  mask=True: returns (sums, lit), lit the uint64 mask of the first 64
+    lights that reach the point.  walk 0: plain loops; walk 1: the kernel's own
+    path over the packed tables."""
+    sph, lgt, src, n, out, dst, lit, lp = _matte_args(spheres, lights, hits, mask)
+    _check(lib().rtg_matte_host(_ptr(sph), len(sph), _ptr(lgt), len(lgt), _ptr(src), n, _ptr(dst),
+                                lp, walk, threads), "rtg_matte_host")
+    return (out, lit) if mask else out
+
+
+def matte(spheres, lights, hits, device: int = 0, mask: bool = False):
+    """The same on the GPU, one-shot (rtg_matte): HIT_DTYPE records as
+    intersect() returns them in."""
+    sph, lgt, src, n, out, dst, lit, lp = _matte_args(spheres, lights, hits, mask)
+    _check(lib().rtg_matte(device, _ptr(sph), len(sph), _ptr(lgt), len(lgt), _ptr(src), n,
+                           _ptr(dst), lp), "rtg_matte")
+    return (out, lit) if mask else out
+
+
+def _points(points):
+    """Points as a contiguous (n, 3) float32 array, n, the int32 result and
+    pointers that are never null for an empty batch."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = len(p)
+    out = np.empty(n, np.int32)
+    return (p if n else np.zeros((1, 3), np.float32)), n, out, (out if n else np.zeros(1, np.int32))
+
+
+def contains_host(spheres, points, walk: int = 0, threads: int = 1) -> np.ndarray:
+    """The containing sphere of every point on the host (rtg_contains_host; no
+    GPU needed): int32, primaryContainer's lowest index or -1.  walk 0: the
+    literal loop; walk 1: the kernel's own path."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    src, n, out, dst = _points(points)
+    _check(lib().rtg_contains_host(_ptr(spheres), len(spheres), _ptr(src), n, _ptr(dst), walk,
+                                   threads), "rtg_contains_host")
+    return out
+
+
+def contains(spheres, points, device: int = 0) -> np.ndarray:
+    """The same on the GPU, one-shot (rtg_contains)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    src, n, out, dst = _points(points)
+    _check(lib().rtg_contains(device, _ptr(spheres), len(spheres), _ptr(src), n, _ptr(dst)),
+           "rtg_contains")
+    return out
+
+
 class MultiContext:
     """Persistent multi-device handle (rtg_multi_*): RCCL communicator, contexts,
     streams and buffers kept across frames."""
@@ -944,6 +1017,28 @@ class Context:
                                             ctypes.c_void_p(dst_ptr),
                                             ctypes.c_void_p(stream) if stream else None),
                "rtg_ao_segments_device")
+
+    def matte_device(self, hits_ptr: int, n: int, dst_ptr: int, lit_ptr: int = 0,
+                     stream: int = 0):
+        """Direct light of n hit points at hits_ptr (device, 32-byte HIT_DTYPE
+        records as intersect_device writes them) under the resident scene's
+        lights into dst_ptr (device, an (N, 3) float32 tensor) and, when lit_ptr
+        is given, the masks of the lights that reach each point (device, n
+        uint64), asynchronously on `stream` (rtg_matte_device)."""
+        _check(lib().rtg_matte_device(self._h, ctypes.c_void_p(hits_ptr), n,
+                                      ctypes.c_void_p(dst_ptr),
+                                      ctypes.c_void_p(lit_ptr) if lit_ptr else None,
+                                      ctypes.c_void_p(stream) if stream else None),
+               "rtg_matte_device")
+
+    def contains_device(self, points_ptr: int, n: int, dst_ptr: int, stream: int = 0):
+        """The containing sphere of n points at points_ptr (device, an (N, 3)
+        float32 tensor) into dst_ptr (device, n int32: the lowest index or -1),
+        asynchronously on `stream` (rtg_contains_device)."""
+        _check(lib().rtg_contains_device(self._h, ctypes.c_void_p(points_ptr), n,
+                                         ctypes.c_void_p(dst_ptr),
+                                         ctypes.c_void_p(stream) if stream else None),
+               "rtg_contains_device")
 
     def render_rows_device(self, width, height, rows_ptr: int, n_rows: int, dst_ptr: int,
                            zoom=-4.0, alias_factor=3.0, stack_size=6, stream: int = 0):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
-                       [--only-order] [--only-ao] [--order-alt-json FILE ...]
+                       [--only-order] [--only-ao] [--only-matte] [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
 with the scene and the rays resident, on three batches of bench.py's frames:
@@ -58,6 +58,13 @@ Ambient occlusion (csrc/rtg_ao.hip) gets rows under "ao" (ao_rows below): the
 fused call on the frame's primary hits next to the unfused path (segments,
 visible, a torch sum), with and without the ray order.  --only-ao runs these
 alone and keeps FILE's other sections.
+
+Direct light and containment (csrc/rtg_matte.hip) get rows under "matte" and
+"contains" (matte_rows, contains_rows below): the fused call on the frame's
+primary hits, with and without the mask, next to the unfused path (torch
+segments, visible, a torch fold); the containment of the refraction test points
+of the same hits.  --only-matte runs these alone and keeps FILE's other
+sections.
 GPU only.
 """
 import argparse
@@ -322,6 +329,122 @@ def ao_rows(args, W, H, rays, stream):
     return out, ok
 
 
+def _spread_rows(sums):
+    return {k: {"ms_median": round(float(np.median(v)), 5), "ms_min": round(min(v), 5),
+                "ms_max": round(max(v), 5)} for k, v in sums.items()}
+
+
+def matte_rows(args, W, H, rays, stream):
+    """Direct light (csrc/rtg_matte.hip) of the frame's 8.3 M aa = 1 primary
+    hits on C3 (3 lights) and C5 (4 lights).  Round by round in one process: the
+    fused call with and without the mask, and the pieces of the unfused path on
+    the same hits: torch building the n x m segments (P, L) (24 m bytes per
+    point), rtg_visible_device over them, and a torch fold of the same
+    arithmetic (direction, incidence, inverse square, sum over the lights).
+    The unfused row is the per-round sum of its pieces.  Reported, not gated:
+    whether the fused call is slower than the unfused row by more than that
+    row's own min-max spread, and whether torch's fold gives the fused words
+    (its division and square root are torch's).  Gated: the sums with and
+    without the mask are the same words."""
+    n = W * H
+    hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+    out_m = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    out_p = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+    lit = torch.empty((n,), dtype=torch.int64, device="cuda")
+    out, ok = {}, True
+    for name in ("c3", "c5"):
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        m = len(lg)
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream)
+        real = hits[:, 0] >= 0
+        P = hits[:, 2:5].view(torch.float32)
+        N = hits[:, 5:8].view(torch.float32)
+        Lp = torch.from_numpy(np.ascontiguousarray(lg["pos"], F)).cuda()
+        Lc = torch.from_numpy(np.ascontiguousarray(lg["col"], F)).cuda()
+        segs = torch.empty((n, m, 6), dtype=torch.float32, device="cuda")
+        vis = torch.empty((n * m,), dtype=torch.uint8, device="cuda")
+
+        def build():
+            segs[:, :, :3] = P[:, None, :]
+            segs[:, :, 3:] = Lp[None, :, :]
+
+        def fold():
+            dist = Lp[None, :, :] - P[:, None, :]
+            gap = (dist[..., 0] * dist[..., 0] + dist[..., 1] * dist[..., 1]) + dist[..., 2] * dist[..., 2]
+            d = (1.0 / torch.sqrt(gap))[..., None] * dist
+            inc = (N[:, None, 0] * d[..., 0] + N[:, None, 1] * d[..., 1]) + N[:, None, 2] * d[..., 2]
+            on = (vis.view(n, m) != 0) & (inc > 0) & real[:, None]
+            w = torch.where(on, inc / gap, torch.zeros_like(inc))
+            total = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+            for l in range(m):  # in order, as the definition adds them
+                total = total + w[:, l, None] * Lc[l][None, :]
+            return total, on
+
+        raw = []
+        fm, fp, bd, vs, fo = measure(
+            [lambda: ctx.matte_device(hits.data_ptr(), n, out_m.data_ptr(), lit.data_ptr(), stream),
+             lambda: ctx.matte_device(hits.data_ptr(), n, out_p.data_ptr(), 0, stream),
+             build,
+             lambda: ctx.visible_device(segs.data_ptr(), n * m, vis.data_ptr(), stream),
+             fold], args.rounds, raw=raw)
+        total, on = fold()
+        equal = bool((out_m.view(torch.int32) == out_p.view(torch.int32)).all())
+        ok = ok and equal
+        bits = torch.zeros((n,), dtype=torch.int64, device="cuda")
+        for l in range(m):
+            bits |= on[:, l].to(torch.int64) << l
+        rows = _spread_rows({"unfused": [a + b + c for a, b, c in zip(raw[2], raw[3], raw[4])]})
+        spread = rows["unfused"]["ms_max"] - rows["unfused"]["ms_min"]
+        nz = (out_p.view(torch.int32) << 1 != 0).any(1)
+        out[name] = {
+            "lights": m, "hit_points": int(real.sum()), "segment_bytes": n * m * 24,
+            "fused_with_mask": fm, "fused": fp, "segments_torch": bd, "visible": vs,
+            "fold_torch": fo, **rows,
+            "unfused_over_fused": round(rows["unfused"]["ms_median"] / fp["ms_median"], 3),
+            "unfused_over_fused_with_mask": round(rows["unfused"]["ms_median"] / fm["ms_median"], 3),
+            "fused_slower_than_unfused_by_more_than_its_spread":
+                bool(max(fp["ms_median"], fm["ms_median"]) - rows["unfused"]["ms_median"] > spread),
+            "Mpoints_per_s": round(n / (fp["ms_median"] * 1e-3) / 1e6, 1),
+            "lit_share_of_hit_points": round(float(nz[real].to(torch.float64).mean()), 4),
+            "fused_equals_fused_with_mask": equal,
+            "torch_fold_equals_fused_share_of_points": round(float(
+                (total.view(torch.int32) == out_p.view(torch.int32)).all(1).to(torch.float64).mean()), 6),
+            "torch_mask_equals_fused_share_of_points": round(float(
+                (bits == lit).to(torch.float64).mean()), 6)}
+        print(f"matte {name}: fused {fp['ms_median']} ms ({fm['ms_median']} with the mask), unfused "
+              f"{rows['unfused']['ms_median']} ms", file=sys.stderr, flush=True)
+        ctx.close()
+        del segs, vis
+    return out, ok
+
+
+def contains_rows(args, W, H, rays, stream):
+    """Containment (contains_kernel, csrc/rtg_matte.hip) of the refraction test
+    points P + 0.01 d of the same primary hits, C3 and C5.  Recorded only."""
+    n = W * H
+    hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+    idx = torch.empty((n,), dtype=torch.int32, device="cuda")
+    out = {}
+    for name in ("c3", "c5"):
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream)
+        pts = (hits[:, 2:5].view(torch.float32) + 0.01 * rays[:, 3:6]).contiguous()
+        (row,) = measure([lambda: ctx.contains_device(pts.data_ptr(), n, idx.data_ptr(), stream)],
+                         args.rounds)
+        real = hits[:, 0] >= 0
+        out[name] = dict(row, Mpoints_per_s=round(n / (row["ms_median"] * 1e-3) / 1e6, 1),
+                         hit_points=int(real.sum()),
+                         contained_share_of_hit_points=round(
+                             float((idx[real] >= 0).to(torch.float64).mean()), 4))
+        print(f"contains {name}: {row['ms_median']} ms", file=sys.stderr, flush=True)
+        ctx.close()
+    return out
+
+
 def finish(args, res, ok):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -341,6 +464,9 @@ def main():
     ap.add_argument("--only-order", action="store_true", help="the ray order's rows alone")
     ap.add_argument("--only-ao", action="store_true",
                     help="the ambient occlusion's rows alone, put into FILE next to what it holds")
+    ap.add_argument("--only-matte", action="store_true",
+                    help="the direct light's and the containment's rows alone, put into FILE "
+                         "next to what it holds")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
     ap.add_argument("--order-alt-json", default=[], action="append",
@@ -376,6 +502,15 @@ def main():
             with open(args.out) as f:
                 res = dict(json.load(f), ao_commit=args.commit)
         res["ao"], ok = ao_rows(args, W, H, rays, stream)
+        finish(args, res, ok)
+
+    if args.only_matte:
+        del hits, hits2, gb, shuffled
+        if os.path.exists(args.out):  # the other sections stay as they were measured
+            with open(args.out) as f:
+                res = dict(json.load(f), matte_commit=args.commit)
+        res["matte"], ok = matte_rows(args, W, H, rays, stream)
+        res["contains"] = contains_rows(args, W, H, rays, stream)
         finish(args, res, ok)
 
     if args.only_camera:
@@ -458,7 +593,9 @@ def main():
     res["camera"], cam_ok = camera_rows(args, W, H, rays, col, fb, stream)
     del col, fb
     res["ao"], ao_ok = ao_rows(args, W, H, rays, stream)
-    ok = ok and cam_ok and order_ok and ao_ok
+    res["matte"], matte_ok = matte_rows(args, W, H, rays, stream)
+    res["contains"] = contains_rows(args, W, H, rays, stream)
+    ok = ok and cam_ok and order_ok and ao_ok and matte_ok
     if args.mapping_json:
         with open(args.mapping_json) as f:
             other = json.load(f)["camera"]
