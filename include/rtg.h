@@ -26,6 +26,7 @@
  *     raytracer.h:410-636
  *   the camera of main.cpp:384-436, moved to a pose   rtg_camera_look_at, rtg_camera_rays[_device|_host],
  *     (fixed at 0 looking down -z in the reference)    rtg_render_camera[_device|_host]
+ *   (many poses, one frame each: probes, cube maps)    rtg_render_views[_device|_host], rtg_camera_cube
  *   (hemisphere visibility of a hit point: the caller's  rtg_ao[_device|_host],
  *     loop over hasClearLineOfSight in the reference)    rtg_ao_segments[_device|_host]
  *   calculateMatte for a caller's own hit points       rtg_matte[_device|_host]
@@ -541,6 +542,82 @@ int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg
                            unsigned lgtNum, const rtg_camera* cam, unsigned width,
                            unsigned height, float zoom, float aliasFactor, int stackSize,
                            int semantics, rtg_vec* dstHost, int walk, int nthreads);
+
+/* ---- many posed views in one launch: cube maps, light probes ----
+ * A probe bake renders many small frames (six faces per probe, hundreds of
+ * probes, 16 x 16 to 64 x 64 pixels a face); one rtg_render_camera_device per
+ * frame fills a fraction of the GPU and ends in its own tail.  These calls
+ * take a table of nViews poses and write nViews frames of one size, view-major:
+ * pixel (x, y) of view v at dst[(v * height + y) * width + x].
+ *
+ * VIEW v of the output is, bit for bit, the frame rtg_render_camera_host(...,
+ * &poses[v], ..., walk 0) writes: the posed camera's arithmetic above, NaN
+ * words as 0xFFC00000, the context's semantics (the `semantics` argument of
+ * the host form), the stack capacity stackSize.  Width, height, zoom,
+ * aliasFactor and stackSize are shared by all views; a view's pixels never
+ * depend on another view's pose (a NaN pose spoils its own frame only).
+ *
+ * The device form reads the poses from DEVICE memory: nViews 48-byte
+ * rtg_camera records, 4-byte aligned, complete before the call's work starts
+ * on `stream`.  A caller may write them on the GPU (from rtg_intersect_device's
+ * hit points, say) with no trip to the host.  It is asynchronous on `stream`,
+ * follows rtg_context_set_semantics, takes none of the context's render
+ * scratch (so it mixes with every other call on a context, as
+ * rtg_render_camera_device does), and rtg_set_launch_opts does not apply.
+ *
+ * nViews == 0 is RTG_OK: nothing is launched, nothing is written, and the pose
+ * table may be null.  RTG_ERR_INVALID with a message, before any GPU call, for
+ * everything rtg_render_camera* rejects, a null pose table with nViews > 0, a
+ * pose table off 4-byte alignment (device form), nViews * tilesX * tilesY
+ * above 2^31-1 workgroups (tiles of 8 x 8 pixels, rounded up per view) and
+ * nViews * width * height * 12 not representable in size_t.
+ *
+ * Out of scope: per-view sizes or zooms, a G-buffer or ray generator over
+ * views, row shards and multi-GPU for views, filtering or SH projection of
+ * the faces. */
+int rtg_render_views_device(rtg_context* ctx, const rtg_camera* posesDevice, size_t nViews,
+                            unsigned width, unsigned height, float zoom, float aliasFactor,
+                            int stackSize, rtg_vec* dstDevice, void* stream);
+/* One-shot: uploads the scene and the poses, renders on `device`, downloads
+ * nViews * W * H rtg_vec. */
+int rtg_render_views(int device, const rtg_sphere* spheres, unsigned sphNum,
+                     const rtg_light* lights, unsigned lgtNum, const rtg_camera* poses,
+                     size_t nViews, unsigned width, unsigned height, float zoom,
+                     float aliasFactor, int stackSize, rtg_vec* dstHost);
+/* The same on the host, no GPU call; walk, semantics and nthreads as in
+ * rtg_render_camera_host (threads take contiguous bands of the nViews * W * H
+ * pixels). */
+int rtg_render_views_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+                          unsigned lgtNum, const rtg_camera* poses, size_t nViews,
+                          unsigned width, unsigned height, float zoom, float aliasFactor,
+                          int stackSize, int semantics, rtg_vec* dstHost, int walk, int nthreads);
+/* The six 90-degree poses of a cube map at `eye`, in the order +X, -X, +Y, -Y,
+ * +Z, -Z, for a SQUARE frame rendered at zoom = -1.  Face f has forward axis
+ * F, right axis R = F x U and up axis U:
+ *
+ *    f   face   F           R           U
+ *    0   +X    ( 1, 0, 0)  ( 0, 0, 1)  ( 0, 1, 0)
+ *    1   -X    (-1, 0, 0)  ( 0, 0,-1)  ( 0, 1, 0)
+ *    2   +Y    ( 0, 1, 0)  (-1, 0, 0)  ( 0, 0,-1)
+ *    3   -Y    ( 0,-1, 0)  (-1, 0, 0)  ( 0, 0, 1)
+ *    4   +Z    ( 0, 0, 1)  (-1, 0, 0)  ( 0, 1, 0)
+ *    5   -Z    ( 0, 0,-1)  ( 1, 0, 0)  ( 0, 1, 0)
+ *
+ * and out[f] = {eye, right = R * (3.f/32.f), up = U * (float)(1.0/6.0), back =
+ * -F}, a zero component being +0.  The frame's edge is at rx = -+8 * (16/12)
+ * and ry = +-6 (main.cpp:384-402), so 8 * (16/12) * (3/32) = 1 and 6 * (1/6)
+ * = 1 in float: the face spans -1..1 along R and U at distance 1 along F.  The
+ * four side faces have U = +Y (the image's top row is up); +Y takes U = -Z
+ * and -Y takes U = +Z, which is the +Z face pitched up and down, and (R, U,
+ * -F) is right-handed on all six; face 5 is the identity pose's basis, scaled.
+ * The reference's sample grid starts at a pixel's CORNER, not its centre
+ * (main.cpp:411-436, camera_dir), and the faces inherit that: sample (0, 0) of
+ * pixel (0, 0) is the face's top left corner exactly, a face holds its top and
+ * left edges and not its bottom and right ones, and with aliasFactor > 1 the
+ * samples of a pixel lie right of and ABOVE its corner.  (So +Y's top row and
+ * left column are, at aliasFactor 1, directions the side faces' top rows have
+ * too.)  The only error is a null pointer. */
+int rtg_camera_cube(const rtg_vec* eye, rtg_camera out[6]);
 
 /* ---- ambient occlusion: hemisphere visibility per hit point ----
  * Hit points go in, one count of unoccluded probes per point comes out: no

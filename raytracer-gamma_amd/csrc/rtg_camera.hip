@@ -18,8 +18,14 @@
 // bit, the host fold of rtg_raytrace_host(walk 0) over rtg_camera_rays_host's
 // rays: no ray buffer, no colour buffer and no fold on the caller's side.
 //
+// Many views in one launch (rtg_render_views*, views_kernel next to
+// camera_kernel): a table of poses in device memory, one frame each, the
+// workgroups spanning the views; the per-tile body is camera_kernel's, so view
+// v is bit for bit the single-view frame of pose v.  rtg_camera_cube writes
+// the six poses of a cube map.
+//
 // This file holds the pose helpers, the generator (kernel and host form), the
-// launcher of the fused kernel (picked from stack_kernels, rtg_trace_kernels.h),
+// launchers of the fused kernels (picked from stack_kernels, rtg_trace_kernels.h),
 // the pose's own argument checks (the rest are rtg_entry.h's) and the host
 // forms of the render (walk 0: trace_ray_plain, the yardstick; walk 1:
 // trace_ray, the kernel's own path over the packed tables, one pixel per
@@ -121,6 +127,56 @@ static size_t camera_blocks(unsigned W, unsigned H, unsigned* tilesX) {
   *tilesX = (unsigned)tx;
   return (ty && tx > 0x7FFFFFFFu / ty) ? 0 : tx * ty;
 }
+
+// The same for nViews frames of W x H (views_kernel: nViews * tilesPerView
+// workgroups); 0 when more than 2^31-1.  nViews > 0.
+static size_t views_blocks(size_t nViews, unsigned W, unsigned H, unsigned* tilesX,
+                           unsigned* tilesPerView) {
+  const size_t per = camera_blocks(W, H, tilesX);
+  *tilesPerView = (unsigned)per;
+  return (per && nViews > 0x7FFFFFFFu / per) ? 0 : nViews * per;
+}
+
+// What rtg_render_views* check first: the pointers (no views need no pose
+// table), then the frame as check_frame does.
+static int check_views_frame(const rtg_camera* poses, size_t nViews, const void* dst, unsigned W,
+                             unsigned H, float zoom, float aa, Camera* out) {
+  if (!dst || (nViews && !poses)) {
+    rtg_set_error("render_views: null %s", dst ? "pose table" : "destination");
+    return RTG_ERR_INVALID;
+  }
+  return make_camera(W, H, zoom, aa, out);
+}
+
+// ... and after it (so W * H > 0): the stack size, then the batch's size, its
+// workgroups (*blocks; 0 for no views) and its bytes.
+static int check_views(size_t nViews, unsigned W, unsigned H, int stackSize, unsigned* tilesX,
+                       unsigned* tilesPerView, size_t* blocks) {
+  const int rc = check_stack("render_views", stackSize);
+  if (rc || nViews == 0) return rc;
+  *blocks = views_blocks(nViews, W, H, tilesX, tilesPerView);
+  if (!*blocks) {
+    rtg_set_error("render_views: batch too large (more than 2^31-1 workgroups)");
+    return RTG_ERR_INVALID;
+  }
+  // W * H < 2^64 always; the views' pixels and their 12 B each may not be
+  if (nViews > SIZE_MAX / sizeof(rtg_vec) / ((size_t)W * H)) {
+    rtg_set_error("render_views: batch too large (%zu views of %u x %u pixels)", nViews, W, H);
+    return RTG_ERR_INVALID;
+  }
+  return RTG_OK;
+}
+
+// Face f of rtg_camera_cube: forward F, right R, up U (rtg.h's table; R =
+// F x U, so (R, U, -F) is right-handed on all six).
+static const signed char kCubeAxes[6][3][3] = {
+    {{1, 0, 0}, {0, 0, 1}, {0, 1, 0}},    // +X
+    {{-1, 0, 0}, {0, 0, -1}, {0, 1, 0}},  // -X
+    {{0, 1, 0}, {-1, 0, 0}, {0, 0, -1}},  // +Y
+    {{0, -1, 0}, {-1, 0, 0}, {0, 0, 1}},  // -Y
+    {{0, 0, 1}, {-1, 0, 0}, {0, 1, 0}},   // +Z
+    {{0, 0, -1}, {1, 0, 0}, {0, 1, 0}},   // -Z
+};
 
 extern "C" {
 
@@ -292,6 +348,126 @@ int rtg_render_camera(int device, const rtg_sphere* spheres, unsigned sphNum,
                   [&](rtg_context* ctx, const void*, void* out) {
                     return rtg_render_camera_device(ctx, cam, width, height, zoom, aliasFactor,
                                                     stackSize, (rtg_vec*)out, nullptr);
+                  });
+}
+
+// ---- many views in one launch ----
+
+int rtg_camera_cube(const rtg_vec* eye, rtg_camera out[6]) {
+  rtg_clear_error();
+  if (!eye || !out) {
+    rtg_set_error("camera_cube: null pointer");
+    return RTG_ERR_INVALID;
+  }
+  const float rs = 3.f / 32.f, us = (float)(1.0 / 6.0);
+  for (int f = 0; f < 6; ++f) {
+    const signed char(*t)[3] = kCubeAxes[f];
+    // a zero component is +0: the table's integers, converted
+    const rtg_camera c = {*eye,
+                          {(float)t[1][0] * rs, (float)t[1][1] * rs, (float)t[1][2] * rs},
+                          {(float)t[2][0] * us, (float)t[2][1] * us, (float)t[2][2] * us},
+                          {(float)-t[0][0], (float)-t[0][1], (float)-t[0][2]}};
+    out[f] = c;
+  }
+  return RTG_OK;
+}
+
+int rtg_render_views_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+                          unsigned lgtNum, const rtg_camera* poses, size_t nViews,
+                          unsigned width, unsigned height, float zoom, float aliasFactor,
+                          int stackSize, int semantics, rtg_vec* dstHost, int walk, int nthreads) {
+  rtg_clear_error();
+  Camera c;
+  unsigned tilesX = 0, tilesPerView = 0;
+  size_t blocks = 0;
+  int rc = check_views_frame(poses, nViews, dstHost, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_views(nViews, width, height, stackSize, &tilesX, &tilesPerView, &blocks);
+  if (!rc) rc = check_scene_arrays("render_views", spheres, sphNum, lights, lgtNum);
+  if (!rc) rc = check_semantics("render_views", semantics);
+  if (!rc) rc = check_walk("render_views", walk);
+  if (!rc) rc = check_sphere_count("render_views", sphNum);
+  if (rc) return rc;
+  if (nViews == 0) return RTG_OK;
+  PackedScene ps;
+  pack_scene(spheres, sphNum, lights, lgtNum, &ps);  // as rtg_context_set_scene
+  const bool bvh = walk == 1 && !ps.bvhNodes.empty();
+  const RayBox box = bvh ? ray_box(ps.originBox) : RayBox{};
+  const CamHostFn fn = host_trace_fn(
+      stackSize, semantics == RTG_SEMANTICS_OPENCL, walk == 1, bvh,
+      [](auto s, auto cl, auto wk, auto bv) -> CamHostFn {
+        return camera_host_range<s.value, cl.value, wk.value, bv.value>;
+      });
+  const size_t per = (size_t)width * height;
+  // bands of the batch's pixels; a band's part of view v is pixels [lo, hi) of it
+  host_bands(nViews * per, nthreads, [&](size_t k0, size_t k1) {
+    for (size_t v = k0 / per; v * per < k1; ++v) {
+      const size_t lo = k0 > v * per ? k0 - v * per : 0;
+      const size_t hi = k1 - v * per < per ? k1 - v * per : per;
+      fn(ps, box, c, cam_pose(poses[v]), width, lo, hi, dstHost + v * per);
+    }
+  });
+  return RTG_OK;
+}
+
+int rtg_render_views_device(rtg_context* ctx, const rtg_camera* posesDevice, size_t nViews,
+                            unsigned width, unsigned height, float zoom, float aliasFactor,
+                            int stackSize, rtg_vec* dstDevice, void* stream) {
+  rtg_clear_error();
+  SceneTables a{};
+  RayBox box{};
+  int device = 0, semantics = RTG_SEMANTICS_CPU;
+  if (!rtg_context_scene(ctx, &a, &device, &box, &semantics)) {
+    rtg_set_error("render_views: no context/scene");
+    return RTG_ERR_INVALID;
+  }
+  Camera c;
+  unsigned tilesX = 0, tilesPerView = 0;
+  size_t blocks = 0;
+  int rc = check_views_frame(posesDevice, nViews, dstDevice, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_views(nViews, width, height, stackSize, &tilesX, &tilesPerView, &blocks);
+  if (rc) return rc;
+  if ((uintptr_t)posesDevice % 4) {
+    rtg_set_error("render_views: pose table not 4-byte aligned");
+    return RTG_ERR_INVALID;
+  }
+  if (nViews == 0) return RTG_OK;
+  DeviceGuard deviceGuard;  // (after the checks: no GPU call before them)
+  const bool bvh = a.bvhNodes != nullptr;
+  const StackKernels* sk = stack_kernels(stackSize);
+  const ViewsFn fn = sk ? sk->views(bvh, semantics == RTG_SEMANTICS_OPENCL) : nullptr;
+  if (!fn) {  // a missing kernel is an error, never another path
+    rtg_set_error("render_views: no kernel for stackSize %d", stackSize);
+    return RTG_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64), raytrace_lds_bytes(stackSize, bvh),
+                     (hipStream_t)stream, a, box, c,
+                     reinterpret_cast<const CamPose*>(posesDevice), width, height, tilesX,
+                     tilesPerView, dstDevice);
+  HIP_TRY(hipGetLastError());
+  return RTG_OK;
+}
+
+int rtg_render_views(int device, const rtg_sphere* spheres, unsigned sphNum,
+                     const rtg_light* lights, unsigned lgtNum, const rtg_camera* poses,
+                     size_t nViews, unsigned width, unsigned height, float zoom,
+                     float aliasFactor, int stackSize, rtg_vec* dstHost) {
+  rtg_clear_error();
+  Camera c;
+  unsigned tilesX = 0, tilesPerView = 0;
+  size_t blocks = 0;
+  int rc = check_views_frame(poses, nViews, dstHost, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_views(nViews, width, height, stackSize, &tilesX, &tilesPerView, &blocks);
+  if (!rc) rc = check_scene_arrays("render_views", spheres, sphNum, lights, lgtNum);
+  if (rc) return rc;
+  if (nViews == 0) return RTG_OK;
+  DeviceGuard deviceGuard;  // (after the checks: no GPU call before them)
+  return one_shot(device, spheres, sphNum, lights, lgtNum, poses, nViews * sizeof(rtg_camera),
+                  dstHost, nViews * width * height * sizeof(rtg_vec),
+                  [&](rtg_context* ctx, const void* in, void* out) {
+                    return rtg_render_views_device(ctx, (const rtg_camera*)in, nViews, width,
+                                                   height, zoom, aliasFactor, stackSize,
+                                                   (rtg_vec*)out, nullptr);
                   });
 }
 

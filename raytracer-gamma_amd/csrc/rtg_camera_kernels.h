@@ -1,7 +1,8 @@
-// rtg_camera_kernels.h — the posed camera's fused render kernel
-// (rtg_render_camera*, rtg.h) as a template over the stack capacity S,
-// instantiated next to the render kernels and raytrace_kernel in
-// rtg_trace_s<S>.hip (camera_fn<S>); the launcher, the generator kernel
+// rtg_camera_kernels.h — the posed camera's fused render kernels
+// (rtg_render_camera*: one pose; rtg_render_views*: a table of poses; rtg.h)
+// as templates over the stack capacity S, instantiated next to the render
+// kernels and raytrace_kernel in rtg_trace_s<S>.hip (camera_fn<S>,
+// views_fn<S>); the launchers, the generator kernel
 // (camera_rays_kernel: not a template, so it is defined once, in the launcher's
 // translation unit) and the host forms are in rtg_camera.hip.
 #pragma once
@@ -19,23 +20,24 @@ namespace rtg {
 constexpr unsigned kCamTileW = 8, kCamTileH = 8;
 static_assert(kCamTileW * kCamTileH == 64, "one lane per pixel of the tile");
 
-// One lane per pixel, one-wave workgroups, workgroup b the tile (b % tilesX,
-// b / tilesX); the LDS image and the scene binding are raytrace_kernel's.  A
-// lane whose pixel lies outside the frame leaves before the trace (the
-// queries' wave-level tests are over the lanes present).  The others trace
-// the pixel's samples in the reference's order, each sample rayTrace of the
-// pose's ray as raytrace_kernel runs it, and fold them as shade_pixel does:
-// pix += (1/nS) * c.
+// One wave's tile of one W x H frame: tile `tile` is (tile % tilesX,
+// tile / tilesX), `dst` the frame's first pixel.  The LDS image and the scene
+// binding are raytrace_kernel's.  A lane whose pixel lies outside the frame
+// leaves before the trace (the queries' wave-level tests are over the lanes
+// present), so a ragged tile never writes past its own frame's rows.  The
+// others trace the pixel's samples in the
+// reference's order, each sample rayTrace of the pose's ray as raytrace_kernel
+// runs it, and fold them as shade_pixel does: pix += (1/nS) * c.
 template <int S, bool kBvh, bool kCL>
-__global__ __launch_bounds__(64) void camera_kernel(const SceneTables a, const RayBox box,
-                                                    const Camera cam, const CamPose pose,
-                                                    unsigned W, unsigned H, unsigned tilesX,
-                                                    rtg_vec* __restrict__ dst) {
+__device__ __forceinline__ void camera_tile(const SceneTables& a, const RayBox& box,
+                                            const Camera& cam, const CamPose& pose, unsigned W,
+                                            unsigned H, unsigned tilesX, unsigned tile,
+                                            rtg_vec* __restrict__ dst) {
   extern __shared__ float4 lds4[];
   RayScene<kBvh> sc;
   bind_raytrace_scene<S>(sc, a, lds4);
-  const size_t px = (size_t)(blockIdx.x % tilesX) * kCamTileW + threadIdx.x % kCamTileW;
-  const size_t py = (size_t)(blockIdx.x / tilesX) * kCamTileH + threadIdx.x / kCamTileW;
+  const size_t px = (size_t)(tile % tilesX) * kCamTileW + threadIdx.x % kCamTileW;
+  const size_t py = (size_t)(tile / tilesX) * kCamTileH + threadIdx.x / kCamTileW;
   if (px >= W || py >= H) return;
   const unsigned x = (unsigned)px, y = (unsigned)py;
   V3 pix = v3(0.f, 0.f, 0.f);
@@ -50,11 +52,49 @@ __global__ __launch_bounds__(64) void camera_kernel(const SceneTables a, const R
   store_colour_dev(dst + (py * W + px), pix);  // px < W, py < H: 12 B of the frame
 }
 
+// One pose, one frame: one lane per pixel, one-wave workgroups, workgroup b
+// the tile b, the pose by value in the kernel arguments.
+template <int S, bool kBvh, bool kCL>
+__global__ __launch_bounds__(64) void camera_kernel(const SceneTables a, const RayBox box,
+                                                    const Camera cam, const CamPose pose,
+                                                    unsigned W, unsigned H, unsigned tilesX,
+                                                    rtg_vec* __restrict__ dst) {
+  camera_tile<S, kBvh, kCL>(a, box, cam, pose, W, H, tilesX, blockIdx.x, dst);
+}
+
+// Many poses, one frame each (rtg_render_views*), view-major: workgroup b is
+// tile b % tilesPerView of view b / tilesPerView, and the grid is exactly
+// nViews * tilesPerView workgroups, so the view is one of the table's.  A
+// view's tiles are neighbours in dispatch order: waves resident together walk
+// the same part of the BVH.  The view index comes from blockIdx.x alone, so
+// the pose's 48 B are read through a wave-uniform address: scalar loads into
+// SGPRs, not 64 lanes' vector loads.  The table is only
+// read, and it is complete before the launch (a kernel boundary), which is
+// what the scalar cache needs.
+template <int S, bool kBvh, bool kCL>
+__global__ __launch_bounds__(64) void views_kernel(const SceneTables a, const RayBox box,
+                                                   const Camera cam,
+                                                   const CamPose* __restrict__ poses, unsigned W,
+                                                   unsigned H, unsigned tilesX,
+                                                   unsigned tilesPerView,
+                                                   rtg_vec* __restrict__ dst) {
+  const unsigned view = blockIdx.x / tilesPerView;
+  const unsigned tile = blockIdx.x - view * tilesPerView;
+  const CamPose pose = poses[view];  // view < nViews: 48 B of the table
+  camera_tile<S, kBvh, kCL>(a, box, cam, pose, W, H, tilesX, tile,
+                            dst + (size_t)view * W * H);
+}
+
 // bvh: the scene has a BVH (SceneTables::bvhNodes); cl: RTG_SEMANTICS_OPENCL.
 template <int S>
 static CameraFn camera_fn(bool bvh, bool cl) {
   if (bvh) return cl ? camera_kernel<S, true, true> : camera_kernel<S, true, false>;
   return cl ? camera_kernel<S, false, true> : camera_kernel<S, false, false>;
+}
+template <int S>
+static ViewsFn views_fn(bool bvh, bool cl) {
+  if (bvh) return cl ? views_kernel<S, true, true> : views_kernel<S, true, false>;
+  return cl ? views_kernel<S, false, true> : views_kernel<S, false, false>;
 }
 
 }  // namespace rtg

@@ -1215,13 +1215,17 @@ typedef void (*RayTraceFn)(const SceneTables, const RayBox, const rtg_ray*, cons
                            rtg_vec*);
 typedef void (*CameraFn)(const SceneTables, const RayBox, const Camera, const CamPose, unsigned,
                          unsigned, unsigned, rtg_vec*);
+// ... and its many-views form (views_kernel: a pose table in device memory).
+typedef void (*ViewsFn)(const SceneTables, const RayBox, const Camera, const CamPose*, unsigned,
+                        unsigned, unsigned, unsigned, rtg_vec*);
 
 // What one per-S object (rtg_trace_s<S>.hip) exports: its kernels by variant
-// (trace_fn<S>, raytrace_fn<S>, camera_fn<S>).
+// (trace_fn<S>, raytrace_fn<S>, camera_fn<S>, views_fn<S>).
 struct StackKernels {
   TraceFn (*trace)(int variant, bool bvh, int list);
   RayTraceFn (*raytrace)(bool bvh, bool cl);
   CameraFn (*camera)(bool bvh, bool cl);
+  ViewsFn (*views)(bool bvh, bool cl);
 };
 #define RTG_X(k) const StackKernels* stack_kernels_s##k();
 RTG_FOR_EACH_S(RTG_X)

@@ -53,6 +53,12 @@ static void usage() {
   printf("                           --semantics): 12-byte rtg_vec records\n");
   printf("      --camera     POSE    Render from a posed camera: ex,ey,ez,tx,ty,tz[,ux,uy,uz] (eye,\n");
   printf("                           target, up; up defaults to 0,1,0), rtg_camera_look_at\n");
+  printf("      --views      FILE    Render one frame per line of FILE, each a pose in --camera's\n");
+  printf("                           syntax, in one launch (rtg_render_views_device); frame k goes\n");
+  printf("                           to <out stem>.<k>.ppm\n");
+  printf("      --cube       EYE     Render the six cube-map faces at ex,ey,ez (rtg_camera_cube: +X,\n");
+  printf("                           -X, +Y, -Y, +Z, -Z) the same way; square frames at zoom -1\n");
+  printf("                           (--width defaults to --height and the reverse, both to 64)\n");
   printf("      --ao         SPEC    Also write the frame's ambient occlusion: K,radius[,bias[,seed]]\n");
   printf("                           (K probes of rtg_ao_directions(K) per primary hit at aa 1, from\n");
   printf("                           --camera or the identity pose; bias defaults to 0.001; a seed\n");
@@ -68,6 +74,18 @@ static void usage() {
   printf("      --semantics  MODE    cpu (default: raytracer.h, bit-exact) or opencl\n");
   printf("                           (raytrace_kernel.cl; use with --depth 4 = its stack of 5)\n");
   printf("\n");
+}
+
+// "ex,ey,ez,tx,ty,tz[,ux,uy,uz]" as rtg_camera_look_at's pose; false when it is not that.
+static bool parse_pose(const char* s, rtg_camera* out) {
+  float v[9] = {0, 0, 0, 0, 0, 0, 0.f, 1.f, 0.f};
+  char tail = 0;
+  const int k = sscanf(s, "%f,%f,%f,%f,%f,%f,%f,%f,%f%c", v, v + 1, v + 2, v + 3, v + 4, v + 5,
+                       v + 6, v + 7, v + 8, &tail);
+  if (k != 6 && k != 9) return false;
+  const rtg_vec eye = {v[0], v[1], v[2]}, target = {v[3], v[4], v[5]}, up = {v[6], v[7], v[8]};
+  check(rtg_camera_look_at(&eye, &target, &up, out), "rtg_camera_look_at");
+  return true;
 }
 
 static bool parse_uint(const char* s, unsigned* out) {
@@ -91,6 +109,9 @@ int main(int argc, char** argv) {
   bool posed = false;
   bool sortRays = false;
   rtg_camera camera;
+  std::string viewsIn;  // --views
+  bool cube = false, haveW = false, haveH = false, haveZoom = false;
+  rtg_vec cubeEye = {0.f, 0.f, 0.f};
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* opt) -> const char* {
       if (++i >= argc) {
@@ -119,8 +140,10 @@ int main(int argc, char** argv) {
       if (!parse_uint(need(a), &device)) { printf("Invalid device index\n"); return 1; }
     } else if (!strcmp(a, "--width")) {
       if (!parse_uint(need(a), &W)) { printf("Invalid width\n"); return 1; }
+      haveW = true;
     } else if (!strcmp(a, "--height")) {
       if (!parse_uint(need(a), &H)) { printf("Invalid height\n"); return 1; }
+      haveH = true;
     } else if (!strcmp(a, "--spheres")) {
       if (!parse_uint(need(a), &nSph)) { printf("Invalid sphere count\n"); return 1; }
     } else if (!strcmp(a, "--lights")) {
@@ -133,6 +156,7 @@ int main(int argc, char** argv) {
       aa = strtof(need(a), nullptr);
     } else if (!strcmp(a, "--zoom")) {
       zoom = strtof(need(a), nullptr);
+      haveZoom = true;
     } else if (!strcmp(a, "--seed")) {
       seed = strtoull(need(a), nullptr, 10);
     } else if (!strcmp(a, "--out")) {
@@ -148,14 +172,20 @@ int main(int argc, char** argv) {
     } else if (!strcmp(a, "--radiance")) {
       radianceOut = need(a);
     } else if (!strcmp(a, "--camera")) {
-      float v[9] = {0, 0, 0, 0, 0, 0, 0.f, 1.f, 0.f};
-      char tail = 0;
-      const int k = sscanf(need(a), "%f,%f,%f,%f,%f,%f,%f,%f,%f%c", v, v + 1, v + 2, v + 3, v + 4,
-                           v + 5, v + 6, v + 7, v + 8, &tail);
-      if (k != 6 && k != 9) { printf("Invalid camera (ex,ey,ez,tx,ty,tz[,ux,uy,uz])\n"); return 1; }
-      const rtg_vec eye = {v[0], v[1], v[2]}, target = {v[3], v[4], v[5]}, up = {v[6], v[7], v[8]};
-      check(rtg_camera_look_at(&eye, &target, &up, &camera), "rtg_camera_look_at");
+      if (!parse_pose(need(a), &camera)) {
+        printf("Invalid camera (ex,ey,ez,tx,ty,tz[,ux,uy,uz])\n");
+        return 1;
+      }
       posed = true;
+    } else if (!strcmp(a, "--views")) {
+      viewsIn = need(a);
+    } else if (!strcmp(a, "--cube")) {
+      char tail = 0;
+      if (sscanf(need(a), "%f,%f,%f%c", &cubeEye.x, &cubeEye.y, &cubeEye.z, &tail) != 3) {
+        printf("Invalid cube (ex,ey,ez)\n");
+        return 1;
+      }
+      cube = true;
     } else if (!strcmp(a, "--ao")) {
       char tail = 0;
       const int k = sscanf(need(a), "%u,%f,%f,%u%c", &aoParams.samples, &aoParams.radius,
@@ -217,6 +247,49 @@ int main(int argc, char** argv) {
     return 1;
   }
 
+  const bool manyViews = cube || !viewsIn.empty();
+  if (manyViews && (cube == !viewsIn.empty() || posed || gpus || ao || matte || !gbufOut.empty() ||
+                    !raysIn.empty())) {
+    printf("--views or --cube renders alone: one of them, on one device, without --camera,\n"
+           "--gbuffer, --rays, --ao or --matte\n");
+    return 1;
+  }
+  if (cube) {  // rtg_camera_cube's poses are for a square frame at zoom -1
+    if (!haveW) W = haveH ? H : 64;
+    if (!haveH) H = W;
+    if (W != H || (haveZoom && zoom != -1.f)) {
+      printf("--cube renders square frames at --zoom -1 (got %ux%u, zoom %g)\n", W, H,
+             haveZoom ? (double)zoom : -1.0);
+      return 1;
+    }
+    zoom = -1.f;
+  }
+  std::vector<rtg_camera> views;
+  if (cube) {
+    views.resize(6);
+    check(rtg_camera_cube(&cubeEye, views.data()), "rtg_camera_cube");
+  } else if (manyViews) {
+    FILE* f = fopen(viewsIn.c_str(), "r");
+    if (!f) {
+      fprintf(stderr, "Error: can't read %s\n", viewsIn.c_str());
+      exit(EXIT_FAILURE);
+    }
+    char line[512];
+    while (fgets(line, sizeof line, f)) {
+      size_t len = strlen(line);
+      while (len && strchr(" \t\r\n", line[len - 1])) line[--len] = 0;
+      if (line[strspn(line, " \t")] == 0) continue;  // a blank line
+      rtg_camera c;
+      if (!parse_pose(line, &c)) {
+        printf("Invalid pose on line %zu of %s (ex,ey,ez,tx,ty,tz[,ux,uy,uz])\n", views.size() + 1,
+               viewsIn.c_str());
+        return 1;
+      }
+      views.push_back(c);
+    }
+    fclose(f);
+  }
+
   std::vector<rtg_sphere> spheres;
   std::vector<rtg_light> lights;
   if (!sceneIn.empty()) {
@@ -240,6 +313,48 @@ int main(int argc, char** argv) {
   char info[256];
   check(rtg_device_info((int)device, info, sizeof info), "rtg_device_info");
   printf("Device %u: %s\n", device, info);
+
+  if (manyViews) {  // one context, the poses up, one launch, every frame down
+    const size_t nV = views.size(), per = (size_t)W * H;
+    std::vector<rtg_vec> frames(nV * per);
+    rtg_context* ctx = nullptr;
+    check(rtg_context_create((int)device, &ctx), "rtg_context_create");
+    check(rtg_context_set_semantics(ctx, semantics), "rtg_context_set_semantics");
+    check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
+          "rtg_context_set_scene");
+    rtg_camera* dv = nullptr;
+    rtg_vec* d = nullptr;
+    if (nV && per) {
+      if (hipMalloc(&dv, nV * sizeof(rtg_camera)) != hipSuccess ||
+          hipMalloc(&d, frames.size() * sizeof(rtg_vec)) != hipSuccess)
+        check(RTG_ERR_NOMEM, "hipMalloc");
+      if (hipMemcpy(dv, views.data(), nV * sizeof(rtg_camera), hipMemcpyHostToDevice) !=
+          hipSuccess)
+        check(RTG_ERR_HIP, "upload");
+    }
+    if (nV)
+      check(rtg_render_views_device(ctx, dv, nV, W, H, zoom, aa, (int)depth + 1, d, nullptr),
+            "rtg_render_views_device");
+    if (nV && per &&
+        hipMemcpy(frames.data(), d, frames.size() * sizeof(rtg_vec), hipMemcpyDeviceToHost) !=
+            hipSuccess)
+      check(RTG_ERR_HIP, "readback");
+    (void)hipFree(dv);
+    (void)hipFree(d);
+    rtg_context_destroy(ctx);
+    const size_t dot = out.rfind('.'), slash = out.find_last_of('/');
+    const bool ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+    const std::string stem = ext ? out.substr(0, dot) : out, suffix = ext ? out.substr(dot) : "";
+    for (size_t k = 0; k < nV; ++k) {  // each frame scaled by its own largest colour, as --camera's
+      const std::string name = stem + "." + std::to_string(k) + suffix;
+      const float mx = rtg_max_colour(frames.data() + k * per, per);
+      check(rtg_save_ppm(frames.data() + k * per, name.c_str(), (int)W, (int)H, mx),
+            "rtg_save_ppm");
+      printf("Wrote %s (%ux%u, view %zu of %zu, max colour %.8g)\n", name.c_str(), W, H, k, nV,
+             (double)mx);
+    }
+    return 0;
+  }
 
   std::vector<rtg_vec> pixels((size_t)W * H);
   rtg_multi* mg = nullptr;  // --gpus: one communicator for every repeat

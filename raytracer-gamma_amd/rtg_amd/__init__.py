@@ -89,6 +89,7 @@ EXPORTED = [
     "rtg_camera_identity", "rtg_camera_look_at", "rtg_camera_sample_count",
     "rtg_camera_rays_host", "rtg_camera_rays_device",
     "rtg_render_camera_device", "rtg_render_camera", "rtg_render_camera_host",
+    "rtg_render_views_device", "rtg_render_views", "rtg_render_views_host", "rtg_camera_cube",
     "rtg_ao_directions", "rtg_ao_segments_host", "rtg_ao_segments_device", "rtg_ao_device",
     "rtg_ao", "rtg_ao_host",
     "rtg_matte_device", "rtg_matte", "rtg_matte_host",
@@ -197,6 +198,10 @@ def lib() -> ctypes.CDLL:
         L.rtg_render_camera_device.argtypes = [vp, vp, u, u, f, f, i, vp, vp]
         L.rtg_render_camera.argtypes = [i, vp, u, vp, u, vp, u, u, f, f, i, vp]
         L.rtg_render_camera_host.argtypes = [vp, u, vp, u, vp, u, u, f, f, i, i, vp, i, i]
+        L.rtg_render_views_device.argtypes = [vp, vp, sz, u, u, f, f, i, vp, vp]
+        L.rtg_render_views.argtypes = [i, vp, u, vp, u, vp, sz, u, u, f, f, i, vp]
+        L.rtg_render_views_host.argtypes = [vp, u, vp, u, vp, sz, u, u, f, f, i, i, vp, i, i]
+        L.rtg_camera_cube.argtypes = [vp, vp]
         L.rtg_ao_directions.argtypes = [u, vp]
         L.rtg_ao_segments_host.argtypes = [vp, sz, vp, vp, u, vp, i]
         L.rtg_ao_segments_device.argtypes = [vp, vp, sz, vp, vp, u, vp, vp]
@@ -599,6 +604,57 @@ def render_camera_host(spheres, lights, cam, width: int, height: int, zoom: floa
     return out
 
 
+def _cameras(cams) -> np.ndarray:
+    """A pose table as CAMERA_DTYPE records (records, or (n, 12) floats)."""
+    a = np.asarray(cams)
+    if a.dtype != CAMERA_DTYPE:
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 12).view(CAMERA_DTYPE)
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def camera_cube(eye) -> np.ndarray:
+    """The six cube-map poses at `eye` (rtg_camera_cube): +X, -X, +Y, -Y, +Z, -Z,
+    for a square frame at zoom = -1."""
+    e = np.ascontiguousarray(eye, np.float32).reshape(3)
+    out = np.zeros(6, CAMERA_DTYPE)
+    _check(lib().rtg_camera_cube(_ptr(e), _ptr(out)), "rtg_camera_cube")
+    return out
+
+
+def render_views(spheres, lights, cams, width: int, height: int, zoom: float = -4.0,
+                 alias_factor: float = 3.0, stack_size: int = 6, device: int = 0) -> np.ndarray:
+    """One-shot frames of a table of poses on the GPU in one launch
+    (rtg_render_views): (n, H, W, 3) float32, view v bit for bit
+    render_camera_host of cams[v]."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    c = _cameras(cams)
+    out = np.empty((len(c), height, width, 3), np.float32)
+    dst = out if len(c) else np.zeros((1, 3), np.float32)
+    _check(lib().rtg_render_views(device, _ptr(spheres), len(spheres), _ptr(lights), len(lights),
+                                  _ptr(c) if len(c) else None, len(c), width, height,
+                                  float(zoom), float(alias_factor), stack_size, _ptr(dst)),
+           "rtg_render_views")
+    return out
+
+
+def render_views_host(spheres, lights, cams, width: int, height: int, zoom: float = -4.0,
+                      alias_factor: float = 3.0, stack_size: int = 6, semantics: int = 0,
+                      walk: int = 0, threads: int = 1) -> np.ndarray:
+    """The same on the host (rtg_render_views_host; no GPU needed); walk and
+    semantics as raytrace_host."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    c = _cameras(cams)
+    out = np.empty((len(c), height, width, 3), np.float32)
+    dst = out if len(c) else np.zeros((1, 3), np.float32)
+    _check(lib().rtg_render_views_host(_ptr(spheres), len(spheres), _ptr(lights), len(lights),
+                                       _ptr(c) if len(c) else None, len(c), width, height,
+                                       float(zoom), float(alias_factor), stack_size, semantics,
+                                       _ptr(dst), walk, threads), "rtg_render_views_host")
+    return out
+
+
 def ao_params(samples: int, radius: float, bias: float = 1e-3, seed: int = 0,
               flags: int = 0) -> np.ndarray:
     """One rtg_ao_params record (flags: AO_JITTER for a per-point window into the table)."""
@@ -981,6 +1037,18 @@ class Context:
                                               ctypes.c_void_p(dst_ptr),
                                               ctypes.c_void_p(stream) if stream else None),
                "rtg_render_camera_device")
+
+    def render_views(self, cams_ptr: int, n_views: int, width, height, dst_ptr: int, zoom=-4.0,
+                     alias_factor=3.0, stack_size=6, stream: int = 0):
+        """n_views posed frames of the resident scene in one launch: the poses at
+        cams_ptr (DEVICE, n_views 48-byte CAMERA_DTYPE records: an (n, 12) float32
+        tensor), the frames into dst_ptr (device, an (n, H, W, 3) float32 tensor),
+        asynchronously on `stream` (rtg_render_views_device)."""
+        _check(lib().rtg_render_views_device(self._h, ctypes.c_void_p(cams_ptr), n_views, width,
+                                             height, float(zoom), float(alias_factor), stack_size,
+                                             ctypes.c_void_p(dst_ptr),
+                                             ctypes.c_void_p(stream) if stream else None),
+               "rtg_render_views_device")
 
     def camera_rays(self, cam, width, height, dst_ptr: int, zoom=-4.0, alias_factor=3.0,
                     stream: int = 0):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
-                       [--only-order] [--only-ao] [--only-matte] [--order-alt-json FILE ...]
+                       [--only-order] [--only-ao] [--only-matte] [--only-views]
+                       [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
 with the scene and the rays resident, on three batches of bench.py's frames:
@@ -65,6 +66,12 @@ primary hits, with and without the mask, next to the unfused path (torch
 segments, visible, a torch fold); the containment of the refraction test points
 of the same hits.  --only-matte runs these alone and keeps FILE's other
 sections.
+
+Many views in one launch (rtg_render_views_device, csrc/rtg_camera.hip) get
+rows under "views" (views_rows below): a bake of 256 probes x 6 cube faces of
+32 x 32 pixels, as one launch, as 1536 single-view launches and through the ray
+generator plus the batch ray tracer, next to one frame of the same pixel count.
+--only-views runs these alone and keeps FILE's other sections.
 GPU only.
 """
 import argparse
@@ -109,16 +116,21 @@ def timed(fn, stream, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def measure(fns, rounds, window_ms=300.0, raw=None):
+def measure(fns, rounds, window_ms=300.0, raw=None, min_reps=3, names=None):
     """Median, min and max ms per launch of each fn, interleaved round by round
-    (raw: a list that receives each fn's per-round times)."""
+    (raw: a list that receives each fn's per-round times; min_reps: launches per
+    round of an fn slower than the window; names: report each fn's first timing
+    on stderr as it is taken)."""
     s = torch.cuda.current_stream()
     reps = []
-    for fn in fns:
-        for _ in range(3):
+    for k, fn in enumerate(fns):
+        for _ in range(min_reps):
             fn()
         torch.cuda.synchronize()
-        reps.append(max(3, min(2000, int(window_ms / max(timed(fn, s, 2), 1e-3)))))
+        first = timed(fn, s, min(2, min_reps))
+        reps.append(max(min_reps, min(2000, int(window_ms / max(first, 1e-3)))))
+        if names:
+            print(f"  {names[k]}: {first:.4f} ms, {reps[-1]} per round", file=sys.stderr, flush=True)
     t = [[] for _ in fns]
     for _ in range(rounds):
         for k, fn in enumerate(fns):
@@ -445,6 +457,108 @@ def contains_rows(args, W, H, rays, stream):
     return out
 
 
+def probe_positions(sph, n, seed=42):
+    """n seeded positions, uniform in the box of the scene's spheres."""
+    c = sph["pos"].astype(np.float64)
+    r = np.abs(sph["radius"].astype(np.float64))[:, None]
+    lo, hi = (c - r).min(0), (c + r).max(0)
+    return np.random.default_rng(seed).uniform(lo, hi, (n, 3))
+
+
+def views_rows(args, stream):
+    """A probe bake on C3 (stack size 6) and C5 (stack size 8) at aa = 1: 256
+    probe positions (probe_positions) x the 6 poses of rtg_camera_cube = 1536
+    views of 32 x 32 at zoom -1, the pose table resident.  Round by round in
+    one process:
+      (a) views        one rtg_render_views_device;
+      (b) per_view     1536 rtg_render_camera_device calls on one stream (the
+                       C entry point through prepared ctypes arguments: the
+                       time includes the host's enqueue of 1536 launches, which
+                       is what a caller of that route pays);
+      (c) unfused      1536 rtg_camera_rays_device calls into one ray buffer
+                       (24 B per ray), one rtg_raytrace_device over it and a
+                       torch fold (at aa = 1: one multiply by 1/nS); the row
+                       is the per-round sum of the three;
+      ceiling          one rtg_render_camera_device of a 1536 x 1024 frame (the
+                       same pixel count) from the first pose.
+    Reported, not gated: the ratios, and whether (a) is faster than (b) and
+    than (c) by more than the slower one's min-max spread.  Gated: the frames of
+    (a), (b) and (c) are the same words."""
+    import ctypes
+    nP, Wv, Hv, aa, zoom = 256, 32, 32, 1.0, -1.0
+    nV, per = nP * 6, Wv * Hv
+    fa = torch.empty((nV, Hv, Wv, 3), dtype=torch.float32, device="cuda")
+    fb = torch.empty((nV, Hv, Wv, 3), dtype=torch.float32, device="cuda")
+    fc = torch.empty((nV, Hv, Wv, 3), dtype=torch.float32, device="cuda")
+    big = torch.empty((1024, 1536, 3), dtype=torch.float32, device="cuda")
+    gen = torch.empty((nV * per, 6), dtype=torch.float32, device="cuda")
+    col = torch.empty((nV * per, 3), dtype=torch.float32, device="cuda")
+    L = R.lib()
+    vp, q = ctypes.c_void_p, ctypes.c_void_p(stream) if stream else None
+    out = {"probes": nP, "views": nV, "width": Wv, "height": Hv, "alias_factor": aa, "zoom": zoom,
+           "pixels": nV * per, "ray_buffer_bytes": nV * per * 24}
+    ok = True
+    for name in ("c3", "c5"):
+        S = CONFIGS[name][4] + 1
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        cams = np.concatenate([R.camera_cube(e) for e in probe_positions(sph, nP)])
+        d_cams = torch.from_numpy(cams.view(F).reshape(nV, 12)).cuda()
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        h = ctx._h
+        pose_p = [vp(cams.ctypes.data + 48 * v) for v in range(nV)]
+        dst_p = [vp(fb.data_ptr() + 12 * per * v) for v in range(nV)]
+        gen_p = [vp(gen.data_ptr() + 24 * per * v) for v in range(nV)]
+        zf, af = ctypes.c_float(zoom), ctypes.c_float(aa)
+
+        def per_view():
+            for v in range(nV):
+                if L.rtg_render_camera_device(h, pose_p[v], Wv, Hv, zf, af, S, dst_p[v], q):
+                    raise R.RtgError(L.rtg_last_error().decode())
+
+        def generate():
+            for v in range(nV):
+                if L.rtg_camera_rays_device(h, pose_p[v], Wv, Hv, zf, af, gen_p[v], q):
+                    raise R.RtgError(L.rtg_last_error().decode())
+
+        raw = []
+        va, vb, vg, vt, vf, vc = measure(
+            [lambda: ctx.render_views(d_cams.data_ptr(), nV, Wv, Hv, fa.data_ptr(), zoom, aa, S,
+                                      stream),
+             per_view, generate,
+             lambda: ctx.raytrace_device(gen.data_ptr(), nV * per, col.data_ptr(), S, stream),
+             lambda: torch.mul(col, 1.0 / (aa * aa), out=fc.view(-1, 3)),
+             lambda: ctx.render_camera(cams[0], 1536, 1024, big.data_ptr(), zoom, aa, S, stream)],
+            args.rounds, raw=raw, min_reps=1,  # (a per-view bake is 1536 launches: one a round)
+            names=[f"views {name} {k}" for k in ("one launch", "per view", "generator per view",
+                                                 "raytrace", "fold", "one frame")])
+        ctx.close()
+        words = lambda t: t.view(torch.int32)  # noqa: E731
+        equal = bool((words(fa) == words(fb)).all()) and bool((words(fa) == words(fc)).all())
+        ok = ok and equal
+        rows = _spread_rows({"unfused": [a + b + c for a, b, c in zip(raw[2], raw[3], raw[4])]})
+        un = rows["unfused"]
+
+        def beats(x):
+            return bool(x["ms_median"] - va["ms_median"] > x["ms_max"] - x["ms_min"])
+
+        out[name] = {
+            "stack_size": S, "views": va, "per_view": vb, "generator_per_view": vg,
+            "raytrace": vt, "fold_torch": vf, **rows, "ceiling_one_frame": vc,
+            "per_view_over_views": round(vb["ms_median"] / va["ms_median"], 3),
+            "unfused_over_views": round(un["ms_median"] / va["ms_median"], 3),
+            "views_over_ceiling": round(va["ms_median"] / vc["ms_median"], 3),
+            "views_faster_than_per_view_by_more_than_its_spread": beats(vb),
+            "views_faster_than_unfused_by_more_than_its_spread": beats(un),
+            "Mpixels_per_s": round(nV * per / (va["ms_median"] * 1e-3) / 1e6, 1),
+            "lit_share_of_pixels": round(float((fa != 0).any(-1).to(torch.float64).mean()), 4),
+            "views_equal_per_view_and_unfused": equal}
+        print(f"views {name}: one launch {va['ms_median']} ms, per view {vb['ms_median']} ms, "
+              f"unfused {un['ms_median']} ms, one frame {vc['ms_median']} ms", file=sys.stderr,
+              flush=True)
+    return out, ok
+
+
 def finish(args, res, ok):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -467,6 +581,8 @@ def main():
     ap.add_argument("--only-matte", action="store_true",
                     help="the direct light's and the containment's rows alone, put into FILE "
                          "next to what it holds")
+    ap.add_argument("--only-views", action="store_true",
+                    help="the many-views rows alone, put into FILE next to what it holds")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
     ap.add_argument("--order-alt-json", default=[], action="append",
@@ -477,6 +593,15 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_rays: needs a GPU")
+    if args.only_views:  # (before the frame's ray buffers: it needs none of them)
+        res = {}
+        if os.path.exists(args.out):  # the other sections stay as they were measured
+            with open(args.out) as f:
+                res = json.load(f)
+        res["views_commit"] = args.commit
+        res["views"], ok = views_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["views"]["rounds"] = args.rounds
+        finish(args, res, ok)
     W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
     assert (W, H) == CONFIGS["c5"][:2]
     n = W * H
@@ -595,7 +720,9 @@ def main():
     res["ao"], ao_ok = ao_rows(args, W, H, rays, stream)
     res["matte"], matte_ok = matte_rows(args, W, H, rays, stream)
     res["contains"] = contains_rows(args, W, H, rays, stream)
-    ok = ok and cam_ok and order_ok and ao_ok and matte_ok
+    del rays
+    res["views"], views_ok = views_rows(args, stream)
+    ok = ok and cam_ok and order_ok and ao_ok and matte_ok and views_ok
     if args.mapping_json:
         with open(args.mapping_json) as f:
             other = json.load(f)["camera"]
