@@ -730,8 +730,12 @@ inline void bvh_grow(const double c[3], double r, double pmax, double omax, floa
   }
 }
 
-inline bool build_bvh(const rtg_sphere* spheres, unsigned n, PackedScene* ps) {
+// depthOut (tests): the depth of the tree that was built, kept or refused;
+// -1 when none was attempted.
+inline bool build_bvh(const rtg_sphere* spheres, unsigned n, PackedScene* ps,
+                      int* depthOut = nullptr) {
   ps->bvhNodes.clear();
+  if (depthOut) *depthOut = -1;
   if (n <= kMaskMaxSpheres) return false;
   auto finite = [](double v) { return v == v && fabs(v) <= 1e30; };
   for (unsigned i = 0; i < n; ++i)
@@ -875,6 +879,7 @@ inline bool build_bvh(const rtg_sphere* spheres, unsigned n, PackedScene* ps) {
     return node;
   };
   build(0, n, 0);
+  if (depthOut) *depthOut = maxDepth;
   if (maxDepth > 20) {  // the wave stack holds 3 * depth + 1 <= 64 entries
     ps->bvhNodes.clear();
     return false;

@@ -1496,6 +1496,12 @@ RTG_HD bool slab_pass(const BoxQ& b, V3 lo, V3 hi, float reach, float& tn) {
 // back (LDS accesses of one wave complete in order); the popped index is made
 // scalar with v_readfirstlane.  (A stack in the lanes of a VGPR does not
 // survive the divergent callers: copies of a VGPR only move active lanes.)
+#if defined(RTG_BVH_STACK_STATS)
+inline int* bvh_stack_stats() {  // {high-water mark, a push at sp == 64 was asked for}
+  static int s[2];
+  return s;
+}
+#endif
 struct BvhStack {
 #if defined(__HIP_DEVICE_COMPILE__)
   int* v;
@@ -1513,7 +1519,18 @@ struct BvhStack {
   int v[64];
   unsigned sp = 0;
   explicit BvhStack(int*) {}
+#if defined(RTG_BVH_STACK_STATS)  // tests/hostsim only: occupancy of the 64 entries
+  void push(int x) {
+    if (sp == 64) {  // recorded, not performed
+      bvh_stack_stats()[1] = 1;
+      return;
+    }
+    v[sp++] = x;
+    if ((int)sp > bvh_stack_stats()[0]) bvh_stack_stats()[0] = (int)sp;
+  }
+#else
   void push(int x) { v[sp++] = x; }
+#endif
   int pop() { return v[--sp]; }
 #endif
   RTG_HD bool empty() const { return sp == 0; }

@@ -9,6 +9,8 @@
 
 #include <vector>
 
+// BvhStack's occupancy counters (hostsim_bvh_stack), before anything includes rtg_trace.h
+#define RTG_BVH_STACK_STATS 1
 #include "rtg.h"
 #include "rtg_internal.h"
 #include "rtg_scene_pack.h"
@@ -876,6 +878,34 @@ extern "C" void hostsim_list_records(const rtg_sphere* spheres, unsigned n,
   if (ps.capOff.empty()) return;
   out[0] = ps.capRec.size() / rtg::kCapWords - rtg::kCapPad;  // without the padding records
   out[1] = ps.ovRec.size() / rtg::kListWords - rtg::kOvPad;
+}
+
+// What build_bvh and sphere_lists make of a scene: out = {1 tree kept / 0
+// refused or not attempted, nodes of the kept tree, depth of the tree built
+// (kept or refused; -1 when none was attempted: n <= 64, a non-finite or too
+// large scene), 1 when the scene gets sphere lists under these lights}.
+extern "C" void hostsim_bvh_stats(const rtg_sphere* spheres, unsigned n, const rtg_light* lights,
+                                  unsigned m, long* out) {
+  rtg::PackedScene ps;
+  int depth = -1;
+  const bool built = rtg::build_bvh(spheres, n, &ps, &depth);
+  out[0] = built ? 1 : 0;
+  out[1] = (long)(ps.bvhNodes.size() / (rtg::kBvhWords * rtg::kBvhCopies));
+  out[2] = depth;
+  out[3] = 0;
+  if (!built) return;
+  rtg::sphere_lists(spheres, n, lights, m, &ps);
+  out[3] = ps.capOff.empty() ? 0 : 1;
+}
+
+// BvhStack's occupancy over the renders since the last reset: out = {the most
+// entries held at once, 1 when a push was asked for with all 64 in use (it is
+// not performed)}.
+extern "C" void hostsim_bvh_stack(long* out, int reset) {
+  int* s = rtg::bvh_stack_stats();
+  out[0] = s[0];
+  out[1] = s[1];
+  if (reset) s[0] = s[1] = 0;
 }
 
 // `behind` (rtg_trace.h) never rejects a sphere the reference's root test
