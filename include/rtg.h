@@ -27,6 +27,9 @@
  *   the camera of main.cpp:384-436, moved to a pose   rtg_camera_look_at, rtg_camera_rays[_device|_host],
  *     (fixed at 0 looking down -z in the reference)    rtg_render_camera[_device|_host]
  *   (many poses, one frame each: probes, cube maps)    rtg_render_views[_device|_host], rtg_camera_cube
+ *   (groups of views folded by a weight table: SH       rtg_views_fold[_device|_host],
+ *     probes, ambient cubes)                              rtg_render_views_fold[_device|_host],
+ *                                                         rtg_cube_sh_weights
  *   (hemisphere visibility of a hit point: the caller's  rtg_ao[_device|_host],
  *     loop over hasClearLineOfSight in the reference)    rtg_ao_segments[_device|_host]
  *   calculateMatte for a caller's own hit points       rtg_matte[_device|_host]
@@ -618,6 +621,125 @@ int rtg_render_views_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_
  * left column are, at aliasFactor 1, directions the side faces' top rows have
  * too.)  The only error is a null pointer. */
 int rtg_camera_cube(const rtg_vec* eye, rtg_camera out[6]);
+
+/* ---- views folded into per-group coefficients: SH light probes ----
+ * A probe is not its faces but a handful of numbers: nine SH coefficients,
+ * six ambient-cube colours, a mean.  These calls reduce GROUPS of views with
+ * a caller-owned weight table, in a float summation order that is defined
+ * here, so the result is the same words on the host and on every GPU.
+ *
+ * INPUTS.  nViews frames of W x H pixels (rtg_vec), view-major, as
+ * rtg_render_views* writes them.  A group is G = viewsPerGroup >= 1
+ * consecutive views; nViews is a multiple of G and nGroups = nViews / G.
+ * K = weights, 1 <= K <= RTG_FOLD_MAX_WEIGHTS.  ONE weight table of G * W * H
+ * * K floats is shared by all groups: w[e * K + k] is weight k of texel e =
+ * (f * H + y) * W + x, f the view's index inside its group.  The caller owns
+ * the table (a device pointer in the device calls), so no transcendental
+ * function is evaluated inside the defined arithmetic, as with rtg_ao*'s
+ * direction table.
+ *
+ * ARITHMETIC, all in float with no contraction and in this order:
+ *   term     for texel e of group g, weight k, channel q:
+ *              term = w[e * K + k] * pix.q,  pix the pixel of view g * G + f.
+ *            With RTG_FOLD_SKIP_NONFINITE a pixel with any word whose exponent
+ *            field is all ones (NaN, +-inf) gives +0.f for every k and q and
+ *            counts one towards the group's `skipped`.  The weight is never
+ *            tested.
+ *   tile     a view is cut into the views kernel's 8 x 8 tiles, row-major;
+ *            lane l is pixel (l % 8, l / 8) of the tile, a lane outside the
+ *            frame holds +0.f.  For s = 1, 2, 4, 8, 16, 32 in that order:
+ *              v[l] = v[l] + v[l + s]  for every l that is a multiple of 2s.
+ *            The tile's sum is v[0] (what lane 0 of a wave holds after an xor
+ *            butterfly in that order).
+ *   group    acc = +0.f; for f = 0 .. G-1, for each tile of view g * G + f in
+ *            tile order: acc = acc + tilesum.   out[g * K + k].q = acc, NaN
+ *            words stored as 0xFFC00000, as every record's.
+ *   skipped  skipped[g] (may be null) is the group's count of skipped texels,
+ *            0 without the flag.
+ * NaN, infinite and -0 inputs follow the arithmetic as written.
+ *
+ * rtg_views_fold_host restates this in plain loops: the yardstick.
+ * rtg_views_fold_device folds frames already in device memory (its context
+ * names the device; it needs no scene).  rtg_render_views_fold_device is the
+ * FUSED call: poses in, coefficients out, no frame written anywhere; word for
+ * word rtg_views_fold_host over rtg_render_views_host(walk 0)'s frames.  It
+ * follows rtg_context_set_semantics, takes none of the context's render
+ * scratch and allocates nothing.  Both device calls are asynchronous on
+ * `stream` and need a caller-owned scratch for their tile partials, 3K + 1
+ * words per tile of every view (rtg_views_fold_scratch gives the bytes):
+ * 16-byte aligned, and the call's until the call has finished on the stream.
+ * `params` is host memory in every call, read before the call returns.
+ *
+ * nViews == 0 is RTG_OK: nothing is launched, nothing is written, and the
+ * pose table, the frames and the scratch may be null.  RTG_ERR_INVALID with a
+ * message, before any GPU call, for everything rtg_render_views* rejects, a
+ * null params, weight table, output or (nViews > 0) scratch, G == 0, nViews
+ * not a multiple of G, K outside 1..RTG_FOLD_MAX_WEIGHTS, an unknown flag, a
+ * scratch that is too small or off 16-byte alignment, and G * W * H * K floats
+ * or the scratch size not representable in size_t.
+ *
+ * Out of scope: per-group weight tables, per-view sizes, a tree-shaped group
+ * sum (the sequential one is the definition; it is slow only for very large
+ * faces), irradiance convolution or windowing, folds over G-buffers or ray
+ * batches, row shards and multi-GPU. */
+#define RTG_FOLD_MAX_WEIGHTS 16
+#define RTG_FOLD_SKIP_NONFINITE 1  /* flags: a NaN or infinite pixel adds +0.f and is counted */
+typedef struct rtg_fold_params {
+  unsigned viewsPerGroup; /* G >= 1; nViews is a multiple of it */
+  unsigned weights;       /* K, 1..RTG_FOLD_MAX_WEIGHTS */
+  unsigned flags;         /* RTG_FOLD_* bits; an unknown bit is RTG_ERR_INVALID */
+} rtg_fold_params;
+/* Bytes of tile partials the device calls need: nViews * tiles * (3K + 1) * 4,
+ * tiles = ceil(W / 8) * ceil(H / 8). */
+int rtg_views_fold_scratch(size_t nViews, unsigned width, unsigned height, unsigned weights,
+                           size_t* bytes);
+/* Plain loops; the result does not depend on nthreads (threads take whole
+ * groups).  nthreads <= 0: 1. */
+int rtg_views_fold_host(const rtg_vec* frames, size_t nViews, unsigned width, unsigned height,
+                        const rtg_fold_params* params, const float* weights, rtg_vec* out,
+                        unsigned* skipped, int nthreads);
+int rtg_views_fold_device(rtg_context* ctx, const rtg_vec* framesDevice, size_t nViews,
+                          unsigned width, unsigned height, const rtg_fold_params* params,
+                          const float* weightsDevice, rtg_vec* outDevice, unsigned* skippedDevice,
+                          void* scratchDevice, size_t scratchBytes, void* stream);
+int rtg_render_views_fold_device(rtg_context* ctx, const rtg_camera* posesDevice, size_t nViews,
+                                 unsigned width, unsigned height, float zoom, float aliasFactor,
+                                 int stackSize, const rtg_fold_params* params,
+                                 const float* weightsDevice, rtg_vec* outDevice,
+                                 unsigned* skippedDevice, void* scratchDevice,
+                                 size_t scratchBytes, void* stream);
+/* One-shot: uploads the scene, the poses and the weights, allocates its own
+ * scratch, runs the fused call on `device`, downloads nGroups * K rtg_vec and
+ * (skipped not null) nGroups counts. */
+int rtg_render_views_fold(int device, const rtg_sphere* spheres, unsigned sphNum,
+                          const rtg_light* lights, unsigned lgtNum, const rtg_camera* poses,
+                          size_t nViews, unsigned width, unsigned height, float zoom,
+                          float aliasFactor, int stackSize, const rtg_fold_params* params,
+                          const float* weights, rtg_vec* outHost, unsigned* skippedHost);
+/* Renders on the host (rtg_render_views_host: walk, semantics, nthreads), then
+ * folds on the host; no GPU call. */
+int rtg_render_views_fold_host(const rtg_sphere* spheres, unsigned sphNum,
+                               const rtg_light* lights, unsigned lgtNum, const rtg_camera* poses,
+                               size_t nViews, unsigned width, unsigned height, float zoom,
+                               float aliasFactor, int stackSize, int semantics,
+                               const rtg_fold_params* params, const float* weights,
+                               rtg_vec* outHost, unsigned* skippedHost, int walk, int nthreads);
+/* A convenience, host only: real-SH projection weights for rtg_camera_cube's
+ * six faces of res x res at zoom -1, G = 6, K = bands * bands (bands 1..4),
+ * k = l * (l + 1) + m:  out[e * K + k] = Y_k(d_e) * O_e, 6 * res * res * K
+ * floats.  d_e is the normalised MEAN sample position of pixel e under its
+ * face's basis: the pixel's corner is u = -1 + 2x / res along R, v = 1 - 2y /
+ * res along U, and sample (i, j) lies 2j / (res * aliasFactor) right of it and
+ * (8/3) i / (res * aliasFactor) above it (the reference's sample step is not
+ * scaled by the aspect vertically).  O_e is the solid angle of the pixel's
+ * cell [u, u + 2 / res] x [v, v + 2 / res] seen from the eye, scaled so that
+ * the 6 * res * res values sum to 4 pi.  Y_k is the orthonormal real basis
+ * (Y_0 = 1 / (2 sqrt(pi)), m < 0 the sine terms), so folding an all-ones cube
+ * gives c_0 = 2 sqrt(pi).  Computed in double and rounded to float; its bits
+ * are NOT part of the contract, as rtg_ao_directions' are not.
+ * RTG_ERR_INVALID for a null pointer, res == 0, bands outside 1..4, an
+ * aliasFactor rtg_render_views* rejects or a table size that overflows. */
+int rtg_cube_sh_weights(unsigned res, unsigned bands, float aliasFactor, float* out);
 
 /* ---- ambient occlusion: hemisphere visibility per hit point ----
  * Hit points go in, one count of unoccluded probes per point comes out: no

@@ -24,6 +24,11 @@
 // v is bit for bit the single-view frame of pose v.  rtg_camera_cube writes
 // the six poses of a cube map.
 //
+// Many views folded into per-group coefficients (rtg_render_views_fold*,
+// views_fold_kernel): the same launch with rtg_fold.h's tile epilogue in place
+// of the pixel store, then rtg_fold.hip's stage 2; no frame is written.
+// rtg_cube_sh_weights builds the SH table for rtg_camera_cube's faces.
+//
 // This file holds the pose helpers, the generator (kernel and host form), the
 // launchers of the fused kernels (picked from stack_kernels, rtg_trace_kernels.h),
 // the pose's own argument checks (the rest are rtg_entry.h's) and the host
@@ -34,14 +39,18 @@
 // FP contract: the Makefile's FPFLAGS, as every kernel.
 #include <hip/hip_runtime.h>
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+
+#include <vector>
 
 #include "rtg.h"
 #include "rtg_camera.h"
 #include "rtg_camera_kernels.h"
 #include "rtg_entry.h"
+#include "rtg_fold.h"
 #include "rtg_host_scene.h"
 #include "rtg_rays.h"
 #include "rtg_scene_pack.h"
@@ -146,6 +155,16 @@ static int check_views_frame(const rtg_camera* poses, size_t nViews, const void*
     return RTG_ERR_INVALID;
   }
   return make_camera(W, H, zoom, aa, out);
+}
+
+// The same for rtg_render_views_fold*, whose destination is the coefficients.
+static int check_fold_views(const rtg_camera* poses, size_t nViews, const void* out, unsigned W,
+                            unsigned H, float zoom, float aa, Camera* cam) {
+  if (!out || (nViews && !poses)) {
+    rtg_set_error("render_views_fold: null %s", out ? "pose table" : "output");
+    return RTG_ERR_INVALID;
+  }
+  return make_camera(W, H, zoom, aa, cam);
 }
 
 // ... and after it (so W * H > 0): the stack size, then the batch's size, its
@@ -469,6 +488,225 @@ int rtg_render_views(int device, const rtg_sphere* spheres, unsigned sphNum,
                                                    height, zoom, aliasFactor, stackSize,
                                                    (rtg_vec*)out, nullptr);
                   });
+}
+
+// ---- many views folded into per-group coefficients (rtg_fold.h) ----
+
+int rtg_render_views_fold_host(const rtg_sphere* spheres, unsigned sphNum,
+                               const rtg_light* lights, unsigned lgtNum, const rtg_camera* poses,
+                               size_t nViews, unsigned width, unsigned height, float zoom,
+                               float aliasFactor, int stackSize, int semantics,
+                               const rtg_fold_params* params, const float* weights,
+                               rtg_vec* outHost, unsigned* skippedHost, int walk, int nthreads) {
+  rtg_clear_error();
+  Camera c;
+  unsigned tilesX = 0, tilesPerView = 0;
+  size_t blocks = 0;
+  int rc = check_fold_views(poses, nViews, outHost, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_views(nViews, width, height, stackSize, &tilesX, &tilesPerView, &blocks);
+  if (!rc) rc = check_scene_arrays("render_views_fold", spheres, sphNum, lights, lgtNum);
+  if (!rc) rc = check_semantics("render_views_fold", semantics);
+  if (!rc) rc = check_walk("render_views_fold", walk);
+  if (!rc) rc = check_sphere_count("render_views_fold", sphNum);
+  if (!rc)
+    rc = check_fold("render_views_fold", nViews, width, height, params, weights, outHost, false,
+                    nullptr, 0, &tilesX, &tilesPerView);
+  if (rc) return rc;
+  if (nViews == 0) return RTG_OK;
+  // the composition itself: the host's frames, then the host's fold
+  std::vector<rtg_vec> frames(nViews * width * height);
+  rc = rtg_render_views_host(spheres, sphNum, lights, lgtNum, poses, nViews, width, height, zoom,
+                             aliasFactor, stackSize, semantics, frames.data(), walk, nthreads);
+  if (rc) return rc;
+  return rtg_views_fold_host(frames.data(), nViews, width, height, params, weights, outHost,
+                             skippedHost, nthreads);
+}
+
+int rtg_render_views_fold_device(rtg_context* ctx, const rtg_camera* posesDevice, size_t nViews,
+                                 unsigned width, unsigned height, float zoom, float aliasFactor,
+                                 int stackSize, const rtg_fold_params* params,
+                                 const float* weightsDevice, rtg_vec* outDevice,
+                                 unsigned* skippedDevice, void* scratchDevice,
+                                 size_t scratchBytes, void* stream) {
+  rtg_clear_error();
+  SceneTables a{};
+  RayBox box{};
+  int device = 0, semantics = RTG_SEMANTICS_CPU;
+  if (!rtg_context_scene(ctx, &a, &device, &box, &semantics)) {
+    rtg_set_error("render_views_fold: no context/scene");
+    return RTG_ERR_INVALID;
+  }
+  Camera c;
+  unsigned tilesX = 0, tilesPerView = 0;
+  size_t blocks = 0;
+  int rc = check_fold_views(posesDevice, nViews, outDevice, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_views(nViews, width, height, stackSize, &tilesX, &tilesPerView, &blocks);
+  if (!rc && (uintptr_t)posesDevice % 4) {
+    rtg_set_error("render_views_fold: pose table not 4-byte aligned");
+    rc = RTG_ERR_INVALID;
+  }
+  if (!rc)
+    rc = check_fold("render_views_fold", nViews, width, height, params, weightsDevice, outDevice,
+                    true, scratchDevice, scratchBytes, &tilesX, &tilesPerView);
+  if (rc) return rc;
+  if (nViews == 0) return RTG_OK;
+  DeviceGuard deviceGuard;  // (after the checks: no GPU call before them)
+  const bool bvh = a.bvhNodes != nullptr;
+  const StackKernels* sk = stack_kernels(stackSize);
+  const ViewsFoldFn fn = sk ? sk->views_fold(bvh, semantics == RTG_SEMANTICS_OPENCL) : nullptr;
+  if (!fn) {  // a missing kernel is an error, never another path
+    rtg_set_error("render_views_fold: no kernel for stackSize %d", stackSize);
+    return RTG_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(device));
+  const FoldArgs fa = {weightsDevice, static_cast<unsigned*>(scratchDevice), params->weights,
+                       params->viewsPerGroup, params->flags & RTG_FOLD_SKIP_NONFINITE};
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64), raytrace_lds_bytes(stackSize, bvh),
+                     (hipStream_t)stream, a, box, c,
+                     reinterpret_cast<const CamPose*>(posesDevice), width, height, tilesX,
+                     tilesPerView, fa);
+  HIP_TRY(hipGetLastError());
+  return launch_fold_stage2(scratchDevice, nViews, tilesPerView, *params, outDevice,
+                            skippedDevice, (hipStream_t)stream);
+}
+
+int rtg_render_views_fold(int device, const rtg_sphere* spheres, unsigned sphNum,
+                          const rtg_light* lights, unsigned lgtNum, const rtg_camera* poses,
+                          size_t nViews, unsigned width, unsigned height, float zoom,
+                          float aliasFactor, int stackSize, const rtg_fold_params* params,
+                          const float* weights, rtg_vec* outHost, unsigned* skippedHost) {
+  rtg_clear_error();
+  Camera c;
+  unsigned tilesX = 0, tilesPerView = 0;
+  size_t blocks = 0;
+  int rc = check_fold_views(poses, nViews, outHost, width, height, zoom, aliasFactor, &c);
+  if (!rc) rc = check_views(nViews, width, height, stackSize, &tilesX, &tilesPerView, &blocks);
+  if (!rc) rc = check_scene_arrays("render_views_fold", spheres, sphNum, lights, lgtNum);
+  if (!rc)
+    rc = check_fold("render_views_fold", nViews, width, height, params, weights, outHost, false,
+                    nullptr, 0, &tilesX, &tilesPerView);
+  if (rc) return rc;
+  if (nViews == 0) return RTG_OK;
+  DeviceGuard deviceGuard;  // (after the checks: no GPU call before them)
+  const size_t K = params->weights, nGroups = nViews / params->viewsPerGroup;
+  const size_t tableBytes = (size_t)params->viewsPerGroup * width * height * K * sizeof(float);
+  const size_t scratchBytes = nViews * tilesPerView * fold_tile_words(params->weights) * 4;
+  const size_t outBytes = nGroups * K * sizeof(rtg_vec);
+  // the poses go up through one_shot; the table, the counts and the scratch here
+  void *dW = nullptr, *dSkipped = nullptr, *dScratch = nullptr;
+  HIP_TRY(hipSetDevice(device));
+  rc = RTG_OK;
+  if (hipMalloc(&dW, tableBytes) != hipSuccess || hipMalloc(&dScratch, scratchBytes) != hipSuccess ||
+      (skippedHost && hipMalloc(&dSkipped, nGroups * sizeof(unsigned)) != hipSuccess)) {
+    rtg_set_error("hipMalloc(%zu + %zu) failed", tableBytes, scratchBytes);
+    rc = RTG_ERR_NOMEM;
+  }
+  if (!rc && hipMemcpy(dW, weights, tableBytes, hipMemcpyHostToDevice) != hipSuccess) {
+    rtg_set_error("upload of %zu bytes failed", tableBytes);
+    rc = RTG_ERR_HIP;
+  }
+  if (!rc)
+    rc = one_shot(device, spheres, sphNum, lights, lgtNum, poses, nViews * sizeof(rtg_camera),
+                  outHost, outBytes, [&](rtg_context* ctx, const void* in, void* out) {
+                    const int r = rtg_render_views_fold_device(
+                        ctx, (const rtg_camera*)in, nViews, width, height, zoom, aliasFactor,
+                        stackSize, params, (const float*)dW, (rtg_vec*)out, (unsigned*)dSkipped,
+                        dScratch, scratchBytes, nullptr);
+                    if (r || !skippedHost) return r;
+                    // (a blocking copy on the null stream: after both kernels)
+                    if (hipMemcpy(skippedHost, dSkipped, nGroups * sizeof(unsigned),
+                                  hipMemcpyDeviceToHost) != hipSuccess) {
+                      rtg_set_error("readback of the skip counts failed");
+                      return RTG_ERR_HIP;
+                    }
+                    return RTG_OK;
+                  });
+  (void)hipFree(dW);
+  (void)hipFree(dSkipped);
+  (void)hipFree(dScratch);
+  return rc;
+}
+
+// Real SH of bands l = 0 .. bands-1 at the unit vector (x, y, z), k = l(l+1)+m.
+static void real_sh(unsigned bands, double x, double y, double z, double* Y) {
+  Y[0] = 0.28209479177387814;
+  if (bands < 2) return;
+  Y[1] = 0.4886025119029199 * y;
+  Y[2] = 0.4886025119029199 * z;
+  Y[3] = 0.4886025119029199 * x;
+  if (bands < 3) return;
+  Y[4] = 1.0925484305920792 * (x * y);
+  Y[5] = 1.0925484305920792 * (y * z);
+  Y[6] = 0.31539156525252005 * (3.0 * (z * z) - 1.0);
+  Y[7] = 1.0925484305920792 * (x * z);
+  Y[8] = 0.5462742152960396 * (x * x - y * y);
+  if (bands < 4) return;
+  Y[9] = 0.5900435899266435 * (y * (3.0 * (x * x) - y * y));
+  Y[10] = 2.890611442640554 * ((x * y) * z);
+  Y[11] = 0.4570457994644658 * (y * (5.0 * (z * z) - 1.0));
+  Y[12] = 0.3731763325901154 * (z * (5.0 * (z * z) - 3.0));
+  Y[13] = 0.4570457994644658 * (x * (5.0 * (z * z) - 1.0));
+  Y[14] = 1.445305721320277 * (z * (x * x - y * y));
+  Y[15] = 0.5900435899266435 * (x * (x * x - 3.0 * (y * y)));
+}
+
+// The corner term of a rectangle's solid angle seen from distance 1.
+static double corner_angle(double u, double v) { return atan2(u * v, sqrt((u * u + v * v) + 1.0)); }
+
+int rtg_cube_sh_weights(unsigned res, unsigned bands, float aliasFactor, float* out) {
+  rtg_clear_error();
+  if (!out) {
+    rtg_set_error("cube_sh_weights: null pointer");
+    return RTG_ERR_INVALID;
+  }
+  if (bands < 1 || bands > 4) {
+    rtg_set_error("cube_sh_weights: bands %u outside [1, 4]", bands);
+    return RTG_ERR_INVALID;
+  }
+  Camera c;
+  const int rc = make_camera(res, res, -1.f, aliasFactor, &c);  // res > 0, the range, nAA
+  if (rc) return rc;
+  const unsigned K = bands * bands;
+  if (6 > SIZE_MAX / sizeof(float) / K / ((size_t)res * res)) {
+    rtg_set_error("cube_sh_weights: table too large (res %u)", res);
+    return RTG_ERR_INVALID;
+  }
+  const double cell = 2.0 / (double)res;
+  // the mean of sample offsets 0 .. nAA-1, right of and above the corner
+  const double mean = c.nAA > 0 ? 0.5 * (double)(c.nAA - 1) : 0.0;
+  const double du = mean * (2.0 / ((double)res * (double)aliasFactor));
+  const double dv = mean * ((8.0 / 3.0) / ((double)res * (double)aliasFactor));
+  // the cells' solid angles: one face's, the same on all six
+  std::vector<double> omega((size_t)res * res);
+  double total = 0.0;
+  for (unsigned y = 0; y < res; ++y) {
+    for (unsigned x = 0; x < res; ++x) {
+      const double u0 = -1.0 + cell * (double)x, v0 = 1.0 - cell * (double)y;
+      const double u1 = u0 + cell, v1 = v0 + cell;
+      const double o = ((corner_angle(u1, v1) - corner_angle(u0, v1)) - corner_angle(u1, v0)) +
+                       corner_angle(u0, v0);
+      omega[(size_t)y * res + x] = o;
+      total += o;
+    }
+  }
+  const double scale = (4.0 * 3.14159265358979323846) / (6.0 * total);
+  for (unsigned f = 0; f < 6; ++f) {
+    const signed char(*t)[3] = kCubeAxes[f];
+    for (unsigned y = 0; y < res; ++y) {
+      for (unsigned x = 0; x < res; ++x) {
+        const double u = (-1.0 + cell * (double)x) + du, v = (1.0 - cell * (double)y) + dv;
+        double d[3];
+        for (int q = 0; q < 3; ++q) d[q] = ((double)t[0][q] + u * (double)t[1][q]) + v * (double)t[2][q];
+        const double len = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        double Y[16];
+        real_sh(bands, d[0] / len, d[1] / len, d[2] / len, Y);
+        const size_t e = ((size_t)f * res + y) * res + x;
+        const double o = omega[(size_t)y * res + x] * scale;
+        for (unsigned k = 0; k < K; ++k) out[e * K + k] = (float)(Y[k] * o);
+      }
+    }
+  }
+  return RTG_OK;
 }
 
 }  // extern "C"

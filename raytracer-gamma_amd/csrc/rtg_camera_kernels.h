@@ -8,6 +8,7 @@
 #pragma once
 
 #include "rtg_camera.h"
+#include "rtg_fold.h"
 #include "rtg_raytrace_kernels.h"
 
 namespace rtg {
@@ -19,6 +20,7 @@ namespace rtg {
 // against 93.7 ms on C5 at aa = 1.
 constexpr unsigned kCamTileW = 8, kCamTileH = 8;
 static_assert(kCamTileW * kCamTileH == 64, "one lane per pixel of the tile");
+static_assert(kCamTileW == kFoldTileW && kCamTileH == kFoldTileH, "rtg.h's fold is over these tiles");
 
 // One wave's tile of one W x H frame: tile `tile` is (tile % tilesX,
 // tile / tilesX), `dst` the frame's first pixel.  The LDS image and the scene
@@ -85,6 +87,47 @@ __global__ __launch_bounds__(64) void views_kernel(const SceneTables a, const Ra
                             dst + (size_t)view * W * H);
 }
 
+// Many poses folded into per-group coefficients (rtg_render_views_fold*): the
+// grid, the pose read and the trace are views_kernel's, and no frame is
+// written.  camera_tile lets a lane outside the frame LEAVE before the trace;
+// here such a lane only steps round it (the queries' wave-level tests are
+// still over the lanes present, so a traced pixel is camera_tile's bit for
+// bit) and comes back holding +0.f, because the epilogue's tree sum
+// (fold_tile, rtg_fold.h) reads all 64 lanes.  The pixel is folded as
+// store_colour_dev would have stored it.
+template <int S, bool kBvh, bool kCL>
+__global__ __launch_bounds__(64) void views_fold_kernel(const SceneTables a, const RayBox box,
+                                                        const Camera cam,
+                                                        const CamPose* __restrict__ poses,
+                                                        unsigned W, unsigned H, unsigned tilesX,
+                                                        unsigned tilesPerView, const FoldArgs fa) {
+  const unsigned view = blockIdx.x / tilesPerView;
+  const unsigned tile = blockIdx.x - view * tilesPerView;
+  const CamPose pose = poses[view];  // view < nViews: 48 B of the table
+  extern __shared__ float4 lds4[];
+  RayScene<kBvh> sc;
+  bind_raytrace_scene<S>(sc, a, lds4);
+  const size_t px = (size_t)(tile % tilesX) * kCamTileW + threadIdx.x % kCamTileW;
+  const size_t py = (size_t)(tile / tilesX) * kCamTileH + threadIdx.x / kCamTileW;
+  const bool live = px < W && py < H;
+  V3 pix = v3(0.f, 0.f, 0.f);
+  if (live) {
+    const unsigned x = (unsigned)px, y = (unsigned)py;
+    for (int i = 0; i < cam.nAA; ++i) {
+      for (int j = 0; j < cam.nAA; ++j) {
+        const V3 d = camera_dir(cam, pose, x, y, i, j);
+        V3 c = trace_ray<S, kCL, kBvh>(sc, box, pose.eye, d);
+        c = vsmul(cam.inv, c);
+        pix = vadd(pix, c);
+      }
+    }
+  }
+  // the lane's texel in its group's table: K consecutive floats, read when live
+  const float* w = fa.weights + (((size_t)(view % fa.G) * H + py) * W + px) * fa.K;
+  fold_tile(live, canon_nan(pix.x), canon_nan(pix.y), canon_nan(pix.z), w, fa.K, fa.skip != 0,
+            fa.partials + (size_t)blockIdx.x * fold_tile_words(fa.K));
+}
+
 // bvh: the scene has a BVH (SceneTables::bvhNodes); cl: RTG_SEMANTICS_OPENCL.
 template <int S>
 static CameraFn camera_fn(bool bvh, bool cl) {
@@ -95,6 +138,11 @@ template <int S>
 static ViewsFn views_fn(bool bvh, bool cl) {
   if (bvh) return cl ? views_kernel<S, true, true> : views_kernel<S, true, false>;
   return cl ? views_kernel<S, false, true> : views_kernel<S, false, false>;
+}
+template <int S>
+static ViewsFoldFn views_fold_fn(bool bvh, bool cl) {
+  if (bvh) return cl ? views_fold_kernel<S, true, true> : views_fold_kernel<S, true, false>;
+  return cl ? views_fold_kernel<S, false, true> : views_fold_kernel<S, false, false>;
 }
 
 }  // namespace rtg

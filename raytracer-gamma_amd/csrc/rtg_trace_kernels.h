@@ -1198,6 +1198,7 @@ static TraceFn trace_fn(int variant, bool bvh, int list) {
 struct RayBox;   // rtg_rays.h
 struct KeyBox;   // rtg_order.h
 struct CamPose;  // rtg_camera.h
+struct FoldArgs;  // rtg_fold.h
 
 // THE list of stack capacities: X(k) for every k an object rtg_trace_s<k>.o is
 // built for (the Makefile's SVALS).
@@ -1218,14 +1219,18 @@ typedef void (*CameraFn)(const SceneTables, const RayBox, const Camera, const Ca
 // ... and its many-views form (views_kernel: a pose table in device memory).
 typedef void (*ViewsFn)(const SceneTables, const RayBox, const Camera, const CamPose*, unsigned,
                         unsigned, unsigned, unsigned, rtg_vec*);
+// ... and the views folded into coefficients (views_fold_kernel: no frame).
+typedef void (*ViewsFoldFn)(const SceneTables, const RayBox, const Camera, const CamPose*,
+                            unsigned, unsigned, unsigned, unsigned, const FoldArgs);
 
 // What one per-S object (rtg_trace_s<S>.hip) exports: its kernels by variant
-// (trace_fn<S>, raytrace_fn<S>, camera_fn<S>, views_fn<S>).
+// (trace_fn<S>, raytrace_fn<S>, camera_fn<S>, views_fn<S>, views_fold_fn<S>).
 struct StackKernels {
   TraceFn (*trace)(int variant, bool bvh, int list);
   RayTraceFn (*raytrace)(bool bvh, bool cl);
   CameraFn (*camera)(bool bvh, bool cl);
   ViewsFn (*views)(bool bvh, bool cl);
+  ViewsFoldFn (*views_fold)(bool bvh, bool cl);
 };
 #define RTG_X(k) const StackKernels* stack_kernels_s##k();
 RTG_FOR_EACH_S(RTG_X)

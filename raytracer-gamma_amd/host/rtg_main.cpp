@@ -59,6 +59,11 @@ static void usage() {
   printf("      --cube       EYE     Render the six cube-map faces at ex,ey,ez (rtg_camera_cube: +X,\n");
   printf("                           -X, +Y, -Y, +Z, -Z) the same way; square frames at zoom -1\n");
   printf("                           (--width defaults to --height and the reverse, both to 64)\n");
+  printf("      --sh         BANDS   With --cube: fold the faces into the probe's BANDS^2 real-SH RGB\n");
+  printf("                           coefficients (1..4 bands; rtg_cube_sh_weights, the fused\n");
+  printf("                           rtg_render_views_fold_device) instead of writing them; needs\n");
+  printf("      --sh-out     FILE    The coefficients as text, one line \"r g b\" per k = l(l+1)+m,\n");
+  printf("                           %%.9g: the floats read back exactly\n");
   printf("      --ao         SPEC    Also write the frame's ambient occlusion: K,radius[,bias[,seed]]\n");
   printf("                           (K probes of rtg_ao_directions(K) per primary hit at aa 1, from\n");
   printf("                           --camera or the identity pose; bias defaults to 0.001; a seed\n");
@@ -112,6 +117,8 @@ int main(int argc, char** argv) {
   std::string viewsIn;  // --views
   bool cube = false, haveW = false, haveH = false, haveZoom = false;
   rtg_vec cubeEye = {0.f, 0.f, 0.f};
+  unsigned shBands = 0;  // --sh
+  std::string shOut;     // --sh-out
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* opt) -> const char* {
       if (++i >= argc) {
@@ -186,6 +193,13 @@ int main(int argc, char** argv) {
         return 1;
       }
       cube = true;
+    } else if (!strcmp(a, "--sh")) {
+      if (!parse_uint(need(a), &shBands) || shBands < 1 || shBands > 4) {
+        printf("Invalid SH band count (1..4)\n");
+        return 1;
+      }
+    } else if (!strcmp(a, "--sh-out")) {
+      shOut = need(a);
     } else if (!strcmp(a, "--ao")) {
       char tail = 0;
       const int k = sscanf(need(a), "%u,%f,%f,%u%c", &aoParams.samples, &aoParams.radius,
@@ -252,6 +266,10 @@ int main(int argc, char** argv) {
                     !raysIn.empty())) {
     printf("--views or --cube renders alone: one of them, on one device, without --camera,\n"
            "--gbuffer, --rays, --ao or --matte\n");
+    return 1;
+  }
+  if ((shBands != 0) != !shOut.empty() || (shBands && !cube)) {
+    printf("--sh BANDS and --sh-out FILE go together, with --cube\n");
     return 1;
   }
   if (cube) {  // rtg_camera_cube's poses are for a square frame at zoom -1
@@ -322,6 +340,50 @@ int main(int argc, char** argv) {
     check(rtg_context_set_semantics(ctx, semantics), "rtg_context_set_semantics");
     check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
           "rtg_context_set_scene");
+    if (shBands) {  // the probe: poses in, coefficients out, no face anywhere
+      const unsigned K = shBands * shBands;
+      const rtg_fold_params fp = {6, K, 0};
+      std::vector<float> wts(6 * per * K);
+      check(rtg_cube_sh_weights(W, shBands, aa, wts.data()), "rtg_cube_sh_weights");
+      size_t scratchBytes = 0;
+      check(rtg_views_fold_scratch(nV, W, H, K, &scratchBytes), "rtg_views_fold_scratch");
+      rtg_camera* dPoses = nullptr;
+      float* dW = nullptr;
+      rtg_vec* dOut = nullptr;
+      void* dScratch = nullptr;
+      if (hipMalloc(&dPoses, nV * sizeof(rtg_camera)) != hipSuccess ||
+          hipMalloc(&dW, wts.size() * sizeof(float)) != hipSuccess ||
+          hipMalloc(&dOut, K * sizeof(rtg_vec)) != hipSuccess ||
+          hipMalloc(&dScratch, scratchBytes) != hipSuccess)
+        check(RTG_ERR_NOMEM, "hipMalloc");
+      if (hipMemcpy(dPoses, views.data(), nV * sizeof(rtg_camera), hipMemcpyHostToDevice) !=
+              hipSuccess ||
+          hipMemcpy(dW, wts.data(), wts.size() * sizeof(float), hipMemcpyHostToDevice) !=
+              hipSuccess)
+        check(RTG_ERR_HIP, "upload");
+      check(rtg_render_views_fold_device(ctx, dPoses, nV, W, H, zoom, aa, (int)depth + 1, &fp, dW,
+                                         dOut, nullptr, dScratch, scratchBytes, nullptr),
+            "rtg_render_views_fold_device");
+      std::vector<rtg_vec> coef(K);
+      if (hipMemcpy(coef.data(), dOut, K * sizeof(rtg_vec), hipMemcpyDeviceToHost) != hipSuccess)
+        check(RTG_ERR_HIP, "readback");
+      (void)hipFree(dPoses);
+      (void)hipFree(dW);
+      (void)hipFree(dOut);
+      (void)hipFree(dScratch);
+      rtg_context_destroy(ctx);
+      FILE* f = fopen(shOut.c_str(), "w");
+      if (!f) {
+        fprintf(stderr, "Error: can't write %s\n", shOut.c_str());
+        exit(EXIT_FAILURE);
+      }
+      for (unsigned k = 0; k < K; ++k)
+        fprintf(f, "%.9g %.9g %.9g\n", (double)coef[k].x, (double)coef[k].y, (double)coef[k].z);
+      fclose(f);
+      printf("Wrote %s (%u SH coefficients of the probe at %g,%g,%g, %ux%u faces)\n",
+             shOut.c_str(), K, (double)cubeEye.x, (double)cubeEye.y, (double)cubeEye.z, W, H);
+      return 0;
+    }
     rtg_camera* dv = nullptr;
     rtg_vec* d = nullptr;
     if (nV && per) {

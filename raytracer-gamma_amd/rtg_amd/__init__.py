@@ -62,6 +62,10 @@ AO_PARAMS_DTYPE = np.dtype([("samples", "<u4"), ("radius", "<f4"), ("bias", "<f4
                             ("seed", "<u4"), ("flags", "<u4")])
 assert AO_PARAMS_DTYPE.itemsize == 20
 AO_MAX_SAMPLES, AO_MAX_DIRS, AO_JITTER = 1024, 65536, 1  # RTG_AO_*
+# rtg_fold_params (include/rtg.h): views folded into per-group coefficients
+FOLD_PARAMS_DTYPE = np.dtype([("viewsPerGroup", "<u4"), ("weights", "<u4"), ("flags", "<u4")])
+assert FOLD_PARAMS_DTYPE.itemsize == 12
+FOLD_MAX_WEIGHTS, FOLD_SKIP_NONFINITE = 16, 1  # RTG_FOLD_*
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -90,6 +94,9 @@ EXPORTED = [
     "rtg_camera_rays_host", "rtg_camera_rays_device",
     "rtg_render_camera_device", "rtg_render_camera", "rtg_render_camera_host",
     "rtg_render_views_device", "rtg_render_views", "rtg_render_views_host", "rtg_camera_cube",
+    "rtg_views_fold_scratch", "rtg_views_fold_host", "rtg_views_fold_device",
+    "rtg_render_views_fold_device", "rtg_render_views_fold", "rtg_render_views_fold_host",
+    "rtg_cube_sh_weights",
     "rtg_ao_directions", "rtg_ao_segments_host", "rtg_ao_segments_device", "rtg_ao_device",
     "rtg_ao", "rtg_ao_host",
     "rtg_matte_device", "rtg_matte", "rtg_matte_host",
@@ -202,6 +209,24 @@ def lib() -> ctypes.CDLL:
         L.rtg_render_views.argtypes = [i, vp, u, vp, u, vp, sz, u, u, f, f, i, vp]
         L.rtg_render_views_host.argtypes = [vp, u, vp, u, vp, sz, u, u, f, f, i, i, vp, i, i]
         L.rtg_camera_cube.argtypes = [vp, vp]
+        # the views folded into coefficients; an RTG_LIB build of the commit before
+        # them (tools/ab_bench.sh against the parent) loads without them
+        for name, at in (
+                ("rtg_views_fold_scratch", [sz, u, u, u, vp]),
+                ("rtg_views_fold_host", [vp, sz, u, u, vp, vp, vp, vp, i]),
+                ("rtg_views_fold_device", [vp, vp, sz, u, u, vp, vp, vp, vp, vp, sz, vp]),
+                ("rtg_render_views_fold_device",
+                 [vp, vp, sz, u, u, f, f, i, vp, vp, vp, vp, vp, sz, vp]),
+                ("rtg_render_views_fold",
+                 [i, vp, u, vp, u, vp, sz, u, u, f, f, i, vp, vp, vp, vp]),
+                ("rtg_render_views_fold_host",
+                 [vp, u, vp, u, vp, sz, u, u, f, f, i, i, vp, vp, vp, vp, i, i]),
+                ("rtg_cube_sh_weights", [u, u, f, vp])):
+            try:
+                getattr(L, name).argtypes = at
+            except AttributeError:
+                if not os.environ.get("RTG_LIB"):
+                    raise
         L.rtg_ao_directions.argtypes = [u, vp]
         L.rtg_ao_segments_host.argtypes = [vp, sz, vp, vp, u, vp, i]
         L.rtg_ao_segments_device.argtypes = [vp, vp, sz, vp, vp, u, vp, vp]
@@ -655,6 +680,103 @@ def render_views_host(spheres, lights, cams, width: int, height: int, zoom: floa
     return out
 
 
+def fold_params(views_per_group: int, weights: int, flags: int = 0) -> np.ndarray:
+    """One rtg_fold_params record (flags: FOLD_SKIP_NONFINITE)."""
+    p = np.zeros(1, FOLD_PARAMS_DTYPE)
+    p[0] = (views_per_group, weights, flags)
+    return p
+
+
+def _fold_table(weights, params):
+    """The weight table as contiguous float32 (never a null pointer) and the
+    params record."""
+    w = np.ascontiguousarray(weights, np.float32)
+    p = np.ascontiguousarray(params, FOLD_PARAMS_DTYPE).reshape(1)
+    return (w if w.size else np.zeros(1, np.float32)), p
+
+
+def views_fold_scratch(n_views: int, width: int, height: int, weights: int) -> int:
+    """Bytes of tile partials Context.views_fold / render_views_fold need
+    (rtg_views_fold_scratch): caller-owned, 16-byte aligned."""
+    out = ctypes.c_size_t(0)
+    _check(lib().rtg_views_fold_scratch(n_views, width, height, weights, ctypes.byref(out)),
+           "rtg_views_fold_scratch")
+    return int(out.value)
+
+
+def views_fold_host(frames, weights, params, threads: int = 1, skipped: bool = False):
+    """Groups of frames folded by a weight table on the host (rtg_views_fold_host,
+    the plain-loop statement of rtg.h's summation order): frames (n, H, W, 3)
+    float32, weights G * H * W * K float32 (any shape), params from fold_params();
+    (nGroups, K, 3) float32, with skipped=True also the uint32 counts."""
+    fr = np.ascontiguousarray(frames, np.float32)
+    assert fr.ndim == 4 and fr.shape[3] == 3, "frames are (n, H, W, 3)"
+    n, H, W = fr.shape[:3]
+    w, p = _fold_table(weights, params)
+    G, K = max(int(p["viewsPerGroup"][0]), 1), int(p["weights"][0])
+    out = np.empty((n // G, K, 3), np.float32)
+    cnt = np.zeros(max(n // G, 1), np.uint32)
+    dst = out if out.size else np.zeros((1, 3), np.float32)
+    _check(lib().rtg_views_fold_host(_ptr(fr) if fr.size else None, n, W, H, _ptr(p), _ptr(w),
+                                     _ptr(dst), _ptr(cnt) if skipped else None, threads),
+           "rtg_views_fold_host")
+    return (out, cnt[:n // G]) if skipped else out
+
+
+def render_views_fold_host(spheres, lights, cams, width: int, height: int, weights, params,
+                           zoom: float = -4.0, alias_factor: float = 3.0, stack_size: int = 6,
+                           semantics: int = 0, walk: int = 0, threads: int = 1,
+                           skipped: bool = False):
+    """render_views_host, then views_fold_host, in one call with no frames on the
+    caller's side (rtg_render_views_fold_host; no GPU needed)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    c = _cameras(cams)
+    w, p = _fold_table(weights, params)
+    G, K = max(int(p["viewsPerGroup"][0]), 1), int(p["weights"][0])
+    out = np.empty((len(c) // G, K, 3), np.float32)
+    cnt = np.zeros(max(len(c) // G, 1), np.uint32)
+    dst = out if out.size else np.zeros((1, 3), np.float32)
+    _check(lib().rtg_render_views_fold_host(
+        _ptr(spheres), len(spheres), _ptr(lights), len(lights), _ptr(c) if len(c) else None,
+        len(c), width, height, float(zoom), float(alias_factor), stack_size, semantics, _ptr(p),
+        _ptr(w), _ptr(dst), _ptr(cnt) if skipped else None, walk, threads),
+        "rtg_render_views_fold_host")
+    return (out, cnt[:len(c) // G]) if skipped else out
+
+
+def render_views_fold(spheres, lights, cams, width: int, height: int, weights, params,
+                      zoom: float = -4.0, alias_factor: float = 3.0, stack_size: int = 6,
+                      device: int = 0, skipped: bool = False):
+    """One-shot fused render + fold on the GPU (rtg_render_views_fold): poses in,
+    (nGroups, K, 3) coefficients out, no frame anywhere; word for word
+    render_views_fold_host(walk 0)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    c = _cameras(cams)
+    w, p = _fold_table(weights, params)
+    G, K = max(int(p["viewsPerGroup"][0]), 1), int(p["weights"][0])
+    out = np.empty((len(c) // G, K, 3), np.float32)
+    cnt = np.zeros(max(len(c) // G, 1), np.uint32)
+    dst = out if out.size else np.zeros((1, 3), np.float32)
+    _check(lib().rtg_render_views_fold(
+        device, _ptr(spheres), len(spheres), _ptr(lights), len(lights),
+        _ptr(c) if len(c) else None, len(c), width, height, float(zoom), float(alias_factor),
+        stack_size, _ptr(p), _ptr(w), _ptr(dst), _ptr(cnt) if skipped else None),
+        "rtg_render_views_fold")
+    return (out, cnt[:len(c) // G]) if skipped else out
+
+
+def cube_sh_weights(res: int, bands: int = 3, alias_factor: float = 1.0) -> np.ndarray:
+    """Real-SH projection weights for camera_cube's six res x res faces at zoom -1
+    (rtg_cube_sh_weights): (6, res, res, bands * bands) float32, for fold_params(6,
+    bands * bands).  A convenience; its bits are not part of the contract."""
+    out = np.zeros((6, max(res, 1), max(res, 1), max(bands * bands, 1)), np.float32)
+    _check(lib().rtg_cube_sh_weights(res, bands, float(alias_factor), _ptr(out)),
+           "rtg_cube_sh_weights")
+    return out
+
+
 def ao_params(samples: int, radius: float, bias: float = 1e-3, seed: int = 0,
               flags: int = 0) -> np.ndarray:
     """One rtg_ao_params record (flags: AO_JITTER for a per-point window into the table)."""
@@ -1049,6 +1171,39 @@ class Context:
                                              ctypes.c_void_p(dst_ptr),
                                              ctypes.c_void_p(stream) if stream else None),
                "rtg_render_views_device")
+
+    def views_fold(self, frames_ptr: int, n_views: int, width, height, params, weights_ptr: int,
+                   dst_ptr: int, scratch_ptr: int, scratch_bytes: int, skipped_ptr: int = 0,
+                   stream: int = 0):
+        """Groups of n_views frames at frames_ptr (device, (n, H, W, 3) float32,
+        render_views' or the caller's own) folded by the weight table at
+        weights_ptr (device, G * H * W * K float32) into dst_ptr (device, (nGroups,
+        K, 3) float32) and, if given, skipped_ptr (nGroups uint32), asynchronously
+        on `stream` (rtg_views_fold_device; params from fold_params(), the scratch
+        views_fold_scratch() bytes, 16-byte aligned; the context needs no scene)."""
+        p = np.ascontiguousarray(params, FOLD_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_views_fold_device(self._h, ctypes.c_void_p(frames_ptr), n_views, width,
+                                           height, _ptr(p), ctypes.c_void_p(weights_ptr),
+                                           ctypes.c_void_p(dst_ptr), ctypes.c_void_p(skipped_ptr),
+                                           ctypes.c_void_p(scratch_ptr), scratch_bytes,
+                                           ctypes.c_void_p(stream) if stream else None),
+               "rtg_views_fold_device")
+
+    def render_views_fold(self, cams_ptr: int, n_views: int, width, height, params,
+                          weights_ptr: int, dst_ptr: int, scratch_ptr: int, scratch_bytes: int,
+                          skipped_ptr: int = 0, zoom=-4.0, alias_factor=3.0, stack_size=6,
+                          stream: int = 0):
+        """The fused call: n_views poses at cams_ptr (device, as render_views takes
+        them) rendered and folded in one launch plus a small second kernel, no
+        frame written anywhere (rtg_render_views_fold_device); the other
+        arguments as views_fold."""
+        p = np.ascontiguousarray(params, FOLD_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_render_views_fold_device(
+            self._h, ctypes.c_void_p(cams_ptr), n_views, width, height, float(zoom),
+            float(alias_factor), stack_size, _ptr(p), ctypes.c_void_p(weights_ptr),
+            ctypes.c_void_p(dst_ptr), ctypes.c_void_p(skipped_ptr), ctypes.c_void_p(scratch_ptr),
+            scratch_bytes, ctypes.c_void_p(stream) if stream else None),
+            "rtg_render_views_fold_device")
 
     def camera_rays(self, cam, width, height, dst_ptr: int, zoom=-4.0, alias_factor=3.0,
                     stream: int = 0):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
                        [--only-order] [--only-ao] [--only-matte] [--only-views]
+                       [--only-fold]
                        [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
@@ -72,6 +73,12 @@ rows under "views" (views_rows below): a bake of 256 probes x 6 cube faces of
 32 x 32 pixels, as one launch, as 1536 single-view launches and through the ray
 generator plus the batch ray tracer, next to one frame of the same pixel count.
 --only-views runs these alone and keeps FILE's other sections.
+
+The views folded into per-probe SH coefficients (rtg_render_views_fold_device,
+csrc/rtg_fold.hip) get rows under "fold" (fold_rows below): the same bake
+through the fused call, through rtg_render_views_device + rtg_views_fold_device
+and through rtg_render_views_device + a torch einsum, with the bytes each route
+allocates.  --only-fold runs these alone and keeps FILE's other sections.
 GPU only.
 """
 import argparse
@@ -559,6 +566,101 @@ def views_rows(args, stream):
     return out, ok
 
 
+def fold_rows(args, stream):
+    """The bake of views_rows (256 probes x 6 faces of 32 x 32 at aa 1, C3 and
+    C5) reduced to SH9 coefficients with rtg_cube_sh_weights' table (G = 6, K =
+    9), round by round in one process:
+      (a) fused        one rtg_render_views_fold_device: no frame anywhere;
+      (b) unfused      rtg_render_views_device into a frame buffer, then
+                       rtg_views_fold_device over it (the row is the per-round
+                       sum; each part has a row of its own);
+      (c) torch        the same frames, a torch mask of the non-finite pixels
+                       and a torch einsum with the table (the per-round sum;
+                       its summation order is torch's).
+    All three with RTG_FOLD_SKIP_NONFINITE's rule: most probes of these scenes
+    see a NaN or infinite pixel, which would otherwise spoil every coefficient.
+    views is this session's rtg_render_views_device alone: what (a) is compared
+    with.  Reported, not gated: the times, (a) minus views against views'
+    min-max spread, and the bytes each route allocates besides the poses, the
+    table and the nGroups * K coefficients (faces nViews * W * H * 12; partials
+    nViews * tiles * (3K + 1) * 4; torch's peak above the faces during the
+    einsum).  Gated: (a) and (b) are the same words."""
+    nP, Wv, Hv, aa, zoom, bands = 256, 32, 32, 1.0, -1.0, 3
+    K, nV = bands * bands, nP * 6
+    frames = torch.empty((nV, Hv, Wv, 3), dtype=torch.float32, device="cuda")
+    table = R.cube_sh_weights(Wv, bands, aa)
+    d_w = torch.from_numpy(table).cuda()
+    p = R.fold_params(6, K, R.FOLD_SKIP_NONFINITE)  # (most probes see a non-finite pixel)
+    zero = torch.zeros((), dtype=torch.float32, device="cuda")
+    skipped = torch.zeros((nP,), dtype=torch.int32, device="cuda")
+    nbytes = R.views_fold_scratch(nV, Wv, Hv, K)
+    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device="cuda")
+    oa = torch.zeros((nP, K, 3), dtype=torch.float32, device="cuda")
+    ob = torch.zeros((nP, K, 3), dtype=torch.float32, device="cuda")
+    oc = torch.zeros((nP, K, 3), dtype=torch.float32, device="cuda")
+    out = {"probes": nP, "views": nV, "width": Wv, "height": Hv, "alias_factor": aa, "zoom": zoom,
+           "weights": K, "views_per_group": 6,
+           "bytes": {"faces": nV * Wv * Hv * 12, "partials": nbytes, "coefficients": nP * K * 12,
+                     "table": table.nbytes, "fused": nbytes, "unfused": nV * Wv * Hv * 12 + nbytes}}
+    ok = True
+    for name in ("c3", "c5"):
+        S = CONFIGS[name][4] + 1
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        cams = np.concatenate([R.camera_cube(e) for e in probe_positions(sph, nP)])
+        d_cams = torch.from_numpy(cams.view(F).reshape(nV, 12)).cuda()
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+
+        def einsum():
+            fr = frames.view(nP, 6, Hv, Wv, 3)  # a pixel with a NaN or infinite word adds nothing
+            fr = torch.where(torch.isfinite(fr).all(-1, keepdim=True), fr, zero)
+            oc.copy_(torch.einsum("pfhwc,fhwk->pkc", fr, d_w))
+
+        raw = []
+        fu, vw, fo, es = measure(
+            [lambda: ctx.render_views_fold(d_cams.data_ptr(), nV, Wv, Hv, p, d_w.data_ptr(),
+                                           oa.data_ptr(), scratch.data_ptr(), nbytes,
+                                           skipped_ptr=skipped.data_ptr(), zoom=zoom,
+                                           alias_factor=aa, stack_size=S, stream=stream),
+             lambda: ctx.render_views(d_cams.data_ptr(), nV, Wv, Hv, frames.data_ptr(), zoom, aa,
+                                      S, stream),
+             lambda: ctx.views_fold(frames.data_ptr(), nV, Wv, Hv, p, d_w.data_ptr(),
+                                    ob.data_ptr(), scratch.data_ptr(), nbytes, stream=stream),
+             einsum],
+            args.rounds, raw=raw, names=[f"fold {name} {k}" for k in ("fused", "views",
+                                                                      "views_fold", "einsum")])
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        einsum()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        ctx.close()
+        equal = bool((oa.view(torch.int32) == ob.view(torch.int32)).all())
+        ok = ok and equal
+        rows = _spread_rows({"unfused": [a + b for a, b in zip(raw[1], raw[2])],
+                             "torch": [a + b for a, b in zip(raw[1], raw[3])]})
+        finite = torch.isfinite(oa) & torch.isfinite(oc)
+        out[name] = {
+            "stack_size": S, "fused": fu, "views": vw, "views_fold": fo, "einsum": es, **rows,
+            "fused_minus_views_ms": round(fu["ms_median"] - vw["ms_median"], 5),
+            "views_spread_ms": round(vw["ms_max"] - vw["ms_min"], 5),
+            "fused_over_views": round(fu["ms_median"] / vw["ms_median"], 4),
+            "fused_over_unfused": round(fu["ms_median"] / rows["unfused"]["ms_median"], 4),
+            "fused_over_torch": round(fu["ms_median"] / rows["torch"]["ms_median"], 4),
+            "einsum_peak_bytes_above_faces": int(peak),
+            "fused_equals_unfused": equal,
+            "non_finite_coefficients": int((~torch.isfinite(oa)).sum()),
+            "skipped_share_of_pixels": round(float(skipped.sum()) / (nV * Wv * Hv), 4),
+            "probes_with_a_skipped_pixel": int((skipped > 0).sum()),
+            "max_abs_difference_from_einsum": float((oa - oc)[finite].abs().max()) if finite.any()
+            else None}
+        print(f"fold {name}: fused {fu['ms_median']} ms, views alone {vw['ms_median']} ms, "
+              f"unfused {rows['unfused']['ms_median']} ms, torch {rows['torch']['ms_median']} ms",
+              file=sys.stderr, flush=True)
+    return out, ok
+
+
 def finish(args, res, ok):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -583,6 +685,11 @@ def main():
                          "next to what it holds")
     ap.add_argument("--only-views", action="store_true",
                     help="the many-views rows alone, put into FILE next to what it holds")
+    ap.add_argument("--only-fold", action="store_true",
+                    help="the rows of the views folded into SH coefficients alone, put into FILE "
+                         "next to what it holds")
+    ap.add_argument("--parent-commit", default="",
+                    help="recorded with --only-fold as the parent of --commit")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
     ap.add_argument("--order-alt-json", default=[], action="append",
@@ -601,6 +708,15 @@ def main():
         res["views_commit"] = args.commit
         res["views"], ok = views_rows(args, torch.cuda.current_stream().cuda_stream)
         res["views"]["rounds"] = args.rounds
+        finish(args, res, ok)
+    if args.only_fold:  # (the same: poses in, coefficients out)
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["fold_commit"], res["fold_parent_commit"] = args.commit, args.parent_commit
+        res["fold"], ok = fold_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["fold"]["rounds"] = args.rounds
         finish(args, res, ok)
     W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
     assert (W, H) == CONFIGS["c5"][:2]
@@ -722,7 +838,8 @@ def main():
     res["contains"] = contains_rows(args, W, H, rays, stream)
     del rays
     res["views"], views_ok = views_rows(args, stream)
-    ok = ok and cam_ok and order_ok and ao_ok and matte_ok and views_ok
+    res["fold"], fold_ok = fold_rows(args, stream)
+    ok = ok and cam_ok and order_ok and ao_ok and matte_ok and views_ok and fold_ok
     if args.mapping_json:
         with open(args.mapping_json) as f:
             other = json.load(f)["camera"]
