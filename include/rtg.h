@@ -34,6 +34,8 @@
  *     loop over hasClearLineOfSight in the reference)    rtg_ao_segments[_device|_host]
  *   calculateMatte for a caller's own hit points       rtg_matte[_device|_host]
  *     raytracer.h:313-367
+ *   (one-bounce indirect light of a hit point: the      rtg_gather[_device|_host],
+ *     caller's loop over rayTrace in the reference)       rtg_gather_rays[_device|_host]
  *   primaryContainer for a caller's own points         rtg_contains[_device|_host]
  *     raytracer.h:245-270
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
@@ -895,6 +897,108 @@ int rtg_matte(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_
 int rtg_matte_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
                    unsigned lgtNum, const rtg_hit* hits, size_t n, rtg_vec* outHost,
                    unsigned long long* litHost, int walk, int nthreads);
+
+/* ---- gather: a hemisphere of rayTrace colours per hit point ----
+ * Hit points go in, one colour per point comes out: the weighted sum of
+ * rayTrace's colour along K directions of the point's hemisphere, the one-bounce
+ * indirect light ("final gather") of a lightmap or irradiance bake, with no
+ * n x K ray buffer, no colour buffer, no sort and no fold on the caller's side.
+ * The call takes n rtg_hit records exactly as rtg_intersect* writes them, a
+ * table of nDirs local directions `dirs` in the frame whose z axis is the
+ * normal, and a table of nDirs floats `weights`, one per direction, samples <=
+ * nDirs <= RTG_GATHER_MAX_DIRS.  Both tables are the caller's (device pointers
+ * in the device calls), as with rtg_ao*: rtg_ao_directions(K) with weights 1 / K
+ * is the cosine-weighted estimate of the irradiance over pi.  It pairs with
+ * rtg_ao* and rtg_matte* on the same records.
+ *
+ * For a record with id >= 0 (P = point, N = normal), all in float with no
+ * contraction and in this operand order:
+ *   point, frame, window   rtg_ao's, word for word: a.q = P.q + bias * N.q, the
+ *            frame T1, T2, N, the window s_i (RTG_GATHER_JITTER, seed) and the
+ *            table index j of probe k
+ *   world    per component q: w.q = (l.x * T1.q + l.y * T2.q) + l.z * N.q with
+ *            l = dirs[j] (rtg_ao's `world`)
+ *   ray k    origin = a;  dir = (1.f / sqrt((w.x * w.x + w.y * w.y) + w.z * w.z)) * w
+ *            (vec.h:41, the posed camera's normalisation: the reference's rays
+ *            are unit rays, and a scaled normal or table entry must not change
+ *            what rayTrace shades with)
+ *   colour   c_k = rayTrace(ray k) exactly as rtg_raytrace* defines it:
+ *            background material, intensity (1, 1, 1), stack capacity
+ *            stackSize, the context's semantics (the host form takes them)
+ *   sum      acc = (+0, +0, +0);  for k = 0 .. K-1 in order, per component q:
+ *              acc.q = acc.q + weights[j] * c_k.q
+ *            With RTG_GATHER_SKIP_NONFINITE a colour with any word whose
+ *            exponent field is all ones (NaN or +-inf) adds +0.f to every
+ *            channel instead and counts one towards skipped[i]; the weight is
+ *            never tested.
+ *   out[i] = acc, NaN words written as 0xFFC00000;  skipped[i] (an unsigned
+ *            short; 0 without the flag)
+ * A record with id < 0 (no point) gets (0, 0, 0) and skipped 0 and makes no
+ * trace.  The directions, the weights and the normal are used as given: any
+ * length or sign is legal, a zero or NaN direction gives a NaN ray, and NaN,
+ * infinite and degenerate inputs follow the arithmetic and the comparisons as
+ * written.  `skipped` may be NULL.
+ *
+ * rtg_gather_rays* write the n * K rays, point-major (ray k of point i at i * K
+ * + k), all-zero rays for a record with id < 0: the generator that pins the
+ * definition.  NaN words are written as 0xFFC00000, as every record's.
+ *
+ * THE CONTRACT: rtg_gather_host(walk 0) is, word for word, the sum above over
+ * rtg_raytrace_host(walk 0) of rtg_gather_rays_host's rays; walk 1, the fused
+ * device call and the one-shot give the same words.
+ *
+ * n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID with a message, before
+ * any GPU call, for a null pointer (`skipped` excepted), samples outside
+ * 1..RTG_GATHER_MAX_SAMPLES, nDirs outside samples..RTG_GATHER_MAX_DIRS, an
+ * unknown flag, a stackSize outside 1..RTG_MAX_STACK, an unknown walk or
+ * semantics, n > 2^32 - 1, an n * K that overflows size_t (the rays), more than
+ * 2^31-1 workgroups (64 lanes each) or, for the fused call only, a context
+ * without a scene.
+ *
+ * Out of scope: per-point direction tables, hit distances or bent normals as
+ * outputs, an _indexed form, re-sorting the rays between bounces, multi-GPU
+ * batches. */
+#define RTG_GATHER_MAX_SAMPLES 1024
+#define RTG_GATHER_MAX_DIRS    65536
+#define RTG_GATHER_JITTER          1  /* per-point window into the tables, as RTG_AO_JITTER */
+#define RTG_GATHER_SKIP_NONFINITE  2  /* a NaN or infinite colour adds +0.f and is counted */
+typedef struct rtg_gather_params {    /* 16 B */
+  unsigned samples;  /* K probes per point, 1..RTG_GATHER_MAX_SAMPLES */
+  float bias;        /* start offset along the normal, used as given */
+  unsigned seed;     /* RTG_GATHER_JITTER only */
+  unsigned flags;    /* RTG_GATHER_* bits; an unknown bit is RTG_ERR_INVALID */
+} rtg_gather_params;
+/* The n * K probe rays on the host.  nthreads <= 0: 1. */
+int rtg_gather_rays_host(const rtg_hit* hits, size_t n, const rtg_gather_params* params,
+                         const rtg_vec* dirs, unsigned nDirs, rtg_ray* raysHost, int nthreads);
+/* The same into device memory, asynchronously on `stream`.  The context names
+ * the device; it needs no scene.  `params` is host memory in every call, read
+ * before the call returns. */
+int rtg_gather_rays_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
+                           const rtg_gather_params* params, const rtg_vec* dirsDevice,
+                           unsigned nDirs, rtg_ray* raysDevice, void* stream);
+/* The fused kernel: n sums into outDevice (12 B each) and, when skippedDevice
+ * is not NULL, n counts, asynchronously on `stream`.  Allocates nothing, takes
+ * none of the context's render scratch and may be mixed with every other call
+ * on the context. */
+int rtg_gather_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
+                      const rtg_gather_params* params, const rtg_vec* dirsDevice,
+                      const float* weightsDevice, unsigned nDirs, int stackSize,
+                      rtg_vec* outDevice, unsigned short* skippedDevice, void* stream);
+/* One-shot: uploads the scene, the hits and the tables, runs on `device`
+ * (CPU semantics), downloads the sums and (skippedHost not NULL) the counts. */
+int rtg_gather(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+               unsigned lgtNum, const rtg_hit* hits, size_t n, const rtg_gather_params* params,
+               const rtg_vec* dirs, const float* weights, unsigned nDirs, int stackSize,
+               rtg_vec* outHost, unsigned short* skippedHost);
+/* The same on the host, no GPU call.  walk 0: plain loops over every sphere
+ * for every query of every probe (the yardstick).  walk 1: the kernel's own
+ * path over the packed tables, as rtg_raytrace_host.  nthreads <= 0: 1. */
+int rtg_gather_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
+                    unsigned lgtNum, const rtg_hit* hits, size_t n,
+                    const rtg_gather_params* params, const rtg_vec* dirs, const float* weights,
+                    unsigned nDirs, int stackSize, int semantics, rtg_vec* outHost,
+                    unsigned short* skippedHost, int walk, int nthreads);
 
 /* ---- containment: primaryContainer per point ----
  * "Which medium is this point in": out[i] is the lowest sphere index s for

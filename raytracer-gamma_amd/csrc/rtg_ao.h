@@ -1,5 +1,6 @@
 // rtg_ao.h — the ambient-occlusion probe (rtg_ao*, rtg.h), written ONCE for the
-// segment generator, the fused kernel and both host walks (rtg_ao.hip), as
+// segment generator, the fused kernel and both host walks (rtg_ao.hip), and
+// for the gather's probe rays (rtg_gather*, rtg_gather.h), as
 // camera_dir (rtg_camera.h) is for the posed camera: the window hash, the
 // tangent frame of a normal, the window index and the probe's end points, in
 // the operand order rtg.h states.  No libm call: copysignf is a bit operation
@@ -55,19 +56,33 @@ RTG_HD AoPoint ao_point(const rtg_hit* hit, float bias) {
 
 // s_i of point i, and the table index of its probe k (s < nDirs, k < K <=
 // nDirs: j < 2 nDirs, one subtraction wraps it).
+RTG_HD unsigned ao_window(unsigned flags, unsigned seed, size_t i, unsigned nDirs) {
+  return (flags & RTG_AO_JITTER) ? ao_mix32(seed + (unsigned)i) % nDirs : 0u;
+}
 RTG_HD unsigned ao_window(const rtg_ao_params& p, size_t i, unsigned nDirs) {
-  return (p.flags & RTG_AO_JITTER) ? ao_mix32(p.seed + (unsigned)i) % nDirs : 0u;
+  return ao_window(p.flags, p.seed, i, nDirs);
 }
 RTG_HD unsigned ao_dir_index(unsigned s, unsigned k, unsigned nDirs) {
   const unsigned j = s + k;
   return j >= nDirs ? j - nDirs : j;
 }
 
+// Entry j < nDirs of the caller's table of local directions.
+RTG_HD V3 ao_dir(const rtg_vec* dirs, unsigned j) {
+  const float* t = reinterpret_cast<const float*>(dirs + j);
+  return v3(t[0], t[1], t[2]);
+}
+
+// The local direction l in the world: rtg.h's `world` (rtg_gather's too).
+RTG_HD V3 ao_world(const AoPoint& p, V3 l) {
+  return v3((l.x * p.T1.x + l.y * p.T2.x) + l.z * p.N.x,
+            (l.x * p.T1.y + l.y * p.T2.y) + l.z * p.N.y,
+            (l.x * p.T1.z + l.y * p.T2.z) + l.z * p.N.z);
+}
+
 // The probe's far end for the local direction l.
 RTG_HD V3 ao_end(const AoPoint& p, V3 l, float radius) {
-  const V3 w = v3((l.x * p.T1.x + l.y * p.T2.x) + l.z * p.N.x,
-                  (l.x * p.T1.y + l.y * p.T2.y) + l.z * p.N.y,
-                  (l.x * p.T1.z + l.y * p.T2.z) + l.z * p.N.z);
+  const V3 w = ao_world(p, l);
   return v3(p.a.x + radius * w.x, p.a.y + radius * w.y, p.a.z + radius * w.z);
 }
 

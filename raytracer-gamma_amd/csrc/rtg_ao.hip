@@ -59,11 +59,6 @@ static_assert(RTG_AO_MAX_SAMPLES <= 0xFFFF, "a count fits an unsigned short");
 
 namespace rtg {
 
-RTG_HD V3 ao_dir(const rtg_vec* dirs, unsigned j) {
-  const float* t = reinterpret_cast<const float*>(dirs + j);
-  return v3(t[0], t[1], t[2]);
-}
-
 // Segment k of point i as six words; a record without a point: zeros.
 RTG_HD void ao_segment(const rtg_hit* hits, size_t i, unsigned k, const rtg_ao_params& p,
                        const rtg_vec* dirs, unsigned nDirs, unsigned* w) {

@@ -1199,6 +1199,7 @@ struct RayBox;   // rtg_rays.h
 struct KeyBox;   // rtg_order.h
 struct CamPose;  // rtg_camera.h
 struct FoldArgs;  // rtg_fold.h
+struct GatherArgs;  // rtg_gather_kernels.h
 
 // THE list of stack capacities: X(k) for every k an object rtg_trace_s<k>.o is
 // built for (the Makefile's SVALS).
@@ -1222,15 +1223,19 @@ typedef void (*ViewsFn)(const SceneTables, const RayBox, const Camera, const Cam
 // ... and the views folded into coefficients (views_fold_kernel: no frame).
 typedef void (*ViewsFoldFn)(const SceneTables, const RayBox, const Camera, const CamPose*,
                             unsigned, unsigned, unsigned, unsigned, const FoldArgs);
+// The gather's fused kernel (gather_kernel, rtg_gather_kernels.h).
+typedef void (*GatherFn)(const SceneTables, const RayBox, const GatherArgs);
 
 // What one per-S object (rtg_trace_s<S>.hip) exports: its kernels by variant
-// (trace_fn<S>, raytrace_fn<S>, camera_fn<S>, views_fn<S>, views_fold_fn<S>).
+// (trace_fn<S>, raytrace_fn<S>, camera_fn<S>, views_fn<S>, views_fold_fn<S>,
+// gather_fn<S>).
 struct StackKernels {
   TraceFn (*trace)(int variant, bool bvh, int list);
   RayTraceFn (*raytrace)(bool bvh, bool cl);
   CameraFn (*camera)(bool bvh, bool cl);
   ViewsFn (*views)(bool bvh, bool cl);
   ViewsFoldFn (*views_fold)(bool bvh, bool cl);
+  GatherFn (*gather)(bool bvh, bool cl);
 };
 #define RTG_X(k) const StackKernels* stack_kernels_s##k();
 RTG_FOR_EACH_S(RTG_X)

@@ -72,6 +72,13 @@ static void usage() {
   printf("      --matte      FILE    Also write the frame's direct light (rtg_matte_device of every\n");
   printf("                           primary hit at aa 1, from --camera or the identity pose) as a\n");
   printf("                           P6 PPM, scaled by its own largest component like the render\n");
+  printf("      --gather     SPEC    Also write the frame's one-bounce indirect light: K[,bias[,seed]]\n");
+  printf("                           (rtg_gather_device of every primary hit at aa 1, from --camera\n");
+  printf("                           or the identity pose: K probes of rtg_ao_directions(K), weights\n");
+  printf("                           1/K, --depth's stack; bias defaults to 0.001; a seed turns\n");
+  printf("                           RTG_GATHER_JITTER on); needs --gather-out\n");
+  printf("      --gather-out FILE    The P6 PPM, scaled by its own largest component like the render\n");
+  printf("      --gather-skip        Leave NaN and infinite probe colours out (RTG_GATHER_SKIP_NONFINITE)\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -106,8 +113,9 @@ int main(int argc, char** argv) {
   unsigned long long seed = 42;
   float aa = 3.f, zoom = -4.f;
   std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut, radianceOut, aoOut;
-  std::string matteOut;
-  bool ao = false, matte = false;
+  std::string matteOut, gatherOut;
+  bool ao = false, matte = false, gather = false, gatherSkip = false;
+  rtg_gather_params gatherParams = {0, 1.0e-3f, 0, 0};
   rtg_ao_params aoParams = {0, 0.f, 1.0e-3f, 0, 0};
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
@@ -212,6 +220,21 @@ int main(int argc, char** argv) {
       ao = true;
     } else if (!strcmp(a, "--ao-out")) {
       aoOut = need(a);
+    } else if (!strcmp(a, "--gather")) {
+      char tail = 0;
+      const int k = sscanf(need(a), "%u,%f,%u%c", &gatherParams.samples, &gatherParams.bias,
+                           &gatherParams.seed, &tail);
+      if (k < 1 || k > 3 || gatherParams.samples < 1 ||
+          gatherParams.samples > RTG_GATHER_MAX_SAMPLES) {
+        printf("Invalid gather (K[,bias[,seed]], K in 1..%d)\n", RTG_GATHER_MAX_SAMPLES);
+        return 1;
+      }
+      if (k == 3) gatherParams.flags |= RTG_GATHER_JITTER;
+      gather = true;
+    } else if (!strcmp(a, "--gather-out")) {
+      gatherOut = need(a);
+    } else if (!strcmp(a, "--gather-skip")) {
+      gatherSkip = true;
     } else if (!strcmp(a, "--matte")) {
       matteOut = need(a);
       matte = true;
@@ -256,16 +279,24 @@ int main(int argc, char** argv) {
     return 1;
   }
 
+  if (gather == gatherOut.empty() || (gatherSkip && !gather) ||
+      (gather && (gatherOut == out || W == 0 || H == 0))) {
+    printf("--gather and --gather-out go together (a file other than --out, for a frame with "
+           "pixels; --gather-skip needs both)\n");
+    return 1;
+  }
+  if (gatherSkip) gatherParams.flags |= RTG_GATHER_SKIP_NONFINITE;
+
   if (posed && gpus) {
     printf("--camera renders on one device\n");
     return 1;
   }
 
   const bool manyViews = cube || !viewsIn.empty();
-  if (manyViews && (cube == !viewsIn.empty() || posed || gpus || ao || matte || !gbufOut.empty() ||
-                    !raysIn.empty())) {
+  if (manyViews && (cube == !viewsIn.empty() || posed || gpus || ao || matte || gather ||
+                    !gbufOut.empty() || !raysIn.empty())) {
     printf("--views or --cube renders alone: one of them, on one device, without --camera,\n"
-           "--gbuffer, --rays, --ao or --matte\n");
+           "--gbuffer, --rays, --ao, --matte or --gather\n");
     return 1;
   }
   if ((shBands != 0) != !shOut.empty() || (shBands && !cube)) {
@@ -581,6 +612,66 @@ int main(int argc, char** argv) {
     }
     printf("Wrote %s (%ux%u, direct light of %u lights per primary hit, max %.8g)\n",
            matteOut.c_str(), W, H, nLgt, (double)lightMax);
+  }
+
+  if (gather) {  // pose -> primary rays -> hits -> gathered light -> bytes, all on the device
+    const size_t n = (size_t)W * H;
+    const unsigned K = gatherParams.samples;
+    if (!posed) rtg_camera_identity(&camera);
+    std::vector<rtg_vec> table(K);
+    check(rtg_ao_directions(K, table.data()), "rtg_ao_directions");
+    const std::vector<float> weights(K, 1.f / (float)K);
+    rtg_context* ctx = nullptr;
+    check(rtg_context_create((int)device, &ctx), "rtg_context_create");
+    check(rtg_context_set_semantics(ctx, semantics), "rtg_context_set_semantics");
+    check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
+          "rtg_context_set_scene");
+    rtg_ray* dr = nullptr;
+    rtg_hit* dh = nullptr;
+    rtg_vec* dd = nullptr;
+    float* dw = nullptr;
+    rtg_vec* dl = nullptr;
+    float* dmax = nullptr;
+    unsigned char* db = nullptr;
+    if (hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
+        hipMalloc(&dh, n * sizeof(rtg_hit)) != hipSuccess ||
+        hipMalloc(&dd, K * sizeof(rtg_vec)) != hipSuccess ||
+        hipMalloc(&dw, K * sizeof(float)) != hipSuccess ||
+        hipMalloc(&dl, n * sizeof(rtg_vec)) != hipSuccess ||
+        hipMalloc(&dmax, sizeof(float)) != hipSuccess || hipMalloc(&db, n * 3) != hipSuccess)
+      check(RTG_ERR_NOMEM, "hipMalloc");
+    if (hipMemcpy(dd, table.data(), K * sizeof(rtg_vec), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dw, weights.data(), K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      check(RTG_ERR_HIP, "upload");
+    check(rtg_camera_rays_device(ctx, &camera, W, H, zoom, 1.f, dr, nullptr),
+          "rtg_camera_rays_device");
+    check(rtg_intersect_device(ctx, dr, n, dh, nullptr), "rtg_intersect_device");
+    check(rtg_gather_device(ctx, dh, n, &gatherParams, dd, dw, K, (int)depth + 1, dl, nullptr,
+                            nullptr),
+          "rtg_gather_device");
+    check(rtg_max_colour_device(ctx, dl, n, dmax, nullptr), "rtg_max_colour_device");
+    check(rtg_ppm_bytes_device(ctx, dl, n, dmax, db, nullptr), "rtg_ppm_bytes_device");
+    std::vector<unsigned char> bytes(n * 3);
+    float lightMax = 0.f;
+    if (hipMemcpy(bytes.data(), db, n * 3, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&lightMax, dmax, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      check(RTG_ERR_HIP, "readback");
+    (void)hipFree(dr);
+    (void)hipFree(dh);
+    (void)hipFree(dd);
+    (void)hipFree(dw);
+    (void)hipFree(dl);
+    (void)hipFree(dmax);
+    (void)hipFree(db);
+    rtg_context_destroy(ctx);
+    FILE* f = fopen(gatherOut.c_str(), "wb");
+    if (!f || fprintf(f, "P6\n%u %u\n255\n", W, H) < 0 ||
+        fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
+      fprintf(stderr, "Error: can't write %s\n", gatherOut.c_str());
+      exit(EXIT_FAILURE);
+    }
+    printf("Wrote %s (%ux%u, %u probes per primary hit, depth %u, max %.8g)\n",
+           gatherOut.c_str(), W, H, K, depth, (double)lightMax);
   }
 
   if (!raysIn.empty()) {  // records as they lie in memory, like the G-buffer's

@@ -62,6 +62,12 @@ AO_PARAMS_DTYPE = np.dtype([("samples", "<u4"), ("radius", "<f4"), ("bias", "<f4
                             ("seed", "<u4"), ("flags", "<u4")])
 assert AO_PARAMS_DTYPE.itemsize == 20
 AO_MAX_SAMPLES, AO_MAX_DIRS, AO_JITTER = 1024, 65536, 1  # RTG_AO_*
+# rtg_gather_params (include/rtg.h): the gather
+GATHER_PARAMS_DTYPE = np.dtype([("samples", "<u4"), ("bias", "<f4"), ("seed", "<u4"),
+                                ("flags", "<u4")])
+assert GATHER_PARAMS_DTYPE.itemsize == 16
+GATHER_MAX_SAMPLES, GATHER_MAX_DIRS = 1024, 65536  # RTG_GATHER_*
+GATHER_JITTER, GATHER_SKIP_NONFINITE = 1, 2
 # rtg_fold_params (include/rtg.h): views folded into per-group coefficients
 FOLD_PARAMS_DTYPE = np.dtype([("viewsPerGroup", "<u4"), ("weights", "<u4"), ("flags", "<u4")])
 assert FOLD_PARAMS_DTYPE.itemsize == 12
@@ -100,6 +106,8 @@ EXPORTED = [
     "rtg_ao_directions", "rtg_ao_segments_host", "rtg_ao_segments_device", "rtg_ao_device",
     "rtg_ao", "rtg_ao_host",
     "rtg_matte_device", "rtg_matte", "rtg_matte_host",
+    "rtg_gather_rays_host", "rtg_gather_rays_device", "rtg_gather_device", "rtg_gather",
+    "rtg_gather_host",
     "rtg_contains_device", "rtg_contains", "rtg_contains_host",
 ]
 
@@ -236,6 +244,19 @@ def lib() -> ctypes.CDLL:
         L.rtg_matte_device.argtypes = [vp, vp, sz, vp, vp, vp]
         L.rtg_matte.argtypes = [i, vp, u, vp, u, vp, sz, vp, vp]
         L.rtg_matte_host.argtypes = [vp, u, vp, u, vp, sz, vp, vp, i, i]
+        # the gather; an RTG_LIB build of the commit before it (tools/ab_bench.sh
+        # against the parent) loads without it
+        for name, at in (
+                ("rtg_gather_rays_host", [vp, sz, vp, vp, u, vp, i]),
+                ("rtg_gather_rays_device", [vp, vp, sz, vp, vp, u, vp, vp]),
+                ("rtg_gather_device", [vp, vp, sz, vp, vp, vp, u, i, vp, vp, vp]),
+                ("rtg_gather", [i, vp, u, vp, u, vp, sz, vp, vp, vp, u, i, vp, vp]),
+                ("rtg_gather_host", [vp, u, vp, u, vp, sz, vp, vp, vp, u, i, i, vp, vp, i, i])):
+            try:
+                getattr(L, name).argtypes = at
+            except AttributeError:
+                if not os.environ.get("RTG_LIB"):
+                    raise
         L.rtg_contains_device.argtypes = [vp, vp, sz, vp, vp]
         L.rtg_contains.argtypes = [i, vp, u, vp, sz, vp]
         L.rtg_contains_host.argtypes = [vp, u, vp, sz, vp, i, i]
@@ -877,6 +898,82 @@ def matte(spheres, lights, hits, device: int = 0, mask: bool = False):
     return (out, lit) if mask else out
 
 
+def gather_params(samples: int, bias: float = 1e-3, seed: int = 0, flags: int = 0) -> np.ndarray:
+    """One rtg_gather_params record (flags: GATHER_JITTER for a per-point window
+    into the tables, GATHER_SKIP_NONFINITE to leave NaN and infinite colours out)."""
+    p = np.zeros(1, GATHER_PARAMS_DTYPE)
+    p[0] = (samples, bias, seed & 0xFFFFFFFF, flags)
+    return p
+
+
+def _gather_args(hits, dirs, weights, params):
+    """Hit records, the two tables and params as contiguous arrays whose
+    pointers are never null (an empty batch is legal), and the two counts; the
+    weights are checked against the directions when given."""
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    p = np.ascontiguousarray(params, GATHER_PARAMS_DTYPE).reshape(1)
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if len(w) != len(d):
+            raise RtgError(f"gather: {len(w)} weights for {len(d)} directions")
+        w = w if len(w) else np.zeros(1, np.float32)
+    return (h if len(h) else np.zeros(1, HIT_DTYPE)), len(h), \
+        (d if len(d) else np.zeros((1, 3), np.float32)), len(d), w, p
+
+
+def gather_rays_host(hits, dirs, params, threads: int = 1) -> np.ndarray:
+    """The probe rays of every hit point on the host (rtg_gather_rays_host):
+    (n * K, 6) float32 (origin, dir), point-major; params from gather_params()."""
+    h, n, d, nd, _, p = _gather_args(hits, dirs, None, params)
+    k = int(p["samples"][0])
+    out = np.empty((n * k, 6), np.float32)
+    dst = out if out.size else np.zeros((1, 6), np.float32)
+    _check(lib().rtg_gather_rays_host(_ptr(h), n, _ptr(p), _ptr(d), nd, _ptr(dst), threads),
+           "rtg_gather_rays_host")
+    return out
+
+
+def _gather_out(n: int, skipped: bool):
+    out = np.empty((n, 3), np.float32)
+    skp = np.empty(n, np.uint16) if skipped else None
+    dst = out if n else np.zeros((1, 3), np.float32)
+    sp = None if skp is None else ctypes.c_void_p((skp if n else np.zeros(1, np.uint16)).ctypes.data)
+    return out, skp, dst, sp
+
+
+def gather_host(spheres, lights, hits, dirs, weights, params, stack_size: int = 6,
+                semantics: int = 0, walk: int = 0, threads: int = 1, skipped: bool = False):
+    """The gather on the host (rtg_gather_host; no GPU needed): per HIT_DTYPE
+    record the weighted sum of rayTrace's colour along its K probes, (n, 3)
+    float32.  skipped=True: returns (sums, counts), counts the uint16 number of
+    probes GATHER_SKIP_NONFINITE left out.  walk 0: plain loops; walk 1: the
+    kernel's own path over the packed tables."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    h, n, d, nd, w, p = _gather_args(hits, dirs, weights, params)
+    out, skp, dst, sp = _gather_out(n, skipped)
+    _check(lib().rtg_gather_host(_ptr(spheres), len(spheres), _ptr(lights), len(lights), _ptr(h),
+                                 n, _ptr(p), _ptr(d), _ptr(w), nd, stack_size, semantics,
+                                 _ptr(dst), sp, walk, threads), "rtg_gather_host")
+    return (out, skp) if skipped else out
+
+
+def gather(spheres, lights, hits, dirs, weights, params, stack_size: int = 6, device: int = 0,
+           skipped: bool = False):
+    """The same on the GPU, one-shot (rtg_gather): HIT_DTYPE records as
+    intersect() returns them in."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    lights = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    h, n, d, nd, w, p = _gather_args(hits, dirs, weights, params)
+    out, skp, dst, sp = _gather_out(n, skipped)
+    _check(lib().rtg_gather(device, _ptr(spheres), len(spheres), _ptr(lights), len(lights),
+                            _ptr(h), n, _ptr(p), _ptr(d), _ptr(w), nd, stack_size, _ptr(dst), sp),
+           "rtg_gather")
+    return (out, skp) if skipped else out
+
+
 def _points(points):
     """Points as a contiguous (n, 3) float32 array, n, the int32 result and
     pointers that are never null for an empty batch."""
@@ -1253,6 +1350,36 @@ class Context:
                                       ctypes.c_void_p(lit_ptr) if lit_ptr else None,
                                       ctypes.c_void_p(stream) if stream else None),
                "rtg_matte_device")
+
+    def gather_device(self, hits_ptr: int, n: int, params, dirs_ptr: int, weights_ptr: int,
+                      n_dirs: int, dst_ptr: int, skipped_ptr: int = 0, stack_size: int = 6,
+                      stream: int = 0):
+        """The gather of n hit points at hits_ptr (device, 32-byte HIT_DTYPE records
+        as intersect_device writes them) with the direction table at dirs_ptr
+        (device, (n_dirs, 3) float32) and the weights at weights_ptr (device,
+        n_dirs float32) into dst_ptr (device, an (N, 3) float32 tensor) and, when
+        skipped_ptr is given, the counts of skipped probes (device, n uint16),
+        asynchronously on `stream`, under the context's semantics
+        (rtg_gather_device; params from gather_params())."""
+        p = np.ascontiguousarray(params, GATHER_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_gather_device(self._h, ctypes.c_void_p(hits_ptr), n, _ptr(p),
+                                       ctypes.c_void_p(dirs_ptr), ctypes.c_void_p(weights_ptr),
+                                       n_dirs, stack_size, ctypes.c_void_p(dst_ptr),
+                                       ctypes.c_void_p(skipped_ptr) if skipped_ptr else None,
+                                       ctypes.c_void_p(stream) if stream else None),
+               "rtg_gather_device")
+
+    def gather_rays_device(self, hits_ptr: int, n: int, params, dirs_ptr: int, n_dirs: int,
+                           dst_ptr: int, stream: int = 0):
+        """The n * K probe rays of those points into dst_ptr (device, 24-byte
+        RAY_DTYPE records, point-major), asynchronously on `stream`
+        (rtg_gather_rays_device; the context needs no scene)."""
+        p = np.ascontiguousarray(params, GATHER_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_gather_rays_device(self._h, ctypes.c_void_p(hits_ptr), n, _ptr(p),
+                                            ctypes.c_void_p(dirs_ptr), n_dirs,
+                                            ctypes.c_void_p(dst_ptr),
+                                            ctypes.c_void_p(stream) if stream else None),
+               "rtg_gather_rays_device")
 
     def contains_device(self, points_ptr: int, n: int, dst_ptr: int, stream: int = 0):
         """The containing sphere of n points at points_ptr (device, an (N, 3)

@@ -68,6 +68,12 @@ segments, visible, a torch fold); the containment of the refraction test points
 of the same hits.  --only-matte runs these alone and keeps FILE's other
 sections.
 
+The gather (csrc/rtg_gather.hip) gets rows under "gather" (gather_rows below):
+the fused call on the frame's primary hits next to the unfused chain (the ray
+generator, the batch ray tracer, a torch fold), with and without jitter and,
+with it, the ray order.  --only-gather runs these alone and keeps FILE's other
+sections.
+
 Many views in one launch (rtg_render_views_device, csrc/rtg_camera.hip) get
 rows under "views" (views_rows below): a bake of 256 probes x 6 cube faces of
 32 x 32 pixels, as one launch, as 1536 single-view launches and through the ray
@@ -351,6 +357,105 @@ def ao_rows(args, W, H, rays, stream):
 def _spread_rows(sums):
     return {k: {"ms_median": round(float(np.median(v)), 5), "ms_min": round(min(v), 5),
                 "ms_max": round(max(v), 5)} for k, v in sums.items()}
+
+
+def gather_rows(args, stream):
+    """The gather (csrc/rtg_gather.hip) of a frame's aa = 1 primary hits: C3 at
+    stack size 6 on the 3840 x 2160 frame, C5 at stack size 8 on a 640 x 360
+    frame (a jittered round of the full frame would take seconds) and, because
+    that frame gives the fused call's one lane per point only 3600 waves, on a
+    1920 x 1080 frame too; K = 16 probes
+    of rtg_ao_directions(16), weights 1 / K, bias 1e-3, jitter off and on.  Round
+    by round in one process: the fused call, and the pieces of the unfused chain
+    on the same hits: rtg_gather_rays_device (24 K bytes per point),
+    rtg_raytrace_device over the n K rays (12 K bytes per point), a torch fold
+    and, for the sorted form, rtg_ray_order_device of the rays plus the indexed
+    launch.  The unfused rows are the per-round sums of their pieces.  Reported,
+    not gated: whether the fused call is slower than the unfused chain by more
+    than the chain's own min-max spread.  Gated: the fused sums are, word for
+    word, the chain's colours folded on the host in the defined order."""
+    K = 16
+    table = torch.from_numpy(R.ao_directions(K)).cuda()
+    wt_np = np.full(K, F(1) / F(K), F)
+    wt = torch.from_numpy(wt_np).cuda()
+    out, ok = {"samples": K, "directions": K, "bias": 1e-3, "weights": "1 / K"}, True
+    for name, cfg, (W, H) in (("c3", "c3", CONFIGS["c3"][:2]), ("c5", "c5", (640, 360)),
+                              ("c5_1080p", "c5", (1920, 1080))):
+        n, S = W * H, CONFIGS[cfg][4] + 1
+        rays0 = torch.from_numpy(primary_rays(W, H)).cuda()
+        hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        rays = torch.empty((n * K, 6), dtype=torch.float32, device="cuda")
+        cols = torch.empty((n * K, 3), dtype=torch.float32, device="cuda")
+        cols_idx = torch.empty((n * K, 3), dtype=torch.float32, device="cuda")
+        acc = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        nbytes = R.ray_order_scratch(n * K)
+        scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device="cuda")
+        order = torch.empty((n * K,), dtype=torch.int32, device="cuda")
+        sph, lg = R.generate_scene(CONFIGS[cfg][2], CONFIGS[cfg][3], 42)
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        ctx.intersect_device(rays0.data_ptr(), n, hits.data_ptr(), stream)
+        real = (hits[:, 0] >= 0).cpu().numpy()
+        out[name] = {"W": W, "H": H, "points": n, "stack_size": S, "hit_points": int(real.sum()),
+                     "ray_bytes": n * K * 24, "colour_bytes": n * K * 12,
+                     "order_scratch_bytes": nbytes}
+        for label, flags in (("plain", 0), ("jitter", R.GATHER_JITTER)):
+            p = R.gather_params(K, 1e-3, 42, flags)
+            fns = [lambda: ctx.gather_device(hits.data_ptr(), n, p, table.data_ptr(), wt.data_ptr(),
+                                             K, acc.data_ptr(), stack_size=S, stream=stream),
+                   lambda: ctx.gather_rays_device(hits.data_ptr(), n, p, table.data_ptr(), K,
+                                                  rays.data_ptr(), stream),
+                   lambda: ctx.raytrace_device(rays.data_ptr(), n * K, cols.data_ptr(), S, stream),
+                   # (the weights are all 1 / K, so the jittered window folds the same way)
+                   lambda: (cols.view(n, K, 3) * wt.view(1, K, 1)).sum(1)]
+            if flags:
+                fns += [lambda: ctx.ray_order(rays.data_ptr(), n * K, order.data_ptr(),
+                                              scratch.data_ptr(), nbytes, stream=stream),
+                        lambda: ctx.raytrace_device(rays.data_ptr(), n * K, cols_idx.data_ptr(), S,
+                                                    stream, order=order.data_ptr())]
+            raw = []
+            m = measure(fns, args.rounds, raw=raw, min_reps=2,
+                        names=[f"gather {name} {label} {k}" for k in
+                               ("fused", "rays", "raytrace", "fold", "order", "indexed")][:len(fns)])
+            # the chain's colours folded on the host in the defined order
+            c = cols.cpu().numpy().reshape(n, K, 3)
+            want = np.zeros((n, 3), F)
+            with np.errstate(all="ignore"):
+                for k in range(K):
+                    want = want + wt_np[k] * c[:, k, :]
+            want[~real] = 0
+            del c
+            got = acc.cpu().numpy()
+
+            def words(a):
+                b = a.view(np.uint32).copy()
+                b[np.isnan(a)] = 0xFFC00000
+                return b
+            equal = bool((words(got) == words(want)).all())
+            if flags:
+                equal = equal and bool((cols.view(torch.int32) == cols_idx.view(torch.int32)).all())
+            ok = ok and equal
+            sums = {"unfused": [a + b + c for a, b, c in zip(raw[1], raw[2], raw[3])]}
+            if flags:
+                sums["unfused_sorted"] = [a + b + c + d for a, b, c, d in
+                                          zip(raw[1], raw[4], raw[5], raw[3])]
+            rows = _spread_rows(sums)
+            fu = m[0]
+            spread = rows["unfused"]["ms_max"] - rows["unfused"]["ms_min"]
+            out[name][label] = {
+                "fused": fu, "rays": m[1], "raytrace": m[2], "fold": m[3],
+                **({"order": m[4], "raytrace_indexed": m[5]} if flags else {}), **rows,
+                "unfused_over_fused": round(rows["unfused"]["ms_median"] / fu["ms_median"], 3),
+                "fused_slower_than_unfused_by_more_than_its_spread":
+                    bool(fu["ms_median"] - rows["unfused"]["ms_median"] > spread),
+                "Mprobes_per_s": round(n * K / (fu["ms_median"] * 1e-3) / 1e6, 1),
+                "nonfinite_share_of_sums": round(float((~np.isfinite(got[real]).all(1)).mean()), 4),
+                "fused_equals_chain_folded_on_host": equal}
+            print(f"gather {name} {label}: fused {fu['ms_median']} ms, unfused "
+                  f"{rows['unfused']['ms_median']} ms, equal {equal}", file=sys.stderr, flush=True)
+        ctx.close()
+        del rays0, hits, rays, cols, cols_idx, acc, scratch, order
+    return out, ok
 
 
 def matte_rows(args, W, H, rays, stream):
@@ -688,8 +793,10 @@ def main():
     ap.add_argument("--only-fold", action="store_true",
                     help="the rows of the views folded into SH coefficients alone, put into FILE "
                          "next to what it holds")
+    ap.add_argument("--only-gather", action="store_true",
+                    help="the gather's rows alone, put into FILE next to what it holds")
     ap.add_argument("--parent-commit", default="",
-                    help="recorded with --only-fold as the parent of --commit")
+                    help="recorded with --only-fold or --only-gather as the parent of --commit")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
     ap.add_argument("--order-alt-json", default=[], action="append",
@@ -717,6 +824,15 @@ def main():
         res["fold_commit"], res["fold_parent_commit"] = args.commit, args.parent_commit
         res["fold"], ok = fold_rows(args, torch.cuda.current_stream().cuda_stream)
         res["fold"]["rounds"] = args.rounds
+        finish(args, res, ok)
+    if args.only_gather:  # (the same: it makes the hits of its own two frames)
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["gather_commit"], res["gather_parent_commit"] = args.commit, args.parent_commit
+        res["gather"], ok = gather_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["gather"]["rounds"] = args.rounds
         finish(args, res, ok)
     W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
     assert (W, H) == CONFIGS["c5"][:2]
@@ -837,9 +953,10 @@ def main():
     res["matte"], matte_ok = matte_rows(args, W, H, rays, stream)
     res["contains"] = contains_rows(args, W, H, rays, stream)
     del rays
+    res["gather"], gather_ok = gather_rows(args, stream)
     res["views"], views_ok = views_rows(args, stream)
     res["fold"], fold_ok = fold_rows(args, stream)
-    ok = ok and cam_ok and order_ok and ao_ok and matte_ok and views_ok and fold_ok
+    ok = ok and cam_ok and order_ok and ao_ok and matte_ok and gather_ok and views_ok and fold_ok
     if args.mapping_json:
         with open(args.mapping_json) as f:
             other = json.load(f)["camera"]
