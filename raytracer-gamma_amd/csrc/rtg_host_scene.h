@@ -187,6 +187,12 @@ struct HostScene {
     return r;
   }
   float refr(int i) const { return mats[8 * (size_t)i + 7]; }
+  // refraction's constants of the material pair (scenes with masks: pack_scene)
+  void pair(int src, int tgt, float& ratio, float& qc) const {
+    const float* p = mats + 8 * (size_t)(n + 1) + 2 * ((size_t)src * (n + 1) + (size_t)tgt);
+    ratio = p[0];
+    qc = p[1];
+  }
   void hit_data(int i, V3& c, float& g2, float& r2, Mat& mt) const {
     c = sphere((unsigned)i, r2);
     g2 = guard_r2((unsigned)i);

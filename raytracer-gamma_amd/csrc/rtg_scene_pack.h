@@ -39,7 +39,9 @@ constexpr unsigned kMaskMaxSpheres = 64;
 // n x the primary-ray c term |0 - c|^2 - r^2 (same float operations and order
 // as the query's vdot(disp, disp) - r2 with disp = 0 - c, exact negation);
 // mats: (n+1) x {matte.xyz, gloss.xyz, opacity, n} with [n] = background
-// {0,0,0, 0,0,0, 0, 1.0} (raytracer.h:694-697; opacity 0);
+// {0,0,0, 0,0,0, 0, 1.0} (raytracer.h:694-697; opacity 0),
+// followed, in scenes with sphere masks, by (n+1)^2 material-pair records
+// {nSrc / nTgt, 1 - 1 / ratio^2} at (n+1) src + tgt (pair_consts below);
 // lights: m x {pos.xyz, col.xyz}.  Arrays are never empty (padded to 1).
 struct PackedScene {
   std::vector<float> geom, crad2, mats, lights;
@@ -934,6 +936,21 @@ inline bool build_bvh(const rtg_sphere* spheres, unsigned n, PackedScene* ps,
   return true;
 }
 
+// calculateRefraction's two values that depend on the pair (source material,
+// target material) alone: ratio = nSrc / nTgt (raytracer.h:700) and the
+// quadratic's c term 1 - 1 / ratio^2 (algebra.h:22-65 with a = 1), in
+// refraction's own float operations and order (rtg_trace.h; no contraction,
+// IEEE division, denormals kept).  Hostile indices (0, negative, denormal,
+// infinite, NaN) give what IEEE gives, as the kernel's own division does
+// (tests/test_gpu_refraction_exact.py::test_pair_table holds both sides to that).
+inline void pair_consts(float nSrc, float nTgt, float* out2) {
+  const float ratio = nSrc / nTgt;
+  const float rr = ratio * ratio;
+  const float inv = 1.f / rr;
+  out2[0] = ratio;
+  out2[1] = 1.f - inv;
+}
+
 inline void pack_scene(const rtg_sphere* spheres, unsigned n, const rtg_light* lights,
                        unsigned m, PackedScene* ps) {
   ps->n = n;
@@ -980,6 +997,14 @@ inline void pack_scene(const rtg_sphere* spheres, unsigned n, const rtg_light* l
   shadow_masks(spheres, n, lights, m, &ps->smask);
   if (!ps->smask.empty()) cone_masks(spheres, n, &ps->cone);
   else ps->cone.clear();
+  if (!ps->smask.empty()) {  // (n <= 64: at most 65^2 records, 33.8 KB)
+    const unsigned k = n + 1;
+    ps->mats.resize((size_t)k * 8 + (size_t)k * k * 2);
+    for (unsigned s = 0; s < k; ++s)
+      for (unsigned t = 0; t < k; ++t)
+        pair_consts(ps->mats[(size_t)s * 8 + 7], ps->mats[(size_t)t * 8 + 7],
+                    &ps->mats[(size_t)k * 8 + ((size_t)s * k + t) * 2]);
+  }
   if (build_bvh(spheres, n, ps)) {
     sphere_lists(spheres, n, lights, m, ps);
   }

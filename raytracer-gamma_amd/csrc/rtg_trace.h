@@ -40,6 +40,7 @@
 #include <math.h>
 
 #include <type_traits>
+#include <utility>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -806,6 +807,51 @@ RTG_HD double sqrt_d_unit(double y) {
   return sqrt(y);
 #endif
 }
+// calculateRefraction's sinA1 = (float)sqrt(1.0 - (double)cc), cc = fl(c * c)
+// for a float c in (-1, 1) (raytracer.h:683), in float operations only: the
+// same bits as the f64 island (sqrt_d_unit above, which the fpcheck library
+// still pins), 14 VALU instead of 18 with 11 of them f64.
+//  * 1 - cc as an exact float pair: yh = RN(1 - cc), yl = (1 - yh) - cc
+//    (Fast2Sum, 1 >= cc; both subtractions are exact).  yl != 0 only for
+//    cc < 1/2, where yh is in (1/2, 1] and |yl| <= 2^-25.
+//  * s = v_sqrt_f32(yh), one of the two floats around sqrt(yh).  The root of
+//    yh + yl is sqrt(yh) + yl / (2 sqrt(yh)), at most 0.36 ulp further, so its
+//    rounding is s or a neighbour of s.
+//  * sqrt_fast's selection with yl added to the residuals: fma(-s', s, yh) is
+//    exact, so the sum has the sign of (yh + yl) - s' s, and s' s is the
+//    square of the midpoint between s' and s less ulp^2 / 4, a gap that holds
+//    no value of yh + yl (for cc >= 2^-25 both are multiples of 2^-48, below
+//    it the result is 1).  yh = 0 gives 0 (both residual tests fail: NaN and
+//    0), NaN gives NaN.
+// The reference rounds twice (the f64 root, then to float) and, below
+// cc = 2^-30, 1 - cc too; that this never shows in the float is what the
+// enumeration establishes: tests/fpcheck/fpcheck_exact_gpu.hip compares the
+// two for EVERY float c in [0, 1) on the GPU (-c squares to the same cc), and
+// for either choice of the root estimate the same holds on the host
+// (with the material-pair records of refraction).
+RTG_HD float sin_from_cos2(float cc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float yh = 1.f - cc;
+  const float yl = (1.f - yh) - cc;
+  float s = __builtin_amdgcn_sqrtf(yh);
+  const float sd = __uint_as_float(__float_as_uint(s) - 1u);
+  const float su = __uint_as_float(__float_as_uint(s) + 1u);
+  const float rd = fmaf(-sd, s, yh) + yl;
+  const float ru = fmaf(-su, s, yh) + yl;
+  s = (rd <= 0.f) ? sd : s;
+  s = (ru > 0.f) ? su : s;
+  return s;
+#else
+  return (float)sqrt(1.0 - (double)cc);
+#endif
+}
+// raytracer.h:671-683: the cosine clamped to [-1, 1] and its sine (NaN: both
+// tests fail, the sine is NaN).
+RTG_HD float clamp_cos_sin(float& cosA1) {
+  if (cosA1 <= -1.0f) { cosA1 = -1.f; return 0.f; }
+  if (cosA1 >= 1.f) { cosA1 = 1.f; return 0.f; }
+  return sin_from_cos2(cosA1 * cosA1);
+}
 RTG_HD double div_d_fresnel(double a, double b, bool fast) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double y = __builtin_amdgcn_rcp(b);
@@ -859,19 +905,29 @@ RTG_HD float polarised_reflection(float n1, float n2, float cosA1, float cosA2) 
 // the refracted direction.  Returns the target material index.
 // hit >= 0: the sphere P lies on, and guardOK: P passed its guard-ball test;
 // then (scenes with masks) the refraction target's containment test runs over
-// the wave's union of overlap masks (primary_container_sel).
+// the wave's union of overlap masks (primary_container_sel), and `rm`, the
+// source material's index (nSrc is its refractive index), selects with the
+// target the scene's material-pair record {nSrc / nTgt, 1 - 1 / ratio^2}
+// (pack_scene: the same float operations, done once per scene) in place of
+// the division and the reciprocal.  Callers that give `hit` give `rm`.
+// (A scene type without the record's accessor `pair`, such as the tests' host
+// scenes, takes the expressions.)
+template <class S, class = void>
+struct HasPairTable : std::false_type {};
+template <class S>
+struct HasPairTable<S, std::void_t<decltype(std::declval<const S&>().pair(
+                           0, 0, std::declval<float&>(), std::declval<float&>()))>>
+    : std::true_type {};
 template <bool kCL = false, class Scene>
 RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRay,
-                      V3& dirOut, float& R, int hit = -1, bool guardOK = false) {
+                      V3& dirOut, float& R, int hit = -1, bool guardOK = false, int rm = -1) {
   float cosA1 = vdot(D, N);
-  float sinA1 = 0.f;
-  if (cosA1 <= -1.0f) { cosA1 = -1.f; sinA1 = 0.f; }
-  else if (cosA1 >= 1.f) { cosA1 = 1.f; sinA1 = 0.f; }
-  else sinA1 = (float)sqrt_d_unit(1.0 - (double)(cosA1 * cosA1));
+  const float sinA1 = clamp_cos_sin(cosA1);
 
   const V3 testPt = vadd(vsmul(0.01f, D), P);
   int tgt;
-  float nTgt;
+  float nTgt, ratio, qc = 0.f;
+  const bool table = HasPairTable<Scene>::value && hit >= 0 && sc.has_smask();
   if (hit >= 0 && sc.has_smask()) {
     const bool ok = guardOK && vdot(D, D) <= kContainDirMax * kContainDirMax;
     const uint64_t cu = sc.contain_union(hit, ok);
@@ -879,6 +935,8 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
     sc.count(kCntContainSel, __builtin_popcountll(cu));
     tgt = primary_container_sel(sc, testPt, cu, nTgt);
     if (tgt < 0) tgt = (int)sc.n;  // background material
+    if constexpr (HasPairTable<Scene>::value) sc.pair(rm, tgt, ratio, qc);
+    else ratio = nSrc / nTgt;
   } else {
     // BVH scene: the first containing sphere of each lane's hit sphere's
     // overlap list, the wave's distinct hit spheres in turn (container_lanes);
@@ -898,14 +956,14 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
       }
     }
     if (tgt < 0) tgt = (int)sc.n;  // background material
+    ratio = nSrc / nTgt;
   }
-  const float ratio = nSrc / nTgt;
   const float sinA2 = ratio * sinA1;
 
   if (wantRay) {
     // solveQuadratic(1, 2cosA1, 1 - 1/ratio^2), algebra.h:22-65 with a = 1.
     const float qb = 2.f * cosA1;
-    const float qc = 1.f - rcp_rn(ratio * ratio);
+    if (!table) qc = 1.f - rcp_rn(ratio * ratio);
     const float rad = (qb * qb) - ((4.f * 1.f) * qc);
     float r0, r1;
     int ns;
@@ -1156,7 +1214,7 @@ RTG_HD V3 trace_sample(const Scene& sc, V3 dir0, FStore&& fc, bool usePrim = fal
         sc.probe_begin(kProbeRefraction);
         sc.count(kCntRefraction, 1);
         sc.count(leaf ? kURefrLeaf : kURefr, 1);
-        const int tgt = Q == 4 ? refraction<kCL>(sc, d, P, N, mr.refr, !leaf, cdir, R, hit, guardOK)
+        const int tgt = Q == 4 ? refraction<kCL>(sc, d, P, N, mr.refr, !leaf, cdir, R, hit, guardOK, rm)
                                : refraction<kCL>(sc, d, P, N, mr.refr, !leaf, cdir, R);
         sc.probe_end(kProbeRefraction);
         // stage-1 reflection colour, raytracer.h:563-578

@@ -441,6 +441,16 @@ struct DevScene {
     return mat_at(fidx(mats, 8u * (unsigned)i));
   }
   __device__ __forceinline__ float refr(int i) const { return fidx(mats, 8u * (unsigned)i)[7]; }
+  // refraction's constants of the material pair (src, tgt), behind the n + 1
+  // material records in scenes with masks (pack_scene): one per-lane 8-byte
+  // load in place of a division, a reciprocal and their range checks
+  __device__ __forceinline__ void pair(int src, int tgt, float& ratio, float& qc) const {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const unsigned k = n + 1u;
+    const f2 v = *(const RTG_CONST f2*)fidx(mats, 8u * k + 2u * ((unsigned)src * k + (unsigned)tgt));
+    ratio = v[0];
+    qc = v[1];
+  }
   // The shading set-up's data of hit sphere i (>= 0): centre, guard radius^2
   // and material.  When every active lane hit the same sphere (a coherent
   // wave) they come through the scalar cache; otherwise per-lane gathers.

@@ -84,12 +84,15 @@ UNIT_COST = {
     "U.shadow": 3,
     # incidence / gap (10), sum += intensity * Lcol (6)
     "U.lit": 16,
-    # cos (5), clamps (4), f64 sinA1 (37), test point (6), |D| test (7), n ratio
-    # (10), solveQuadratic incl. sqrt_rn (28), the two candidate directions (32),
-    # cosA2 (16), two f64 Fresnel factors (80), R (2), reflection colour (18)
-    "U.refr": 245,
+    # cos (5), clamps (4), float-only sinA1 (15: the exact pair 3, v_sqrt 2, two
+    # neighbours 2, their residuals 4, selects 4), test point (6), |D| test (7),
+    # the material-pair record's address (2), solveQuadratic incl. sqrt_rn (21),
+    # the two candidate directions (32), cosA2 (16), two f64 Fresnel factors (80),
+    # R (2), reflection colour (18).  The masked scenes' form (C1-C4); BVH
+    # scenes have no pair table and divide: n ratio 10 and 1 - rcp_rn 7 more.
+    "U.refr": 208,
     # the same without the refracted direction (solveQuadratic and candidates)
-    "U.refrLeaf": 185,
+    "U.refrLeaf": 155,
     # 2 d.N (6), d - p N (6), vnorm (27), origin P + 0.01 rd (6), flags (3)
     "U.push": 48,
     # frame metadata (6), entering / origin-ball tests (8), child I (7), moves (7)
@@ -149,8 +152,14 @@ UNIT_COST.update({
     "U.lightDir": 35.96,
     "U.shadow": 3.06,
     "U.lit": 17.88,
-    "U.refr": 216.57,
-    "U.refrLeaf": 270.71,
+    # (after the fit sinA1 lost its f64 island and the masked scenes' refraction
+    # its division and reciprocal.  The fit is to SQ_INSTS_VALU, which counts an
+    # f64 instruction once, so the fitted 216.57 and 270.71 lose the INSTRUCTION
+    # deltas of the gfx950 listing by hand: sinA1 18 -> 14, the division 11 -> 2
+    # for the record's address, and with the refracted ray 1 - rcp_rn's 7:
+    # -20 and -13)
+    "U.refr": 196.57,
+    "U.refrLeaf": 257.71,
     "U.push": 50.08,
     "U.descend": 27.69,
     "U.unwind": 11.92,
