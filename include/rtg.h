@@ -36,6 +36,8 @@
  *     raytracer.h:313-367
  *   (one-bounce indirect light of a hit point: the      rtg_gather[_device|_host],
  *     caller's loop over rayTrace in the reference)       rtg_gather_rays[_device|_host]
+ *   (a frame of those per-pixel signals smoothed along   rtg_filter[_device|_host],
+ *     its surfaces, guided by the frame's hit records)    rtg_filter_scratch
  *   primaryContainer for a caller's own points         rtg_contains[_device|_host]
  *     raytracer.h:245-270
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
@@ -999,6 +1001,108 @@ int rtg_gather_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light*
                     const rtg_gather_params* params, const rtg_vec* dirs, const float* weights,
                     unsigned nDirs, int stackSize, int semantics, rtg_vec* outHost,
                     unsigned short* skippedHost, int walk, int nthreads);
+
+/* ---- filter: edge-stopping a-trous filter guided by hit records ----
+ * rtg_ao*'s counts, rtg_matte*'s and rtg_gather*'s colours at a few probes per
+ * pixel are Monte-Carlo noise.  These calls smooth such a frame along its
+ * surfaces with the edge-avoiding a-trous wavelet filter, guided by the
+ * frame's own rtg_hit records (the "denoiser guides" of the G-buffer), in
+ * float arithmetic that is defined here: the same words on the host and on
+ * every GPU.
+ *
+ * INPUTS.  A W x H frame, row-major, n = W * H pixels.  `hits`: n rtg_hit
+ * records exactly as rtg_intersect* writes them for the aa-1 rays of
+ * rtg_camera_rays*.  Of a record, id is read for its sign and for equality
+ * only (an id >= sphNum is legal), point and normal are used as given, t is
+ * not read.  `src`: n values of one `kind`: RTG_FILTER_RGB rtg_vec (3
+ * channels), RTG_FILTER_GRAY float, RTG_FILTER_COUNT unsigned short with value
+ * (float)c, which is exact (rtg_ao*'s counts go in as they are).  `dst`:
+ * rtg_vec for RGB, float for GRAY and COUNT.  The call needs no scene: the
+ * context only names the device, as for rtg_views_fold_device.
+ *
+ * ONE PASS of step s reads image `in` (floats) and writes `out`, all in float
+ * with no contraction and in this operand order; dot(a, b) = (a.x * b.x +
+ * a.y * b.y) + a.z * b.z:
+ *   centre p = (x, y) with id_p < 0:  out[p] = in[p]; there are no taps.
+ *   otherwise  sum.q = +0.f per channel q, sw = +0.f; then for dy = -2 .. 2
+ *            (outer) and dx = -2 .. 2 (inner), q = (x + dx * s, y + dy * s) in
+ *            integer arithmetic that cannot wrap.  The tap is left out
+ *            (nothing is added) when q is outside the frame, or id_q < 0, or
+ *            RTG_FILTER_SAME_ID is set and id_q != id_p, or
+ *            RTG_FILTER_SKIP_NONFINITE is set and any channel word of in[q]
+ *            has an all-ones exponent field (NaN, +-inf).  Otherwise
+ *              w = h[dy + 2] * h[dx + 2],  h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *                                          (every product is exact)
+ *              RTG_FILTER_NORMAL:  c = dot(N_p, N_q);  c = c > 0.f ? c : 0.f
+ *                                  (a NaN goes to 0); normalLog2 times c = c * c;
+ *                                  w = w * c
+ *              RTG_FILTER_PLANE:   e = P_q - P_p per component;
+ *                                  d = fabsf(dot(N_p, e));
+ *                                  z = 1.f - d * planeScale;
+ *                                  z = z > 0.f ? z : 0.f;  w = w * z
+ *              (a term whose flag is off is not multiplied in)
+ *              if (!(w > 0.f)) the tap is left out (zero, negative, NaN)
+ *              sum.q = sum.q + w * in[q].q per channel;  sw = sw + w
+ *            The centre tap is a tap like any other.
+ *   result   out[p].q = sw > 0.f ? sum.q / sw : in[p].q, the division the
+ *            correctly rounded float quotient.
+ * PASSES.  Pass i = 0 .. passes - 1 has step 1 << i.  Pass 0 reads src (COUNT
+ * converted), pass i the output of pass i - 1; the guides never change.  dst
+ * receives the last pass, NaN words stored as 0xFFC00000 as in every record.
+ * NaN, infinite and degenerate inputs follow the arithmetic and the
+ * comparisons as written.  The result depends on no scene, light, stack size
+ * or semantics.
+ *
+ * rtg_filter_host restates this in plain loops: the yardstick.
+ * rtg_filter_device is asynchronous on `stream`, allocates nothing, takes none
+ * of the context's render scratch and may be mixed with every other call on
+ * the context; `params` is host memory, read before the call returns.  It
+ * needs a caller-owned scratch of rtg_filter_scratch's bytes (the ping-pong
+ * image of passes >= 2; 0 for one pass, and then the scratch may be null):
+ * at least that many bytes, 16-byte aligned, the call's until it has finished
+ * on the stream.  dst holds intermediate passes before the last one lands.
+ *
+ * RTG_ERR_INVALID with a message, before any GPU call, for a null pointer (a
+ * null scratch is legal only when 0 bytes are needed), W or H equal to 0,
+ * W * H above 2^32 - 1 or (device) a grid above 2^31 - 1 workgroups, passes,
+ * normalLog2 or kind out of range, an unknown flag, hits off 16-byte alignment
+ * (device), a scratch that is too small or misaligned, and dst's byte range
+ * overlapping src's or the scratch's (addresses compared as numbers, on the
+ * host and on the device alike).
+ *
+ * Out of scope: a value- or variance-driven term (SVGF), temporal
+ * accumulation, rtg_gbuf_px records as guides, per-pass parameters, filtering
+ * ray batches that are not a frame, views and multi-GPU. */
+#define RTG_FILTER_MAX_PASSES 8
+#define RTG_FILTER_RGB   0           /* kind: src and dst are rtg_vec */
+#define RTG_FILTER_GRAY  1           /* kind: src and dst are float */
+#define RTG_FILTER_COUNT 2           /* kind: src is unsigned short, dst is float */
+#define RTG_FILTER_SAME_ID 1         /* a tap of another id is left out */
+#define RTG_FILTER_NORMAL 2          /* the normal term */
+#define RTG_FILTER_PLANE 4           /* the plane-distance term */
+#define RTG_FILTER_SKIP_NONFINITE 8  /* a tap whose value has a NaN or infinite word is left out */
+typedef struct rtg_filter_params {   /* 20 B */
+  unsigned passes;      /* 1..RTG_FILTER_MAX_PASSES; pass i has step 1 << i */
+  unsigned normalLog2;  /* 0..8: the clamped cosine is squared this many times */
+  float planeScale;     /* used as given */
+  unsigned kind;        /* RTG_FILTER_RGB / GRAY / COUNT */
+  unsigned flags;       /* RTG_FILTER_* bits; an unknown bit is RTG_ERR_INVALID */
+} rtg_filter_params;
+/* Bytes of scratch rtg_filter_device needs for such a frame. */
+int rtg_filter_scratch(unsigned width, unsigned height, const rtg_filter_params* params,
+                       size_t* bytes);
+/* Plain loops; the result does not depend on nthreads (threads take bands of
+ * rows of one pass).  nthreads <= 0: 1. */
+int rtg_filter_host(const rtg_hit* hits, unsigned width, unsigned height,
+                    const rtg_filter_params* params, const void* src, void* dstHost,
+                    int nthreads);
+int rtg_filter_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned width,
+                      unsigned height, const rtg_filter_params* params, const void* srcDevice,
+                      void* dstDevice, void* scratchDevice, size_t scratchBytes, void* stream);
+/* One-shot: uploads the hits and src, allocates its own scratch, runs on
+ * `device`, downloads n values. */
+int rtg_filter(int device, const rtg_hit* hits, unsigned width, unsigned height,
+               const rtg_filter_params* params, const void* src, void* dstHost);
 
 /* ---- containment: primaryContainer per point ----
  * "Which medium is this point in": out[i] is the lowest sphere index s for

@@ -69,6 +69,11 @@ static void usage() {
   printf("                           --camera or the identity pose; bias defaults to 0.001; a seed\n");
   printf("                           turns RTG_AO_JITTER on); needs --ao-out\n");
   printf("      --ao-out     FILE    The 8-bit binary PGM of (255 * count) / K per pixel\n");
+  printf("      --ao-filter  SPEC    Smooth the counts before they are written: PASSES[,planeScale\n");
+  printf("                           [,normalLog2]] (rtg_filter_device guided by the primary hits,\n");
+  printf("                           RTG_FILTER_SAME_ID | NORMAL | PLANE; planeScale defaults to 1,\n");
+  printf("                           normalLog2 to 3); the PGM is then 255 * value / K, clamped to\n");
+  printf("                           0..255; needs --ao\n");
   printf("      --matte      FILE    Also write the frame's direct light (rtg_matte_device of every\n");
   printf("                           primary hit at aa 1, from --camera or the identity pose) as a\n");
   printf("                           P6 PPM, scaled by its own largest component like the render\n");
@@ -79,6 +84,9 @@ static void usage() {
   printf("                           RTG_GATHER_JITTER on); needs --gather-out\n");
   printf("      --gather-out FILE    The P6 PPM, scaled by its own largest component like the render\n");
   printf("      --gather-skip        Leave NaN and infinite probe colours out (RTG_GATHER_SKIP_NONFINITE)\n");
+  printf("      --gather-filter SPEC Smooth the gathered light before it is scaled and written: the\n");
+  printf("                           spec and the filter of --ao-filter, with\n");
+  printf("                           RTG_FILTER_SKIP_NONFINITE under --gather-skip; needs --gather\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -100,6 +108,33 @@ static bool parse_pose(const char* s, rtg_camera* out) {
   return true;
 }
 
+// "PASSES[,planeScale[,normalLog2]]" of --ao-filter and --gather-filter; false when it is not that.
+static bool parse_filter(const char* s, rtg_filter_params* p) {
+  char tail = 0;
+  p->planeScale = 1.f;
+  p->normalLog2 = 3;
+  const int k = sscanf(s, "%u,%f,%u%c", &p->passes, &p->planeScale, &p->normalLog2, &tail);
+  p->flags = RTG_FILTER_SAME_ID | RTG_FILTER_NORMAL | RTG_FILTER_PLANE;
+  return k >= 1 && k <= 3 && p->passes >= 1 && p->passes <= RTG_FILTER_MAX_PASSES &&
+         p->normalLog2 <= 8;
+}
+
+// rtg_filter_device of the frame at `src` into a new device buffer, on the default stream.
+static void* filter_frame(rtg_context* ctx, const rtg_hit* hits, unsigned W, unsigned H,
+                          const rtg_filter_params& p, const void* src) {
+  const size_t n = (size_t)W * H, out = n * (p.kind == RTG_FILTER_RGB ? 3 : 1) * sizeof(float);
+  size_t bytes = 0;
+  check(rtg_filter_scratch(W, H, &p, &bytes), "rtg_filter_scratch");
+  void *dst = nullptr, *scratch = nullptr;
+  if (hipMalloc(&dst, out) != hipSuccess || (bytes && hipMalloc(&scratch, bytes) != hipSuccess))
+    check(RTG_ERR_NOMEM, "hipMalloc");
+  check(rtg_filter_device(ctx, hits, W, H, &p, src, dst, scratch, bytes, nullptr),
+        "rtg_filter_device");
+  if (hipDeviceSynchronize() != hipSuccess) check(RTG_ERR_HIP, "rtg_filter_device");
+  (void)hipFree(scratch);
+  return dst;
+}
+
 static bool parse_uint(const char* s, unsigned* out) {
   char* end;
   unsigned long v = strtoul(s, &end, 10);
@@ -117,6 +152,8 @@ int main(int argc, char** argv) {
   bool ao = false, matte = false, gather = false, gatherSkip = false;
   rtg_gather_params gatherParams = {0, 1.0e-3f, 0, 0};
   rtg_ao_params aoParams = {0, 0.f, 1.0e-3f, 0, 0};
+  bool aoFilter = false, gatherFilter = false;
+  rtg_filter_params aoFilterParams = {}, gatherFilterParams = {};
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   bool posed = false;
@@ -235,6 +272,14 @@ int main(int argc, char** argv) {
       gatherOut = need(a);
     } else if (!strcmp(a, "--gather-skip")) {
       gatherSkip = true;
+    } else if (!strcmp(a, "--ao-filter") || !strcmp(a, "--gather-filter")) {
+      const bool forAo = a[2] == 'a';
+      if (!parse_filter(need(a), forAo ? &aoFilterParams : &gatherFilterParams)) {
+        printf("Invalid filter (PASSES[,planeScale[,normalLog2]], PASSES in 1..%d, normalLog2 in "
+               "0..8)\n", RTG_FILTER_MAX_PASSES);
+        return 1;
+      }
+      (forAo ? aoFilter : gatherFilter) = true;
     } else if (!strcmp(a, "--matte")) {
       matteOut = need(a);
       matte = true;
@@ -286,6 +331,13 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (gatherSkip) gatherParams.flags |= RTG_GATHER_SKIP_NONFINITE;
+  if ((aoFilter && !ao) || (gatherFilter && !gather)) {
+    printf("--ao-filter needs --ao, --gather-filter needs --gather\n");
+    return 1;
+  }
+  aoFilterParams.kind = RTG_FILTER_COUNT;
+  gatherFilterParams.kind = RTG_FILTER_RGB;
+  if (gatherSkip) gatherFilterParams.flags |= RTG_FILTER_SKIP_NONFINITE;
 
   if (posed && gpus) {
     printf("--camera renders on one device\n");
@@ -550,9 +602,17 @@ int main(int argc, char** argv) {
     check(rtg_intersect_device(ctx, dr, n, dh, nullptr), "rtg_intersect_device");
     check(rtg_ao_device(ctx, dh, n, &aoParams, dd, K, dc, nullptr), "rtg_ao_device");
     std::vector<unsigned short> counts(n);
+    std::vector<float> smooth;
     if (hipMemcpy(counts.data(), dc, n * sizeof(unsigned short), hipMemcpyDeviceToHost) !=
         hipSuccess)
       check(RTG_ERR_HIP, "readback");
+    if (aoFilter) {  // the counts never leave the device on their way through the filter
+      void* df = filter_frame(ctx, dh, W, H, aoFilterParams, dc);
+      smooth.resize(n);
+      if (hipMemcpy(smooth.data(), df, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        check(RTG_ERR_HIP, "readback");
+      (void)hipFree(df);
+    }
     (void)hipFree(dr);
     (void)hipFree(dh);
     (void)hipFree(dd);
@@ -560,6 +620,10 @@ int main(int argc, char** argv) {
     rtg_context_destroy(ctx);
     std::vector<unsigned char> grey(n);
     for (size_t k = 0; k < n; ++k) grey[k] = (unsigned char)((255u * counts[k]) / K);
+    for (size_t k = 0; k < smooth.size(); ++k) {
+      const float v = 255.f * smooth[k] / (float)K;
+      grey[k] = (unsigned char)(v > 0.f ? (v < 255.f ? v : 255.f) : 0.f);  // (a NaN: 0)
+    }
     FILE* f = fopen(aoOut.c_str(), "wb");
     if (!f || fprintf(f, "P5\n%u %u\n255\n", W, H) < 0 ||
         fwrite(grey.data(), 1, n, f) != n || fclose(f) != 0) {
@@ -649,6 +713,11 @@ int main(int argc, char** argv) {
     check(rtg_gather_device(ctx, dh, n, &gatherParams, dd, dw, K, (int)depth + 1, dl, nullptr,
                             nullptr),
           "rtg_gather_device");
+    if (gatherFilter) {
+      rtg_vec* smooth = (rtg_vec*)filter_frame(ctx, dh, W, H, gatherFilterParams, dl);
+      (void)hipFree(dl);
+      dl = smooth;
+    }
     check(rtg_max_colour_device(ctx, dl, n, dmax, nullptr), "rtg_max_colour_device");
     check(rtg_ppm_bytes_device(ctx, dl, n, dmax, db, nullptr), "rtg_ppm_bytes_device");
     std::vector<unsigned char> bytes(n * 3);

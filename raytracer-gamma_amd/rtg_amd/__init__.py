@@ -72,6 +72,13 @@ GATHER_JITTER, GATHER_SKIP_NONFINITE = 1, 2
 FOLD_PARAMS_DTYPE = np.dtype([("viewsPerGroup", "<u4"), ("weights", "<u4"), ("flags", "<u4")])
 assert FOLD_PARAMS_DTYPE.itemsize == 12
 FOLD_MAX_WEIGHTS, FOLD_SKIP_NONFINITE = 16, 1  # RTG_FOLD_*
+# rtg_filter_params (include/rtg.h): the edge-stopping a-trous filter
+FILTER_PARAMS_DTYPE = np.dtype([("passes", "<u4"), ("normalLog2", "<u4"), ("planeScale", "<f4"),
+                                ("kind", "<u4"), ("flags", "<u4")])
+assert FILTER_PARAMS_DTYPE.itemsize == 20
+FILTER_MAX_PASSES = 8  # RTG_FILTER_*
+FILTER_RGB, FILTER_GRAY, FILTER_COUNT = 0, 1, 2
+FILTER_SAME_ID, FILTER_NORMAL, FILTER_PLANE, FILTER_SKIP_NONFINITE = 1, 2, 4, 8
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -108,6 +115,7 @@ EXPORTED = [
     "rtg_matte_device", "rtg_matte", "rtg_matte_host",
     "rtg_gather_rays_host", "rtg_gather_rays_device", "rtg_gather_device", "rtg_gather",
     "rtg_gather_host",
+    "rtg_filter_scratch", "rtg_filter_host", "rtg_filter_device", "rtg_filter",
     "rtg_contains_device", "rtg_contains", "rtg_contains_host",
 ]
 
@@ -252,6 +260,18 @@ def lib() -> ctypes.CDLL:
                 ("rtg_gather_device", [vp, vp, sz, vp, vp, vp, u, i, vp, vp, vp]),
                 ("rtg_gather", [i, vp, u, vp, u, vp, sz, vp, vp, vp, u, i, vp, vp]),
                 ("rtg_gather_host", [vp, u, vp, u, vp, sz, vp, vp, vp, u, i, i, vp, vp, i, i])):
+            try:
+                getattr(L, name).argtypes = at
+            except AttributeError:
+                if not os.environ.get("RTG_LIB"):
+                    raise
+        # the filter; an RTG_LIB build of the commit before it (tools/ab_bench.sh
+        # against the parent) loads without it
+        for name, at in (
+                ("rtg_filter_scratch", [u, u, vp, vp]),
+                ("rtg_filter_host", [vp, u, u, vp, vp, vp, i]),
+                ("rtg_filter_device", [vp, vp, u, u, vp, vp, vp, vp, sz, vp]),
+                ("rtg_filter", [i, vp, u, u, vp, vp, vp])):
             try:
                 getattr(L, name).argtypes = at
             except AttributeError:
@@ -974,6 +994,59 @@ def gather(spheres, lights, hits, dirs, weights, params, stack_size: int = 6, de
     return (out, skp) if skipped else out
 
 
+def filter_params(passes: int, kind: int = FILTER_RGB, flags: int = 0, plane_scale: float = 0.0,
+                  normal_log2: int = 0) -> np.ndarray:
+    """One rtg_filter_params record (kind: FILTER_RGB / GRAY / COUNT; flags:
+    FILTER_SAME_ID | NORMAL | PLANE | SKIP_NONFINITE)."""
+    p = np.zeros(1, FILTER_PARAMS_DTYPE)
+    p[0] = (passes, normal_log2, plane_scale, kind, flags)
+    return p
+
+
+def filter_scratch(width: int, height: int, params) -> int:
+    """Bytes of device scratch Context.filter_device needs for such a frame
+    (rtg_filter_scratch): caller-owned, 16-byte aligned; 0 for one pass."""
+    p = np.ascontiguousarray(params, FILTER_PARAMS_DTYPE).reshape(1)
+    out = ctypes.c_size_t(0)
+    _check(lib().rtg_filter_scratch(width, height, _ptr(p), ctypes.byref(out)),
+           "rtg_filter_scratch")
+    return out.value
+
+
+def _filter_args(hits, width: int, height: int, params, src):
+    """Hit records, params and the source as contiguous arrays of the kind's
+    type, and the destination: (H, W, 3) float32 for RGB, (H, W) otherwise."""
+    p = np.ascontiguousarray(params, FILTER_PARAMS_DTYPE).reshape(1)
+    kind = int(p["kind"][0])
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    s = np.ascontiguousarray(src, np.uint16 if kind == FILTER_COUNT else np.float32).reshape(-1)
+    n = width * height
+    if len(h) != n or len(s) != n * (3 if kind == FILTER_RGB else 1):
+        raise ValueError(f"filter: {len(h)} hit records and {len(s)} source words for a "
+                         f"{width} x {height} frame of kind {kind}")
+    out = np.empty((height, width, 3) if kind == FILTER_RGB else (height, width), np.float32)
+    return h, p, s, out
+
+
+def filter_host(hits, width: int, height: int, params, src, threads: int = 1) -> np.ndarray:
+    """The edge-stopping a-trous filter on the host (rtg_filter_host; no GPU
+    needed): HIT_DTYPE records of the frame's aa-1 primary rays as guides, src
+    the frame's signal (float32 (H, W, 3) or (H, W), or uint16 counts), params
+    from filter_params(); float32 out."""
+    h, p, s, out = _filter_args(hits, width, height, params, src)
+    _check(lib().rtg_filter_host(_ptr(h), width, height, _ptr(p), _ptr(s), _ptr(out), threads),
+           "rtg_filter_host")
+    return out
+
+
+def filter(hits, width: int, height: int, params, src, device: int = 0) -> np.ndarray:  # noqa: A001
+    """The same on the GPU, one-shot (rtg_filter)."""
+    h, p, s, out = _filter_args(hits, width, height, params, src)
+    _check(lib().rtg_filter(device, _ptr(h), width, height, _ptr(p), _ptr(s), _ptr(out)),
+           "rtg_filter")
+    return out
+
+
 def _points(points):
     """Points as a contiguous (n, 3) float32 array, n, the int32 result and
     pointers that are never null for an empty batch."""
@@ -1337,6 +1410,23 @@ class Context:
                                             ctypes.c_void_p(dst_ptr),
                                             ctypes.c_void_p(stream) if stream else None),
                "rtg_ao_segments_device")
+
+    def filter_device(self, hits_ptr: int, width: int, height: int, params, src_ptr: int,
+                      dst_ptr: int, scratch_ptr: int = 0, scratch_bytes: int = 0,
+                      stream: int = 0):
+        """The edge-stopping a-trous filter of a width x height frame: guides at
+        hits_ptr (device, 32-byte HIT_DTYPE records as intersect_device writes
+        them), the signal at src_ptr (device; float32 x 3, float32 or uint16 per
+        pixel by params' kind) into dst_ptr (device, float32 per channel),
+        asynchronously on `stream` (rtg_filter_device; params from
+        filter_params(), the scratch filter_scratch() bytes, 16-byte aligned; the
+        context needs no scene)."""
+        p = np.ascontiguousarray(params, FILTER_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_filter_device(self._h, ctypes.c_void_p(hits_ptr), width, height, _ptr(p),
+                                       ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr),
+                                       ctypes.c_void_p(scratch_ptr), scratch_bytes,
+                                       ctypes.c_void_p(stream) if stream else None),
+               "rtg_filter_device")
 
     def matte_device(self, hits_ptr: int, n: int, dst_ptr: int, lit_ptr: int = 0,
                      stream: int = 0):

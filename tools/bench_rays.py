@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
                        [--only-order] [--only-ao] [--only-matte] [--only-views]
-                       [--only-fold]
+                       [--only-fold] [--only-gather] [--only-filter]
                        [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
@@ -85,6 +85,12 @@ csrc/rtg_fold.hip) get rows under "fold" (fold_rows below): the same bake
 through the fused call, through rtg_render_views_device + rtg_views_fold_device
 and through rtg_render_views_device + a torch einsum, with the bytes each route
 allocates.  --only-fold runs these alone and keeps FILE's other sections.
+
+The edge-stopping a-trous filter (rtg_filter_device, csrc/rtg_filter.hip) gets
+rows under "filter" (filter_rows below): five passes over the frame's AO counts
+and gathered light, the total and each pass, the tiled and the direct form of
+the pass kernel side by side per step, and a torch chain of the same
+arithmetic.  --only-filter runs these alone and keeps FILE's other sections.
 GPU only.
 """
 import argparse
@@ -458,6 +464,176 @@ def gather_rows(args, stream):
     return out, ok
 
 
+def torch_filter(ids, P, N, img, passes, flags, normal_log2, scale):
+    """rtg_filter*'s arithmetic as a torch chain: shifted slices over the padded
+    planes, `where` for the left-out taps.  ids (H, W) int32, P and N three
+    (H, W) planes each, img a list of C (H, W) planes; the filtered planes."""
+    import torch.nn.functional as TF
+    H, W = ids.shape
+    hw = (0.0625, 0.25, 0.375, 0.25, 0.0625)
+    zero = torch.zeros((), dtype=torch.float32, device=ids.device)
+    for i in range(passes):
+        s = 1 << i
+        b = 2 * s
+        pad = lambda a, v: TF.pad(a, (b, b, b, b), value=v)  # noqa: E731
+        idp = pad(ids, -1)
+        Pp, Np, vp = [pad(a, 0.0) for a in P], [pad(a, 0.0) for a in N], [pad(a, 0.0) for a in img]
+        acc = [torch.zeros_like(a) for a in img]
+        sw = torch.zeros_like(img[0])
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                ys, xs = slice(b + dy * s, b + dy * s + H), slice(b + dx * s, b + dx * s + W)
+                idq = idp[ys, xs]
+                keep = idq >= 0
+                if flags & R.FILTER_SAME_ID:
+                    keep &= idq == ids
+                if flags & R.FILTER_SKIP_NONFINITE:
+                    for a in vp:
+                        keep &= torch.isfinite(a[ys, xs])
+                w = torch.full_like(sw, hw[dy + 2] * hw[dx + 2])
+                if flags & R.FILTER_NORMAL:
+                    c = (N[0] * Np[0][ys, xs] + N[1] * Np[1][ys, xs]) + N[2] * Np[2][ys, xs]
+                    c = torch.where(c > 0, c, zero)
+                    for _ in range(normal_log2):
+                        c = c * c
+                    w = w * c
+                if flags & R.FILTER_PLANE:
+                    e = [Pp[q][ys, xs] - P[q] for q in range(3)]
+                    d = ((N[0] * e[0] + N[1] * e[1]) + N[2] * e[2]).abs()
+                    z = 1.0 - d * scale
+                    w = w * torch.where(z > 0, z, zero)
+                keep &= w > 0
+                w = torch.where(keep, w, zero)
+                for q in range(len(img)):
+                    acc[q] += torch.where(keep, w * vp[q][ys, xs], zero)
+                sw += w
+        done = (sw > 0) & (ids >= 0)
+        img = [torch.where(done, acc[q] / sw, img[q]) for q in range(len(img))]
+    return img
+
+
+def filter_rows(args, stream):
+    """The edge-stopping a-trous filter (csrc/rtg_filter.hip) at passes 5 with
+    SAME_ID | NORMAL | PLANE, planeScale 1 / (the scene's largest |radius|),
+    normalLog2 3, on the aa = 1 primary hits of C3 and C5: the counts of
+    rtg_ao_device (K = 16, jittered) at 3840 x 2160, the light of
+    rtg_gather_device (K = 16, jittered, the skip flag) at 3840 x 2160 on C3 and
+    1920 x 1080 on C5.  Round by round in one process: the call as it chooses
+    its forms, the call with each form forced (RTG_FILTER_FORM) at passes 1 to 5,
+    whose differences are the passes on their own (step 16 does not fit the
+    tiled form's LDS and runs direct under either name), and a torch chain of
+    the same arithmetic.  Reported, not gated: every time, and each pass's
+    distance from the streaming floor (32 guide bytes, the value in and out per
+    pixel at 6 TB/s).  Gated: the call and the torch chain agree to 1e-4
+    relative on finite pixels (torch's sum order is its own: a sanity bound)."""
+    K, passes, nlog = 16, 5, 3
+    FORMS = ("tiled", "direct")
+    flags = R.FILTER_SAME_ID | R.FILTER_NORMAL | R.FILTER_PLANE
+    table = torch.from_numpy(R.ao_directions(K)).cuda()
+    wt = torch.full((K,), 1.0 / K, dtype=torch.float32, device="cuda")
+    out, ok = {"passes": passes, "flags": flags, "normalLog2": nlog, "samples": K,
+               "floor_bandwidth_TBps": 6.0}, True
+    for name, cfg, (W, H), kind in (("c3_count", "c3", CONFIGS["c3"][:2], R.FILTER_COUNT),
+                                    ("c5_count", "c5", CONFIGS["c5"][:2], R.FILTER_COUNT),
+                                    ("c3_rgb", "c3", CONFIGS["c3"][:2], R.FILTER_RGB),
+                                    ("c5_rgb_1080p", "c5", (1920, 1080), R.FILTER_RGB)):
+        n, S, C = W * H, CONFIGS[cfg][4] + 1, 3 if kind == R.FILTER_RGB else 1
+        sph, lg = R.generate_scene(CONFIGS[cfg][2], CONFIGS[cfg][3], 42)
+        scale = float(F(1) / np.abs(sph["radius"]).max())
+        rays0 = torch.from_numpy(primary_rays(W, H)).cuda()
+        hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        ctx.intersect_device(rays0.data_ptr(), n, hits.data_ptr(), stream)
+        if kind == R.FILTER_COUNT:
+            src = torch.empty((n,), dtype=torch.int16, device="cuda")
+            radius = float(F(2.5) * np.abs(sph["radius"]).max())
+            ctx.ao_device(hits.data_ptr(), n, R.ao_params(K, radius, 1e-3, 42, R.AO_JITTER),
+                          table.data_ptr(), K, src.data_ptr(), stream)
+        else:
+            src = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+            gp = R.gather_params(K, 1e-3, 42, R.GATHER_JITTER | R.GATHER_SKIP_NONFINITE)
+            ctx.gather_device(hits.data_ptr(), n, gp, table.data_ptr(), wt.data_ptr(), K,
+                              src.data_ptr(), stack_size=S, stream=stream)
+        torch.cuda.synchronize()
+        del rays0
+        dst = torch.empty((n, C), dtype=torch.float32, device="cuda")
+        ps = [R.filter_params(k, kind, flags, scale, nlog) for k in range(1, passes + 1)]
+        nbytes = R.filter_scratch(W, H, ps[-1])
+        scratch = torch.empty((max(nbytes, 16) // 4,), dtype=torch.int32, device="cuda")
+
+        def call(form, p):
+            if form:
+                os.environ["RTG_FILTER_FORM"] = form
+            else:
+                os.environ.pop("RTG_FILTER_FORM", None)
+            ctx.filter_device(hits.data_ptr(), W, H, p, src.data_ptr(), dst.data_ptr(),
+                              scratch.data_ptr(), nbytes, stream)
+
+        fns = [lambda: call("", ps[-1])]
+        fns += [(lambda f=f, p=p: call(f, p)) for f in FORMS for p in ps]
+        raw = []
+        m = measure(fns, args.rounds, window_ms=100.0, raw=raw,
+                    names=[f"filter {name} default"] + [f"filter {name} {f} passes {k}" for f in FORMS
+                                                         for k in range(1, passes + 1)])
+        os.environ.pop("RTG_FILTER_FORM", None)
+        floor = n * (32 + 8 * C) / 6.0e12 * 1e3
+        forms = {}
+        for fi, f in enumerate(FORMS):
+            cum = raw[1 + fi * passes:1 + (fi + 1) * passes]
+            per = [cum[0]] + [[b - a for a, b in zip(cum[k - 1], cum[k])] for k in range(1, passes)]
+            forms[f] = {"cumulative": m[1 + fi * passes:1 + (fi + 1) * passes],
+                        "pass_ms_median": [round(float(np.median(v)), 5) for v in per],
+                        "pass_ms_min": [round(min(v), 5) for v in per],
+                        "pass_ms_max": [round(max(v), 5) for v in per],
+                        "pass_over_floor": [round(float(np.median(v)) / floor, 2) for v in per]}
+        # the call's own answer, then the torch chain of the same arithmetic
+        call("", ps[-1])
+        torch.cuda.synchronize()
+        got = dst.clone()
+        h = hits.view(torch.float32)
+        ids = hits[:, 0].reshape(H, W).contiguous()
+        P = [h[:, 2 + q].reshape(H, W).contiguous() for q in range(3)]
+        N = [h[:, 5 + q].reshape(H, W).contiguous() for q in range(3)]
+        if kind == R.FILTER_COUNT:
+            img = [(src.to(torch.int32) & 0xFFFF).to(torch.float32).reshape(H, W)]
+        else:
+            img = [src[:, q].reshape(H, W).contiguous() for q in range(3)]
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        chain = lambda: torch_filter(ids, P, N, img, passes, flags, nlog, scale)  # noqa: E731
+        ref = torch.stack(chain(), -1).reshape(n, C)
+        torch.cuda.synchronize()
+        extra = torch.cuda.max_memory_allocated() - base - ref.numel() * 4
+        tm = measure([chain], args.rounds, window_ms=100.0, min_reps=1,
+                     names=[f"filter {name} torch chain"])[0]
+        fin = torch.isfinite(got) & torch.isfinite(ref)
+        same_nonfinite = bool((torch.isfinite(got) == torch.isfinite(ref)).all())
+        rel = ((got - ref).abs() / ref.abs().clamp_min(1e-30))[fin]
+        worst = float(rel.max()) if rel.numel() else 0.0
+        agree = same_nonfinite and worst <= 1e-4
+        ok = ok and agree
+        real = hits[:, 0] >= 0
+        out[name] = {
+            "W": W, "H": H, "kind": int(kind), "hit_points": int(real.sum()),
+            "plane_scale": scale, "floor_ms_per_pass": round(floor, 5), "default": m[0],
+            "default_forms": "tiled up to step 4, direct beyond", "forms": forms,
+            "filter_scratch_bytes": nbytes, "torch_chain": tm, "torch_extra_bytes": int(extra),
+            "torch_over_filter": round(tm["ms_median"] / m[0]["ms_median"], 2),
+            "changed_share_of_hit_pixels": round(float(
+                ((got != torch.stack(img, -1).reshape(n, C)).any(1) & real).sum() / real.sum()), 4),
+            "largest_relative_difference": worst, "bit_equal": bool(
+                (got.view(torch.int32)[fin] == ref.view(torch.int32)[fin]).all()),
+            "agree_to_1e-4": agree}
+        print(f"filter {name}: {m[0]['ms_median']} ms, torch {tm['ms_median']} ms, "
+              f"largest relative difference {worst:.3g}", file=sys.stderr, flush=True)
+        ctx.close()
+        del hits, src, dst, scratch, got, ref, ids, P, N, img, h, fin, rel, real
+        torch.cuda.empty_cache()
+    return out, ok
+
+
 def matte_rows(args, W, H, rays, stream):
     """Direct light (csrc/rtg_matte.hip) of the frame's 8.3 M aa = 1 primary
     hits on C3 (3 lights) and C5 (4 lights).  Round by round in one process: the
@@ -795,8 +971,11 @@ def main():
                          "next to what it holds")
     ap.add_argument("--only-gather", action="store_true",
                     help="the gather's rows alone, put into FILE next to what it holds")
+    ap.add_argument("--only-filter", action="store_true",
+                    help="the filter's rows alone, put into FILE next to what it holds")
     ap.add_argument("--parent-commit", default="",
-                    help="recorded with --only-fold or --only-gather as the parent of --commit")
+                    help="recorded with --only-fold, --only-gather or --only-filter as the parent "
+                         "of --commit")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
     ap.add_argument("--order-alt-json", default=[], action="append",
@@ -833,6 +1012,15 @@ def main():
         res["gather_commit"], res["gather_parent_commit"] = args.commit, args.parent_commit
         res["gather"], ok = gather_rows(args, torch.cuda.current_stream().cuda_stream)
         res["gather"]["rounds"] = args.rounds
+        finish(args, res, ok)
+    if args.only_filter:  # (the same: it makes the hits and the signals of its own frames)
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["filter_commit"], res["filter_parent_commit"] = args.commit, args.parent_commit
+        res["filter"], ok = filter_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["filter"]["rounds"] = args.rounds
         finish(args, res, ok)
     W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
     assert (W, H) == CONFIGS["c5"][:2]
