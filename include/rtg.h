@@ -1148,6 +1148,12 @@ int rtg_diag_read(rtg_context* ctx, unsigned long long* out8, int reset);
  * .. n) lane-level sums.  Copies min(cap, n) values, optionally zeroes them,
  * and returns n (cap <= 0: just returns n); negative on error. */
 int rtg_diag_counts(rtg_context* ctx, unsigned long long* out, int cap, int reset);
+/* Diagnostic, no GPU: *ranged = 1 when the scene passes the value-range proof
+ * under which renders of scenes with sphere masks run the kernel compiled
+ * without its rare-path guards (every refractive index finite, with
+ * 2^-96 <= |n| <= 2^96), else 0 (such a scene renders through the guarded
+ * kernel; the frame is the same either way). */
+int rtg_scene_ranged(const rtg_sphere* spheres, unsigned sphNum, int* ranged);
 #define RTG_LAUNCH_TIMELINE 1 /* record a per-wave timeline (rtg_diag_timeline) */
 /* Compacted launches list pixel groups heaviest first, by the trace times the
  * previous launch of the same frame geometry measured (launch-order feedback:

@@ -331,6 +331,9 @@ struct rtg_context {
   rtg_launch_opts opts{};
   int semantics = RTG_SEMANTICS_CPU;
   bool hasScene = false;
+  // the scene passed scene_ranged (PackedScene::ranged): with its masks, the
+  // compacted launch takes the kernel compiled without the rare-path guards
+  bool sceneRanged = false;
   // the last rtg_context_set_scene: host preparation ms (records, masks,
   // cone masks, BVH), upload ms, device bytes, BVH nodes (rtg_context_scene_stats)
   double sceneStats[4] = {0, 0, 0, 0};
@@ -382,6 +385,7 @@ static void free_scene(rtg_context* c) {
   for (const SceneTable& e : kSceneTables) (void)hipFree(e.get(c->scene));
   c->scene = SceneTables{};
   c->hasScene = false;
+  c->sceneRanged = false;
 }
 
 bool rtg_context_scene(const rtg_context* ctx, SceneTables* t, int* device, RayBox* box,
@@ -572,6 +576,16 @@ int rtg_context_scene_stats(rtg_context* ctx, double* out4) {
   return RTG_OK;
 }
 
+int rtg_scene_ranged(const rtg_sphere* spheres, unsigned sphNum, int* ranged) {
+  rtg_clear_error();
+  if (!ranged || (sphNum && !spheres)) {
+    rtg_set_error("rtg_scene_ranged: null argument");
+    return RTG_ERR_INVALID;
+  }
+  *ranged = scene_ranged(spheres, sphNum) ? 1 : 0;
+  return RTG_OK;
+}
+
 int rtg_diag_counts(rtg_context* ctx, unsigned long long* out, int cap, int reset) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
@@ -754,6 +768,7 @@ int rtg_context_set_scene(rtg_context* ctx, const rtg_sphere* spheres, unsigned 
   ctx->scene.n = sphNum;
   ctx->scene.m = lgtNum;
   ctx->scene.n4 = ps.n4;
+  ctx->sceneRanged = ps.ranged;
   ctx->rayBox = ray_box(ps.originBox);
   float keyLo[3], keyHi[3];
   key_bounds(spheres, sphNum, keyLo, keyHi);
@@ -1008,8 +1023,11 @@ static int launch_trace(rtg_context* ctx, unsigned width, unsigned height, float
     }
   }
   // the compacted default kernel of a scene with shadow/overlap and cone masks
-  // takes them as compile-time facts (kMasks)
-  const int listKind = !listed ? 0 : (ctx->scene.smask && ctx->scene.cone) ? 2 : 1;
+  // takes them as compile-time facts (kMasks), and the scene's range proof
+  // with them (kRanged): trace_fn_v's list kinds
+  const int listKind = !listed ? 0
+                       : !(ctx->scene.smask && ctx->scene.cone) ? 1
+                       : ctx->sceneRanged ? 3 : 2;
   const StackKernels* sk = stack_kernels(stackSize);
   TraceFn fn = sk ? sk->trace(variant, ctx->scene.bvhNodes != nullptr, listKind) : nullptr;
   if (!fn) {

@@ -67,6 +67,8 @@ struct PackedScene {
   std::vector<unsigned> capOff, ovOff;
   unsigned n = 0, m = 0;
   unsigned n4 = 0;  // n rounded up to a multiple of 4; geom holds 3 x (n4 + 4) records + the fused part
+  // The scene passed scene_ranged (below); only read with the sphere masks.
+  bool ranged = false;
 };
 
 // Shadow-ray sphere masks.  A shadow ray of raytracer.h:272-309 starts at the
@@ -951,6 +953,23 @@ inline void pair_consts(float nSrc, float nTgt, float* out2) {
   out2[1] = 1.f - inv;
 }
 
+// The scene fact behind the masked kernel's range proofs (IsRangedScene,
+// rtg_trace.h): every refractive index n_i, and the background's 1.0, has
+// 2^-96 <= |n_i| <= 2^96.  The kernel's proof (polarised_reflection) needs
+// |n_i| <= 2^100 and no NaN; the margin of 2^4 is explicit, and the lower
+// bound, which that proof does not need, keeps every material pair's ratio
+// n_s / n_t finite and non-zero.  Anything else, a zero, an infinity or a NaN
+// included, fails (the comparison is false for a NaN), and a scene fails as
+// soon as one sphere does: appending a sphere never turns a failing scene
+// into a passing one.
+inline bool scene_ranged(const rtg_sphere* spheres, unsigned n) {
+  for (unsigned i = 0; i < n; ++i) {
+    const double v = fabs((double)spheres[i].material.refractiveIndex);
+    if (!(v >= 0x1p-96 && v <= 0x1p96)) return false;
+  }
+  return true;
+}
+
 inline void pack_scene(const rtg_sphere* spheres, unsigned n, const rtg_light* lights,
                        unsigned m, PackedScene* ps) {
   ps->n = n;
@@ -994,6 +1013,7 @@ inline void pack_scene(const rtg_sphere* spheres, unsigned n, const rtg_light* l
     mt[6] = s.material.opacity; mt[7] = s.material.refractiveIndex;
   }
   ps->mats[(size_t)n * 8 + 7] = 1.00f;
+  ps->ranged = scene_ranged(spheres, n);
   shadow_masks(spheres, n, lights, m, &ps->smask);
   if (!ps->smask.empty()) cone_masks(spheres, n, &ps->cone);
   else ps->cone.clear();

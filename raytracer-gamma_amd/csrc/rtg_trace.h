@@ -152,6 +152,28 @@ RTG_HD float cull_rsq(float x) {
 #endif
 }
 RTG_HD float rtg_sqrtf(float x) { return sqrt_rn(x); }
+// sqrt_fast made total on the negatives: v_sqrt_f32 reads a subnormal operand
+// as a zero, so sqrt_fast alone returns -0 for the negative subnormals where
+// sqrtf returns a NaN (every other negative, and -inf, is a NaN already; -0
+// stays -0, as from sqrtf).  One compare and one select, no scalar work.
+// Equal to sqrtf on 0, [2^-96, +inf], every float with the sign bit set and
+// every NaN (NaNs by position): tests/fpcheck/fpcheck_ranged_gpu.hip.
+RTG_HD float sqrt_fast_signed(float x) {
+  const float s = sqrt_fast(x);
+#if defined(__HIP_DEVICE_COMPILE__)
+  return x < 0.f ? __builtin_nanf("") : s;
+#else
+  return s;
+#endif
+}
+// The same as rtg_sqrtf with the range check compiled out where the call site
+// proves that sqrt_fast_signed returns sqrtf's result (kShort; proofs at the
+// sites).
+template <bool kShort>
+RTG_HD float sqrt_sel(float x) {
+  if constexpr (kShort) return sqrt_fast_signed(x);
+  else return sqrt_rn(x);
+}
 // rcp_rn(sqrt_rn(x)) with ONE range check: for x in sqrt_fast's range the
 // rounded root lies in [2^-48, 2^64], inside rcp_fast's, so both short
 // sequences hold; outside it, both compiler sequences (same results).
@@ -310,20 +332,29 @@ RTG_HD RayQ query_head(V3 o, V3 d, float& a) {
   q.a4 = 4.0f * a;
   return q;
 }
+// kUnit: the caller's proof that no lane needs the division (unit_dir_query
+// below): the range test, its ballot and the branches on it compile away.
+template <bool kUnit = false>
 RTG_HD void query_rest(RayQ& q, float a) {
   q.den = 2.0f * a;
   q.ap = a * (1.0f - 0x1p-16f);
-  q.fast = (q.den >= 0x1p-60f) && (q.den <= 0x1p60f);
-  q.slow = any_lane(!q.fast);
+  if constexpr (kUnit) {
+    q.fast = true;
+    q.slow = false;
+  } else {
+    q.fast = (q.den >= 0x1p-60f) && (q.den <= 0x1p60f);
+    q.slow = any_lane(!q.fast);
+  }
   // y is used only when q.fast (quot, quot_k<true>); den is then in
   // [2^-60, 2^60], inside rcp_fast's range, so no range check is needed.
   q.y = rcp_fast(q.den);
 }
 
+template <bool kUnit = false>
 RTG_HD RayQ make_query(V3 o, V3 d) {
   float a;
   RayQ q = query_head(o, d, a);
-  query_rest(q, a);
+  query_rest<kUnit>(q, a);
   return q;
 }
 
@@ -651,7 +682,7 @@ template <int Q, class Scene>
 RTG_HD int query_closest(const Scene& sc, V3 o, V3 d, float& t);
 template <int Q, class Scene>
 RTG_HD bool query_blocked(const Scene& sc, V3 o, V3 d, float gap);
-template <class Scene>
+template <bool kUnit = false, class Scene>
 RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, int hit = -1,
                         V3 hc = V3{}, float hr2 = 0.f);
 template <class Scene>
@@ -690,6 +721,51 @@ template <class S, class = void>
 struct IsBvhScene : std::false_type {};
 template <class S>
 struct IsBvhScene<S, std::void_t<decltype(S::kIsBvh)>> : std::bool_constant<S::kIsBvh> {};
+
+// Does the scene type carry the range proofs (DevScene::kRanged)?  Only the
+// masked render kernel's instantiation does, launched for scenes that pass
+// scene_ranged (rtg_scene_pack.h); it compiles out the rare-path guards below
+// that a value-range argument shows can never fire for the renderer's own
+// rays.  Every other scene type, the host's included, keeps every guard.
+// NaN convention of the proofs: a guard may go when the short sequence gives
+// the long one's value bit for bit, or a NaN where the long one gives a NaN:
+// positions matter, payloads and signs of NaNs do not, because no comparison
+// sees them and the frame store canonicalises them (canon_nan).
+//  * refraction's two float square roots: by the expressions' own ranges
+//    (proofs beside them);
+//  * div_d_fresnel's `fast`: scene_ranged bounds every refractive index;
+//  * the shadow and primary queries' q.fast / q.slow: unit_dir_query.
+template <class S, class = void>
+struct IsRangedScene : std::false_type {};
+template <class S>
+struct IsRangedScene<S, std::void_t<decltype(S::kRanged)>> : std::bool_constant<S::kRanged> {};
+
+// unit_dir_query: a query whose direction is d = vsmul(l, v) with
+// l = rcp_sqrt_rn(g), g = vdot(v, v) (vnorm's operations: sample_dir's primary
+// directions, matte_light's light directions) needs no range test of
+// den = 2 d.d.  One of these holds:
+//  (a) g is NaN, or +inf with an infinite v_k (l = 0), or 0 with a zero v_k
+//      (l = +inf): a component of d is NaN and so is den;
+//  (b) g = +inf, every v_k finite: l = 0, d = (+-0, +-0, +-0), den = 0;
+//  (c) g = 0, every v_k non-zero: l = +inf, every d_k infinite, den = +inf;
+//  (d) 0 < g < inf.  With T the exact |v|^2: each square is rounded with
+//      relative error 2^-24 or, below 2^-126, to a multiple of u = 2^-149,
+//      where one rounded to k u >= u is at least k u / 2 and one rounded to 0
+//      at most u / 2; the two sums add a relative 2^-23 at most (sums of
+//      subnormals are exact).  So T / 2.6 <= g <= 2.1 T (g >= u).  l is
+//      within 2^-22 of 1 / sqrt(g) (two correct roundings, no underflow:
+//      sqrt(g) >= 2^-75), so l^2 T is in [0.47, 2.61]; |l v_k| < 2 never
+//      overflows, the largest is above 0.39, and a d_k that underflows adds
+//      less than 2^-125.  The computed d.d is in [0.46, 2.62] and den in
+//      [0.92, 5.24], inside [2^-60, 2^60].
+// For den in {NaN, 0, +inf} the division's quotients are NaN, infinite or
+// zero and the short sequence's are NaN (y = rcp_fast(den) is NaN: v_rcp_f32
+// gives inf or 0 and the residual fma(-den, y, 1) is 0 * inf); the root tests
+// read a quotient only through u > 1e-5f && u < sm, sm <= 10000, which all of
+// these fail alike.  So the short sequence alone gives every lane's answer.
+// (matte_light runs its query only for N.d > 0, which excludes (a) and (b);
+// the primary query meets all four.)  The refraction child's direction
+// D + r N is not of this form: queries that may hold one keep the test.
 
 // raytracer.h:313-367, with the incidence test hoisted ahead of the shadow ray.
 // Q == 4: shadow rays test only the union of the wave's shadow masks
@@ -745,7 +821,8 @@ RTG_HD V3 matte_light(const Scene& sc, V3 P, V3 N, int hit = -1, bool guardOK = 
           const uint64_t su = sc.shadow_union(l, hit, guardOK);
           sc.count(kCntShadowQ, 1);
           sc.count(kCntShadowSel, __builtin_popcountll(su));
-          blk = blocked_sel(sc, P, dir, gap, su, hit, hc, hr2);
+          // (dir is rcp_sqrt_rn(gap) dist and incidence > 0: unit_dir_query)
+          blk = blocked_sel<IsRangedScene<Scene>::value>(sc, P, dir, gap, su, hit, hc, hr2);
         } else {
           // BVH scene: each lane's hit sphere's capsule list for light l, the
           // wave's distinct hit spheres in turn (blocked_cap_lanes); the lanes
@@ -852,6 +929,9 @@ RTG_HD float clamp_cos_sin(float& cosA1) {
   if (cosA1 >= 1.f) { cosA1 = 1.f; return 0.f; }
   return sin_from_cos2(cosA1 * cosA1);
 }
+// kAllFast: the caller's proof that every lane is `fast`, or holds a NaN
+// operand (NaN from either sequence), or discards the quotient.
+template <bool kAllFast = false>
 RTG_HD double div_d_fresnel(double a, double b, bool fast) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double y = __builtin_amdgcn_rcp(b);
@@ -862,9 +942,11 @@ RTG_HD double div_d_fresnel(double a, double b, bool fast) {
   const double q = a * y;
   const double r = fma(-b, q, a);
   double d = fma(r, y, q);
-  if (any_lane(!fast)) {  // wave-uniform test: the rare fallback
-    no_speculate();
-    if (!fast) d = a / b;
+  if constexpr (!kAllFast) {
+    if (any_lane(!fast)) {  // wave-uniform test: the rare fallback
+      no_speculate();
+      if (!fast) d = a / b;
+    }
   }
   return d;
 #else
@@ -875,7 +957,13 @@ RTG_HD double div_d_fresnel(double a, double b, bool fast) {
 
 // raytracer.h:370-403 (f64 island).  kCL: the OpenCL kernel's all-float
 // version, raytrace_kernel.cl:399-432.
-template <bool kCL = false>
+// kRanged: n1 and n2 are indices of a scene that passed scene_ranged
+// (|n| <= 2^100) and the cosines are refraction's: cosA1 clamped to [-1, 1]
+// or NaN, cosA2 = +-sqrt(1 - sinA2^2) in [0, 1] in magnitude or NaN.  A
+// product of such a pair is at most 2^100 in magnitude (rounding is monotone)
+// or NaN, so every lane is `fast` or carries a NaN into num and den both,
+// where the short sequence gives NaN as the division does: no `fast` test.
+template <bool kCL = false, bool kRanged = false>
 RTG_HD float polarised_reflection(float n1, float n2, float cosA1, float cosA2) {
   const float left = n1 * cosA1;
   const float right = n2 * cosA2;
@@ -896,7 +984,7 @@ RTG_HD float polarised_reflection(float n1, float n2, float cosA1, float cosA2) 
   // a divergent early return)
   const bool tiny = den < (double)1.0e-6f;
   const bool fast = fabsf(left) <= 0x1p100f && fabsf(right) <= 0x1p100f;
-  float refl = (float)div_d_fresnel(num * num, den, fast || tiny);
+  float refl = (float)div_d_fresnel<kRanged>(num * num, den, fast || tiny);
   if (refl > 1.f) refl = 1.f;
   return tiny ? 1.f : refl;
 }
@@ -921,6 +1009,7 @@ struct HasPairTable<S, std::void_t<decltype(std::declval<const S&>().pair(
 template <bool kCL = false, class Scene>
 RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRay,
                       V3& dirOut, float& R, int hit = -1, bool guardOK = false, int rm = -1) {
+  constexpr bool kRanged = IsRangedScene<Scene>::value;
   float cosA1 = vdot(D, N);
   const float sinA1 = clamp_cos_sin(cosA1);
 
@@ -972,7 +1061,12 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
       r1 = 0.f;
       ns = 1;
     } else {
-      const float root = rtg_sqrtf(rad);
+      // Ranged: a lane here has !(|rad| < 0.001f), so rad >= 0.001 (inside
+      // sqrt_fast_range), or rad <= -0.001 or NaN (NaN from v_sqrt_f32 and
+      // through both residuals, as from sqrtf), or +inf (s = inf, its
+      // neighbours FLT_MAX and a NaN, both residuals NaN, both selects keep
+      // inf = sqrtf(inf)).  The other lanes discard the value.
+      const float root = sqrt_sel<kRanged>(rad);
       const float den = 2.0f * 1.f;
       r0 = (-qb + root) / den;
       r1 = (-qb - root) / den;
@@ -992,10 +1086,15 @@ RTG_HD int refraction(const Scene& sc, V3 D, V3 P, V3 N, float nSrc, bool wantRa
     }
     dirOut = dir;
   }
-  float cosA2 = rtg_sqrtf(1.f - (sinA2 * sinA2));
+  // Ranged: fl(sinA2^2) is >= 0, +inf or NaN, so the operand fl(1 - fl(s^2))
+  // is 0 exactly, or in [2^-24, 1] (inside sqrt_fast_range), or negative,
+  // -inf or NaN.  sqrt_fast_signed gives sqrtf's result on all of these: at
+  // 0, s = 0, one neighbour is a NaN and the other's residual is 0, so both
+  // selects keep +0; a negative or NaN operand gives NaN as sqrtf does.
+  float cosA2 = sqrt_sel<kRanged>(1.f - (sinA2 * sinA2));
   if (cosA1 < 0.f) cosA2 = -cosA2;
-  const float Rs = polarised_reflection<kCL>(nSrc, nTgt, cosA1, cosA2);
-  const float Rp = polarised_reflection<kCL>(nSrc, nTgt, cosA2, cosA1);
+  const float Rs = polarised_reflection<kCL, kRanged>(nSrc, nTgt, cosA1, cosA2);
+  const float Rp = polarised_reflection<kCL, kRanged>(nSrc, nTgt, cosA2, cosA1);
   // (float)((double)(Rs + Rp) * 0.5) (raytracer.h:801): the f64 product is
   // exact, so its rounding to float is the float product's.
   R = (Rs + Rp) * 0.5f;
@@ -2181,7 +2280,9 @@ RTG_HD bool blocked_sel_fused(const Scene& sc, const RayQ& q, float gap, uint64_
   return blkv != 0u;
 }
 
-template <class Scene>
+// kUnit: d is a unit_dir_query direction, so the fused form runs its kFast
+// instantiation with no range test (the unfused form keeps its own).
+template <bool kUnit, class Scene>
 RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, int hit,
                         V3 hc, float hr2) {
   float a;
@@ -2210,7 +2311,8 @@ RTG_HD bool blocked_sel(const Scene& sc, V3 o, V3 d, float gap, uint64_t sel, in
       return false;
     }
     sc.count(kUQuery, 1);
-    query_rest(q, a);
+    query_rest<kUnit>(q, a);
+    if constexpr (kUnit) return blocked_sel_fused<true>(sc, q, gap, sel, skip);
     if (sc.all(q.fast)) return blocked_sel_fused<true>(sc, q, gap, sel, skip);
     return blocked_sel_fused<false>(sc, q, gap, sel, skip);
   }
@@ -2462,12 +2564,15 @@ RTG_HD int closest_hit_sel_fused(const Scene& sc, const RayQ& q, uint64_t sel, f
 template <class Scene>
 RTG_HD int closest_hit_sel(const Scene& sc, V3 o, V3 d, float& tOut, uint64_t sel) {
   sc.count(kUQuery, 1);
-  const RayQ q = make_query(o, d);
+  // (a scene with the range proofs: d is sample_dir's, unit_dir_query)
+  constexpr bool kUnit = IsRangedScene<Scene>::value;
+  const RayQ q = make_query<kUnit>(o, d);
   // The primary ray starts at the origin (main.cpp:417): disp = 0 - c = -c
   // exactly, so b = 2 d.disp = -(2 d.c) and b*b is (2 d.c)^2; the c term
   // |disp|^2 - r^2 is precomputed per sphere (origin_c).  Same radicand bits.
   (void)o;
   if (sc.fuse & kFusePrim) {
+    if constexpr (kUnit) return closest_hit_sel_fused<true>(sc, q, sel, tOut);
     if (sc.all(q.fast)) return closest_hit_sel_fused<true>(sc, q, sel, tOut);
     return closest_hit_sel_fused<false>(sc, q, sel, tOut);
   }

@@ -87,11 +87,18 @@ struct LdsFramesTop {
 // wave-level execution, on the wave's first active lane; flush_counts() adds
 // the wave's sums to KernelArgs::counts.  Control flow is the default
 // kernel's, so the counts are the default kernel's executed work.
+// kRanged_ (with kMasks, the default kernel's compacted launch only): the scene
+// passed scene_ranged (rtg_scene_pack.h) and the primary directions are
+// sample_dir's, so the rare-path guards that IsRangedScene (rtg_trace.h) lists
+// compile away.  A masked scene that fails the proof runs the compacted kernel
+// without kMasks, with every guard (trace_fn_v).
 template <bool kDiag = false, int kThreads = kBlock, bool kBvh = false, int kFuse = 0,
-          bool kMasks = false, bool kCount = false>
+          bool kMasks = false, bool kCount = false, bool kRanged_ = false>
 struct DevScene {
   static constexpr int fuse = kFuse;
   static constexpr bool kIsBvh = kBvh;
+  static constexpr bool kRanged = kRanged_;
+  static_assert(!kRanged_ || (kMasks && !kBvh), "range proofs: the masked kernel only");
   FrameC* lfr;
   __device__ __forceinline__ bool all(bool b) const { return __ballot(!b) == 0ull; }
   __device__ __forceinline__ bool any(bool b) const { return __ballot(b) != 0ull; }
@@ -996,13 +1003,14 @@ struct IsDiag {
 // kMasks (compacted default kernel only): the launcher guarantees the
 // scene's shadow/overlap and cone masks (DevScene).
 // The body of the sample kernels (one per launch kind below).
-template <int S, int kVariant, bool kBvh, bool kList, bool kMasks>
+// kRanged (with kMasks): the scene passed scene_ranged too (DevScene).
+template <int S, int kVariant, bool kBvh, bool kList, bool kMasks, bool kRanged = false>
 __device__ __forceinline__ void trace_samples_body(const KernelArgs& a) {
   constexpr int kThreads = 64;
   constexpr bool kCount = IsCount<kVariant>::value;
   // every sample kernel runs the fused query forms
   constexpr int kFuse = kFusePrim | kFuseCone | kFuseShadow | kFuseEnter;
-  DevScene<IsDiag<kVariant>::value, kThreads, kBvh, kFuse, kMasks, kCount> sc;
+  DevScene<IsDiag<kVariant>::value, kThreads, kBvh, kFuse, kMasks, kCount, kRanged> sc;
   sc.count_reset();
   sc.count(kUWave, 1);  // every wave, those past the listed groups included
   const unsigned t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
@@ -1081,10 +1089,11 @@ __device__ __forceinline__ void trace_samples_body(const KernelArgs& a) {
   else record_wave(a, t0, gw);
 }
 
-template <int S, int kVariant, bool kBvh = false, bool kList = false, bool kMasks = false>
+template <int S, int kVariant, bool kBvh = false, bool kList = false, bool kMasks = false,
+          bool kRanged = false>
 __global__ __launch_bounds__(64, (MinWaves<S, kVariant, kBvh>::value))
 void trace_samples_kernel(const KernelArgs a) {
-  trace_samples_body<S, kVariant, kBvh, kList, kMasks>(a);
+  trace_samples_body<S, kVariant, kBvh, kList, kMasks, kRanged>(a);
 }
 
 // The compacted default kernel of a masked scene with an SGPR budget
@@ -1095,13 +1104,14 @@ void trace_samples_kernel(const KernelArgs a) {
 // extra SGPR spills to VGPR lanes cost less than the eighth wave gains
 // (A/B C3 1.755 vs 1.780 ms, C4 11.05 vs 11.35; resident waves per SIMD mean
 // 7.1, peak 7.8, vs 6.4 / 6.8).  Instantiated for S <= 6 (trace_fn_v).
+// Its scenes passed scene_ranged as well (kRanged, DevScene).
 #ifndef RTG_NUM_SGPR
 #define RTG_NUM_SGPR 78
 #endif
 template <int S>
 __global__ __launch_bounds__(64, 8) __attribute__((amdgpu_num_sgpr(RTG_NUM_SGPR)))
 void trace_samples_kernel_masked(const KernelArgs a) {
-  trace_samples_body<S, 0, false, true, true>(a);
+  trace_samples_body<S, 0, false, true, true, true>(a);
 }
 
 // Kernel variants (rtg_launch_opts.variant; results identical, speed differs):
@@ -1145,7 +1155,10 @@ inline const VariantInfo* variant_info(int v) {
 }
 
 // list: 0 the direct launch, 1 the compacted launch, 2 the compacted launch
-// of a scene with masks (kMasks instantiation of the default kernel).  Only
+// of a scene with masks, 3 of a scene with masks that passed scene_ranged
+// (kMasks and kRanged instantiation of the default kernel; a masked scene
+// that fails the proof runs the compacted kernel, which reads the masks
+// through run-time flags and keeps every guard: the same frame).  Only
 // the sample kernels 0, 50, 110 and 120 have compacted forms; a list request
 // for any other variant gets nullptr, an error, never a wrong frame.
 template <int S, int V>
@@ -1153,13 +1166,15 @@ static TraceFn trace_fn_v(int list) {
   if constexpr (V == 0) {
     // S <= 6: the SGPR-budgeted 8-wave kernel; deeper stacks hold more LDS
     // per wave than 8 waves per SIMD admit anyway
-    if (list == 2) {
+    if (list == 3) {
       if constexpr (S <= 6) return trace_samples_kernel_masked<S>;
-      else return trace_samples_kernel<S, 0, false, true, true>;
+      else return trace_samples_kernel<S, 0, false, true, true, true>;
     }
     return list ? trace_samples_kernel<S, 0, false, true> : trace_samples_kernel<S, 0>;
-  } else if constexpr (V == 120) {  // the counting build of exactly the masked kernel
-    return list == 2 ? trace_samples_kernel<S, 120, false, true, true> : nullptr;
+  } else if constexpr (V == 120) {
+    // the counting build of the masked kernel, with every guard: the units it
+    // counts are the same with and without them
+    return list >= 2 ? trace_samples_kernel<S, 120, false, true, true> : nullptr;
   } else if constexpr (V == 110) {  // the probe build of the compacted default kernel
     return list ? trace_samples_kernel<S, 110, false, true> : nullptr;
   } else if constexpr (V == 50) {

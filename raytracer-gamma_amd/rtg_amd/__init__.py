@@ -91,7 +91,7 @@ EXPORTED = [
     "rtg_shard_rows", "rtg_shard_global_row", "rtg_render_device", "rtg_render_rows_device",
     "rtg_render_rows", "rtg_set_launch_opts", "rtg_diag_read", "rtg_diag_timeline", "rtg_diag_counts",
     "rtg_diag_group_list",
-    "rtg_context_scene_stats",
+    "rtg_context_scene_stats", "rtg_scene_ranged",
     "rtg_max_colour", "rtg_max_colour_device", "rtg_ppm_bytes", "rtg_ppm_bytes_device",
     "rtg_save_ppm", "rtg_make_material", "rtg_scene_generate", "rtg_assemble_shards_device",
     "rtg_render_multi", "rtg_scene_load", "rtg_scene_save", "rtg_context_set_semantics",
@@ -178,6 +178,7 @@ def lib() -> ctypes.CDLL:
         for name, at in (("rtg_diag_counts", [vp, vp, i, i]),
                          ("rtg_context_scene_stats", [vp, vp]),
                          ("rtg_multi_set_gather", [vp, i]),
+                         ("rtg_scene_ranged", [vp, u, ctypes.POINTER(i)]),
                          ("rtg_place_shard_device", [vp, vp, u, u, u, u, u, vp, vp])):
             try:
                 getattr(L, name).argtypes = at
@@ -428,6 +429,16 @@ def render_multi(spheres, lights, width: int, height: int, devices=(0,), zoom: f
                                   float(alias_factor), stack_size, row_block, _ptr(out),
                                   _ptr(tm)), "rtg_render_multi")
     return out, [float(v) for v in tm]
+
+
+def scene_ranged(spheres) -> bool:
+    """Whether the scene passes the value-range proof of the masked render
+    kernel's guard-free build (rtg_scene_ranged; host only, no GPU needed)."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    out = ctypes.c_int(-1)
+    _check(lib().rtg_scene_ranged(_ptr(spheres), len(spheres), ctypes.byref(out)),
+           "rtg_scene_ranged")
+    return bool(out.value)
 
 
 def gbuffer(spheres, width: int, height: int, zoom: float = -4.0, alias_factor: float = 3.0,

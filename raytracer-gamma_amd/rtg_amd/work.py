@@ -124,7 +124,9 @@ UNIT_COST = {
 FIT_RECORD = "profiles/r06/calib_units/fit.json"
 UNIT_COST_SOURCE = dict(UNIT_COST)
 UNIT_COST.update({
-    "U.query": 19.97,
+    # (after the fit the masked kernel lost the range test of its shadow and
+    # primary queries, about two thirds of its queries: the fitted 19.97 less 2)
+    "U.query": 17.97,
     "U.primIter": 11.58,
     "U.primExact": 48.38,
     "U.selIter": 11.43,
@@ -157,9 +159,14 @@ UNIT_COST.update({
     # f64 instruction once, so the fitted 216.57 and 270.71 lose the INSTRUCTION
     # deltas of the gfx950 listing by hand: sinA1 18 -> 14, the division 11 -> 2
     # for the record's address, and with the refracted ray 1 - rcp_rn's 7:
-    # -20 and -13)
-    "U.refr": 196.57,
-    "U.refrLeaf": 257.71,
+    # -20 and -13; and then the masked kernel's guards of the two float square
+    # roots (less the compare and select of sqrt_fast_signed) and of the two
+    # Fresnel quotients: -4 and -4.  With U.query's -2 these are the 11.2 M
+    # instructions per C3 frame that SQ_INSTS_VALU lost, 1054.5 -> 1043.3 M,
+    # profiles/ranged_guards; the BVH kernels keep the guards and are priced a
+    # little low by it)
+    "U.refr": 192.57,
+    "U.refrLeaf": 253.71,
     "U.push": 50.08,
     "U.descend": 27.69,
     "U.unwind": 11.92,
