@@ -38,6 +38,8 @@
  *     caller's loop over rayTrace in the reference)       rtg_gather_rays[_device|_host]
  *   (a frame of those per-pixel signals smoothed along   rtg_filter[_device|_host],
  *     its surfaces, guided by the frame's hit records)    rtg_filter_scratch
+ *   (such a signal carried from frame to frame while     rtg_accumulate[_device|_host],
+ *     the camera moves: reprojection by the hit points)   rtg_camera_project[_device|_host]
  *   primaryContainer for a caller's own points         rtg_contains[_device|_host]
  *     raytracer.h:245-270
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
@@ -528,6 +530,39 @@ int rtg_camera_rays_host(const rtg_camera* cam, unsigned width, unsigned height,
 int rtg_camera_rays_device(rtg_context* ctx, const rtg_camera* cam, unsigned width,
                            unsigned height, float zoom, float aliasFactor, rtg_ray* raysDevice,
                            void* stream);
+/* The generator's inverse: where in the pose's W x H frame a point P lies.
+ * All in float with no contraction and in this operand order, dot(a, b) =
+ * (a.x * b.x + a.y * b.y) + a.z * b.z:
+ *
+ *   e.q = P.q - eye.q
+ *   a = dot(e, right);  b = dot(e, up);  d = dot(e, back)
+ *   k = zoom / d                       (the correctly rounded quotient)
+ *   rx = a * k;  ry = b * k
+ *   fx = rx * kx + halfW               kx = (float)W * 0.046875f  (= 1 / (xs * asp))
+ *   fy = halfH - ry * ky               ky = (float)H / 12.f
+ *                                      halfW = W * 0.5f, halfH = H * 0.5f
+ *
+ * out[i] = {fx, fy, k} as computed, NaN words stored as 0xFFC00000.  P lies in
+ * front of the camera exactly when k > 0.f; the caller tests it.  Integer fx,
+ * fy are the positions of the aa-1 sample rays of rtg_camera_rays*: the point
+ * rtg_intersect* finds on the ray of pixel (x, y) projects to (x, y) up to
+ * rounding.  This is the generator's inverse only for an orthonormal basis,
+ * which is what rtg_camera_look_at builds; any other basis gives what the
+ * arithmetic gives.  NaN and infinite inputs and d == 0 follow the arithmetic.
+ *
+ * n == 0 writes nothing and is RTG_OK.  RTG_ERR_INVALID with a message, before
+ * any GPU call, for a null pointer, an empty frame, W or H above 2^24 (their
+ * floats are then exact) or a batch of more than 2^31-1 workgroups (device).
+ * The device form is asynchronous on `stream`, takes points in device memory
+ * and needs no scene; the pose is host memory, read before return. */
+int rtg_camera_project_host(const rtg_camera* cam, unsigned width, unsigned height, float zoom,
+                            const rtg_vec* points, size_t n, rtg_vec* outHost, int nthreads);
+int rtg_camera_project_device(rtg_context* ctx, const rtg_camera* cam, unsigned width,
+                              unsigned height, float zoom, const rtg_vec* pointsDevice, size_t n,
+                              rtg_vec* outDevice, void* stream);
+/* One-shot: uploads the points, runs on `device`, downloads n records. */
+int rtg_camera_project(int device, const rtg_camera* cam, unsigned width, unsigned height,
+                       float zoom, const rtg_vec* points, size_t n, rtg_vec* outHost);
 /* Fused render of the pose's whole W x H frame (row major) into device memory
  * on `stream`, asynchronously: no ray buffer, no colour buffer, no fold on the
  * caller's side.  Follows rtg_context_set_semantics; rtg_set_launch_opts does
@@ -1070,9 +1105,9 @@ int rtg_gather_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light*
  * overlapping src's or the scratch's (addresses compared as numbers, on the
  * host and on the device alike).
  *
- * Out of scope: a value- or variance-driven term (SVGF), temporal
- * accumulation, rtg_gbuf_px records as guides, per-pass parameters, filtering
- * ray batches that are not a frame, views and multi-GPU. */
+ * Out of scope: a value- or variance-driven term (SVGF), rtg_gbuf_px records
+ * as guides, per-pass parameters, filtering ray batches that are not a frame,
+ * views and multi-GPU. */
 #define RTG_FILTER_MAX_PASSES 8
 #define RTG_FILTER_RGB   0           /* kind: src and dst are rtg_vec */
 #define RTG_FILTER_GRAY  1           /* kind: src and dst are float */
@@ -1103,6 +1138,120 @@ int rtg_filter_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned widt
  * `device`, downloads n values. */
 int rtg_filter(int device, const rtg_hit* hits, unsigned width, unsigned height,
                const rtg_filter_params* params, const void* src, void* dstHost);
+
+/* ---- accumulate: temporal accumulation by reprojection ----
+ * rtg_ao* and rtg_gather* give a different probe set per frame under their
+ * JITTER flags and a seed; rtg_filter* smooths one frame in space.  These calls
+ * are the time half: they carry a per-pixel running mean from frame to frame
+ * while the camera moves.  Scenes are static, so the world-space hit point of
+ * a pixel is the exact key into the previous frame: it is projected into the
+ * previous pose (rtg_camera_project*'s arithmetic) and the previous state is
+ * fetched there with four validated bilinear taps.  Float arithmetic that is
+ * defined here: the same words on the host and on every GPU.
+ *
+ * INPUTS.  A W x H frame, row-major, n = W * H pixels.  `hits`: the current
+ * pose's aa-1 rtg_hit records, read as rtg_filter* reads them (id for its sign
+ * and for equality, point and normal as given, t not read).  `src`: the current
+ * signal, one of rtg_filter*'s kinds (RTG_FILTER_RGB rtg_vec, RTG_FILTER_GRAY
+ * float, RTG_FILTER_COUNT unsigned short with value (float)c); C = 3 channels
+ * for RGB, else 1.  The previous frame's state: `prevHits` (its records),
+ * `prevAcc` (n * C floats, its outAcc), `prevLen` (n unsigned short, its
+ * outLen, the history length), optionally `prevM2` (n * C floats, its outM2),
+ * and the previous pose `prevCam` with the frame's `zoom`.  Outputs: outAcc
+ * (n * C floats), outLen (n unsigned short) and optionally outM2 (n * C
+ * floats), a running mean of the squared signal.
+ * prevHits, prevAcc and prevLen are all null or all non-null.  All null is a
+ * RESET FRAME: no pixel finds history, prevCam and prevM2 are not read and
+ * may be null.  Otherwise prevM2 follows outM2: both null or both non-null.
+ *
+ * PER PIXEL p = (x, y), all in float with no contraction and in this operand
+ * order, dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z, q over the channels:
+ *   cur.q = src[p].q (converted);  cur2.q = cur.q * cur.q
+ *   id_p < 0:  outAcc[p] = cur, outM2[p] = cur2, outLen[p] = 0; nothing else.
+ *   LOOKUP.  {fx, fy, k} = rtg_camera_project's of P_p under prevCam, W, H,
+ *     zoom.  There is no history on a reset frame, or when !(k > 0.f), or when
+ *     !(fx > -1.f && fx < (float)W && fy > -1.f && fy < (float)H).  Otherwise
+ *     x0 = floorf(fx), tx = fx - x0, y0 = floorf(fy), ty = fy - y0 (x0, y0
+ *     then convert to int exactly); sum.q = s2.q = sw = +0.f, nmin = 65535;
+ *     taps dy = 0, 1 (outer), dx = 0, 1 (inner): q = (x0 + dx, y0 + dy),
+ *     wx = dx ? tx : 1.f - tx, wy = dy ? ty : 1.f - ty, w = wy * wx.  The tap
+ *     is left out when q is outside the frame, or prevId_q < 0, or
+ *     prevLen_q == 0, or RTG_ACCUM_SAME_ID is set and prevId_q != id_p, or
+ *     RTG_ACCUM_SKIP_NONFINITE is set and any word of prevAcc[q] has an
+ *     all-ones exponent field.  Then rtg_filter*'s two terms, verbatim:
+ *       RTG_ACCUM_NORMAL:  c = dot(N_p, prevN_q);  c = c > 0.f ? c : 0.f;
+ *                          normalLog2 times c = c * c;  w = w * c
+ *       RTG_ACCUM_PLANE:   e = prevP_q - P_p per component;
+ *                          d = fabsf(dot(N_p, e));  z = 1.f - d * planeScale;
+ *                          z = z > 0.f ? z : 0.f;  w = w * z
+ *     and the tap is left out when !(w > 0.f).  An accepted tap gives
+ *       sum.q = sum.q + w * prevAcc[q].q;  s2.q = s2.q + w * prevM2[q].q;
+ *       sw = sw + w;  nmin = min(nmin, prevLen_q)
+ *     The lookup is FOUND when sw > 0.f; then hist.q = sum.q / sw and
+ *     hist2.q = s2.q / sw, the correctly rounded quotients.
+ *   BLEND.  curOK is false only when RTG_ACCUM_SKIP_NONFINITE is set and a
+ *     word of cur has an all-ones exponent field.
+ *       found,  curOK:  n = min(nmin + 1, maxHistory), alpha = 1.f / (float)n,
+ *                       outAcc.q = hist.q + alpha * (cur.q - hist.q), outLen = n
+ *       found, !curOK:  outAcc.q = hist.q, outLen = nmin
+ *       !found, curOK:  outAcc.q = cur.q,  outLen = 1
+ *       !found, !curOK: outAcc.q = cur.q,  outLen = 0
+ *     outM2 follows outAcc's pattern with cur2 and hist2.
+ * NaN words are stored as 0xFFC00000.  NaN poses, points and normals follow
+ * the comparisons as written.  With maxHistory = 65535 outAcc is the running
+ * mean of the pixel's surface point over the frames it was seen in; a smaller
+ * maxHistory is an exponential average with alpha >= 1 / maxHistory.
+ *
+ * rtg_accumulate_host restates this in plain loops: the yardstick.
+ * rtg_accumulate_device is one kernel launch, asynchronous on `stream`; it
+ * allocates nothing, needs no scratch and no scene, takes none of the
+ * context's render scratch and may be mixed with every other call on the
+ * context.  `params` and `prevCam` are host memory, read before return.
+ *
+ * RTG_ERR_INVALID with a message, before any GPU call, for a null hits, src,
+ * params, outAcc or outLen, a partly null prev set, a null prevCam with a prev
+ * set, outM2 without prevM2 with a prev set or prevM2 without outM2, W or H
+ * equal to 0 or above 2^24, normalLog2 above 8, an unknown kind or flag,
+ * maxHistory 0 or above 65535, hits or prevHits off 16-byte alignment
+ * (device), a grid above 2^31 - 1 workgroups (device), and any output's byte
+ * range overlapping any input's or another output's: the kernel gathers from
+ * the previous state, so in-place use is a race (addresses compared as
+ * numbers, on the host and on the device alike).
+ *
+ * Out of scope: moving spheres and motion vectors, a variance-guided filter
+ * term, per-pixel alpha clamps, views and multi-GPU. */
+#define RTG_ACCUM_SAME_ID 1         /* a tap of another id is left out */
+#define RTG_ACCUM_NORMAL 2          /* the normal term */
+#define RTG_ACCUM_PLANE 4           /* the plane-distance term */
+#define RTG_ACCUM_SKIP_NONFINITE 8  /* non-finite history taps and current values are left out */
+typedef struct rtg_accumulate_params { /* 20 B */
+  unsigned kind;        /* RTG_FILTER_RGB / GRAY / COUNT */
+  unsigned flags;       /* RTG_ACCUM_* bits; an unknown bit is RTG_ERR_INVALID */
+  unsigned normalLog2;  /* 0..8 */
+  float planeScale;     /* used as given */
+  unsigned maxHistory;  /* 1..65535: outLen's cap */
+} rtg_accumulate_params;
+/* Plain loops; the result does not depend on nthreads (threads take bands of
+ * rows).  nthreads <= 0: 1. */
+int rtg_accumulate_host(const rtg_hit* hits, unsigned width, unsigned height,
+                        const rtg_accumulate_params* params, const void* src,
+                        const rtg_camera* prevCam, float zoom, const rtg_hit* prevHits,
+                        const float* prevAcc, const unsigned short* prevLen, const float* prevM2,
+                        float* outAcc, unsigned short* outLen, float* outM2, int nthreads);
+int rtg_accumulate_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned width,
+                          unsigned height, const rtg_accumulate_params* params,
+                          const void* srcDevice, const rtg_camera* prevCam, float zoom,
+                          const rtg_hit* prevHitsDevice, const float* prevAccDevice,
+                          const unsigned short* prevLenDevice, const float* prevM2Device,
+                          float* outAccDevice, unsigned short* outLenDevice, float* outM2Device,
+                          void* stream);
+/* One-shot: uploads the inputs (host memory), runs on `device`, downloads the
+ * outputs. */
+int rtg_accumulate(int device, const rtg_hit* hits, unsigned width, unsigned height,
+                   const rtg_accumulate_params* params, const void* src,
+                   const rtg_camera* prevCam, float zoom, const rtg_hit* prevHits,
+                   const float* prevAcc, const unsigned short* prevLen, const float* prevM2,
+                   float* outAcc, unsigned short* outLen, float* outM2);
 
 /* ---- containment: primaryContainer per point ----
  * "Which medium is this point in": out[i] is the lowest sphere index s for

@@ -40,4 +40,32 @@ RTG_HD V3 camera_dir(const Camera& cam, const CamPose& p, unsigned x, unsigned y
   return vnorm(v);
 }
 
+// The frame constants of rtg_camera_project* (rtg.h): W, H <= 2^24, so their
+// floats are exact; halfW, halfH as make_camera computes them.
+struct ProjFrame {
+  float zoom, kx, ky, halfW, halfH;
+};
+
+RTG_HD ProjFrame proj_frame(unsigned W, unsigned H, float zoom) {
+  ProjFrame f;
+  f.zoom = zoom;
+  f.kx = (float)W * 0.046875f;  // 1 / (xs * asp)
+  f.ky = (float)H / 12.f;
+  f.halfW = W * 0.5f;
+  f.halfH = H * 0.5f;
+  return f;
+}
+
+// camera_dir's inverse for an orthonormal basis (rtg.h has the arithmetic):
+// {fx, fy, k} of point P; P lies in front of the camera exactly when k > 0.f.
+// ONE function for rtg_camera_project*'s kernel and host loops and for the
+// lookup of rtg_accumulate* (rtg_accumulate.h).
+RTG_HD V3 camera_project(const ProjFrame& f, const CamPose& c, V3 P) {
+  const V3 e = vsub(P, c.eye);
+  const float a = vdot(e, c.right), b = vdot(e, c.up), d = vdot(e, c.back);
+  const float k = f.zoom / d;
+  const float rx = a * k, ry = b * k;
+  return v3(rx * f.kx + f.halfW, f.halfH - ry * f.ky, k);
+}
+
 }  // namespace rtg

@@ -29,6 +29,9 @@
 // of the pixel store, then rtg_fold.hip's stage 2; no frame is written.
 // rtg_cube_sh_weights builds the SH table for rtg_camera_cube's faces.
 //
+// The generator's inverse (rtg_camera_project*, camera_project of rtg_camera.h):
+// a point's frame position {fx, fy} and k under a pose, one lane per point.
+//
 // This file holds the pose helpers, the generator (kernel and host form), the
 // launchers of the fused kernels (picked from stack_kernels, rtg_trace_kernels.h),
 // the pose's own argument checks (the rest are rtg_entry.h's) and the host
@@ -82,6 +85,26 @@ __global__ __launch_bounds__(64) void camera_rays_kernel(const Camera cam, const
   camera_ray(cam, pose, W, k, reinterpret_cast<float*>(rays + k));  // k < n: 24 B of the batch
 }
 
+// Point k of the batch under the pose: {fx, fy, k} as three words, NaN as the
+// records' NaN.
+RTG_HD void camera_project_words(const ProjFrame& f, const CamPose& p, const float* pt,
+                                 unsigned* w) {
+  const V3 r = camera_project(f, p, v3(pt[0], pt[1], pt[2]));
+  w[0] = nan_bits(r.x); w[1] = nan_bits(r.y); w[2] = nan_bits(r.z);
+}
+
+// One lane per point, 12 B in and out; n > 0.
+__global__ __launch_bounds__(64) void camera_project_kernel(const ProjFrame f, const CamPose pose,
+                                                            size_t n,
+                                                            const float* __restrict__ points,
+                                                            unsigned* __restrict__ out) {
+  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (k >= n) return;
+  unsigned w[3];
+  camera_project_words(f, pose, points + 3 * k, w);  // k < n: 12 B of each batch
+  out[3 * k] = w[0]; out[3 * k + 1] = w[1]; out[3 * k + 2] = w[2];
+}
+
 // ---- host forms of the render ----
 
 // Pixels [k0, k1) of the frame; kWalk 1: the kernel's path, else plain loops.
@@ -127,6 +150,24 @@ static int check_frame(const char* what, const rtg_camera* cam, const void* dst,
     return RTG_ERR_INVALID;
   }
   return make_camera(W, H, zoom, aa, out);
+}
+
+// rtg_camera_project*'s arguments, in the order they are reported in.
+static int check_project(const rtg_camera* cam, unsigned W, unsigned H, const void* points,
+                         size_t n, const void* dst) {
+  if (!cam || (n && (!points || !dst))) {
+    rtg_set_error("camera_project: null %s", !cam ? "camera" : !points ? "points" : "destination");
+    return RTG_ERR_INVALID;
+  }
+  if (W == 0 || H == 0) {
+    rtg_set_error("camera_project: empty frame %ux%u", W, H);
+    return RTG_ERR_INVALID;
+  }
+  if (W > (1u << 24) || H > (1u << 24)) {
+    rtg_set_error("camera_project: frame %ux%u (at most 2^24 each way)", W, H);
+    return RTG_ERR_INVALID;
+  }
+  return RTG_OK;
 }
 
 // Workgroups of the fused kernel for a W x H frame; 0 when more than 2^31-1.
@@ -279,6 +320,81 @@ int rtg_camera_rays_device(rtg_context* ctx, const rtg_camera* cam, unsigned wid
                      cam_pose(*cam), width, n, raysDevice);
   HIP_TRY(hipGetLastError());
   return RTG_OK;
+}
+
+int rtg_camera_project_host(const rtg_camera* cam, unsigned width, unsigned height, float zoom,
+                            const rtg_vec* points, size_t n, rtg_vec* outHost, int nthreads) {
+  rtg_clear_error();
+  const int rc = check_project(cam, width, height, points, n, outHost);
+  if (rc || n == 0) return rc;
+  const ProjFrame f = proj_frame(width, height, zoom);
+  const CamPose pose = cam_pose(*cam);
+  host_bands(n, nthreads, [&](size_t k0, size_t k1) {
+    for (size_t k = k0; k < k1; ++k) {
+      unsigned w[3];
+      camera_project_words(f, pose, &points[k].x, w);
+      memcpy(outHost + k, w, sizeof w);
+    }
+  });
+  return RTG_OK;
+}
+
+int rtg_camera_project_device(rtg_context* ctx, const rtg_camera* cam, unsigned width,
+                              unsigned height, float zoom, const rtg_vec* pointsDevice, size_t n,
+                              rtg_vec* outDevice, void* stream) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  int device = 0;
+  if (!rtg_context_device(ctx, &device)) {
+    rtg_set_error("camera_project: no context");
+    return RTG_ERR_INVALID;
+  }
+  int rc = check_project(cam, width, height, pointsDevice, n, outDevice);
+  if (rc || n == 0) return rc;
+  unsigned blocks;
+  rc = ray_blocks("camera_project", "batch", n, &blocks);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(camera_project_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream,
+                     proj_frame(width, height, zoom), cam_pose(*cam), n,
+                     reinterpret_cast<const float*>(pointsDevice),
+                     reinterpret_cast<unsigned*>(outDevice));
+  HIP_TRY(hipGetLastError());
+  return RTG_OK;
+}
+
+int rtg_camera_project(int device, const rtg_camera* cam, unsigned width, unsigned height,
+                       float zoom, const rtg_vec* points, size_t n, rtg_vec* outHost) {
+  DeviceGuard deviceGuard;  // the caller's current device is restored on return
+  rtg_clear_error();
+  int rc = check_project(cam, width, height, points, n, outHost);
+  if (rc || n == 0) return rc;
+  rtg_context* ctx = nullptr;
+  rc = rtg_context_create(device, &ctx);
+  if (rc) return rc;
+  const size_t bytes = n * sizeof(rtg_vec);
+  unsigned char* d = nullptr;  // the points, then the results
+  if (hipSetDevice(device) != hipSuccess || hipMalloc(&d, 2 * bytes) != hipSuccess) {
+    rtg_set_error("camera_project: hipMalloc(%zu) failed", 2 * bytes);
+    rc = RTG_ERR_NOMEM;
+  }
+  if (!rc && hipMemcpy(d, points, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    rtg_set_error("camera_project: upload of %zu bytes failed", bytes);
+    rc = RTG_ERR_HIP;
+  }
+  if (!rc)
+    rc = rtg_camera_project_device(ctx, cam, width, height, zoom, (const rtg_vec*)d, n,
+                                   (rtg_vec*)(d + bytes), nullptr);
+  if (!rc) {
+    const hipError_t e = hipMemcpy(outHost, d + bytes, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+      rtg_set_error("camera_project: kernel/readback failed: %s", hipGetErrorString(e));
+      rc = RTG_ERR_HIP;
+    }
+  }
+  (void)hipFree(d);
+  rtg_context_destroy(ctx);
+  return rc;
 }
 
 int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,

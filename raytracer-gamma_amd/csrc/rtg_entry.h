@@ -1,5 +1,6 @@
 // rtg_entry.h — what the C ABI entry points of librtg.so share (rtg_kernel.hip,
-// rtg_gbuffer.hip, rtg_rays.hip, rtg_raytrace.hip, rtg_order.hip, rtg_camera.hip, rtg_ao.hip, rtg_matte.hip, rtg_gather.hip, rtg_filter.hip): the HIP error
+// rtg_gbuffer.hip, rtg_rays.hip, rtg_raytrace.hip, rtg_order.hip, rtg_camera.hip, rtg_ao.hip, rtg_matte.hip, rtg_gather.hip, rtg_filter.hip,
+// rtg_accumulate.hip): the HIP error
 // return, the records' NaN form, the colour and 32-byte record stores, the
 // host forms' plain scene and thread bands, the argument checks that differ
 // between entry points only in their prefix, and the one-shot body.  HIP

@@ -59,16 +59,18 @@ RTG_HD bool filter_admits(const FilterTerms& t, int idP, int idQ) {
   return idQ >= 0 && (!(t.flags & RTG_FILTER_SAME_ID) || idQ == idP);
 }
 
-// An admitted tap: `hw` = h[dy + 2] * h[dx + 2], `c` the centre's guide, `g`
-// and `v` the tap's guide and value.
+// Whether any of a value's C words is a NaN or an infinity.
 template <int C>
-RTG_HD void filter_tap(const FilterTerms& t, const FilterGuide& c, const FilterGuide& g,
-                       const float* v, float hw, FilterSum<C>& a) {
-  if (t.flags & RTG_FILTER_SKIP_NONFINITE) {
-    bool bad = false;
-    for (int q = 0; q < C; ++q) bad = bad || fold_nonfinite(v[q]);
-    if (bad) return;
-  }
+RTG_HD bool filter_nonfinite(const float* v) {
+  bool bad = false;
+  for (int q = 0; q < C; ++q) bad = bad || fold_nonfinite(v[q]);
+  return bad;
+}
+
+// A tap's weight: `hw` times the terms that are on, `c` the centre's guide and
+// `g` the tap's (also the bilinear taps of rtg_accumulate.h).
+RTG_HD float filter_weight(const FilterTerms& t, const FilterGuide& c, const FilterGuide& g,
+                           float hw) {
   float w = hw;
   if (t.flags & RTG_FILTER_NORMAL) {
     float k = vdot(c.n, g.n);
@@ -82,6 +84,16 @@ RTG_HD void filter_tap(const FilterTerms& t, const FilterGuide& c, const FilterG
     z = z > 0.f ? z : 0.f;
     w = w * z;
   }
+  return w;
+}
+
+// An admitted tap: `hw` = h[dy + 2] * h[dx + 2], `c` the centre's guide, `g`
+// and `v` the tap's guide and value.
+template <int C>
+RTG_HD void filter_tap(const FilterTerms& t, const FilterGuide& c, const FilterGuide& g,
+                       const float* v, float hw, FilterSum<C>& a) {
+  if ((t.flags & RTG_FILTER_SKIP_NONFINITE) && filter_nonfinite<C>(v)) return;
+  const float w = filter_weight(t, c, g, hw);
   if (!(w > 0.f)) return;
   for (int q = 0; q < C; ++q) a.v[q] = a.v[q] + w * v[q];
   a.sw = a.sw + w;

@@ -74,6 +74,15 @@ static void usage() {
   printf("                           RTG_FILTER_SAME_ID | NORMAL | PLANE; planeScale defaults to 1,\n");
   printf("                           normalLog2 to 3); the PGM is then 255 * value / K, clamped to\n");
   printf("                           0..255; needs --ao\n");
+  printf("      --ao-history FILE[,MAXHISTORY]\n");
+  printf("                           Accumulate the counts over a camera path before they are written:\n");
+  printf("                           one frame per line of FILE (poses in --camera's syntax, oldest\n");
+  printf("                           first) and then the --camera frame, frame k with seed + k, each\n");
+  printf("                           blended onto the last by rtg_accumulate_device (reprojection,\n");
+  printf("                           RTG_ACCUM_SAME_ID | NORMAL | PLANE, planeScale 1, normalLog2 3,\n");
+  printf("                           maxHistory 65535 unless given); the PGM is 255 * value / K as\n");
+  printf("                           with --ao-filter, which then smooths the accumulated frame;\n");
+  printf("                           needs --ao\n");
   printf("      --matte      FILE    Also write the frame's direct light (rtg_matte_device of every\n");
   printf("                           primary hit at aa 1, from --camera or the identity pose) as a\n");
   printf("                           P6 PPM, scaled by its own largest component like the render\n");
@@ -87,6 +96,10 @@ static void usage() {
   printf("      --gather-filter SPEC Smooth the gathered light before it is scaled and written: the\n");
   printf("                           spec and the filter of --ao-filter, with\n");
   printf("                           RTG_FILTER_SKIP_NONFINITE under --gather-skip; needs --gather\n");
+  printf("      --gather-history FILE[,MAXHISTORY]\n");
+  printf("                           Accumulate the gathered light the same way (with\n");
+  printf("                           RTG_ACCUM_SKIP_NONFINITE under --gather-skip) before it is\n");
+  printf("                           filtered, scaled and written; needs --gather\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -135,6 +148,69 @@ static void* filter_frame(rtg_context* ctx, const rtg_hit* hits, unsigned W, uns
   return dst;
 }
 
+// The poses of a file, one per line in --camera's syntax (blank lines are
+// skipped); exits on a file that cannot be read or a line that is no pose.
+static std::vector<rtg_camera> read_poses(const std::string& path) {
+  std::vector<rtg_camera> poses;
+  FILE* f = fopen(path.c_str(), "r");
+  if (!f) {
+    fprintf(stderr, "Error: can't read %s\n", path.c_str());
+    exit(EXIT_FAILURE);
+  }
+  char line[512];
+  while (fgets(line, sizeof line, f)) {
+    size_t len = strlen(line);
+    while (len && strchr(" \t\r\n", line[len - 1])) line[--len] = 0;
+    if (line[strspn(line, " \t")] == 0) continue;  // a blank line
+    rtg_camera c;
+    if (!parse_pose(line, &c)) {
+      printf("Invalid pose on line %zu of %s (ex,ey,ez,tx,ty,tz[,ux,uy,uz])\n", poses.size() + 1,
+             path.c_str());
+      exit(1);
+    }
+    poses.push_back(c);
+  }
+  fclose(f);
+  return poses;
+}
+
+// "FILE[,maxHistory]" of --ao-history and --gather-history: a camera path to
+// accumulate over; false when maxHistory is not in 1..65535.
+struct History {
+  bool on = false;
+  std::string file;
+  std::vector<rtg_camera> poses;  // oldest first; the --camera frame follows them
+  rtg_accumulate_params params = {0, RTG_ACCUM_SAME_ID | RTG_ACCUM_NORMAL | RTG_ACCUM_PLANE, 3, 1.f,
+                                  65535};
+};
+static bool parse_history(const char* s, History* h) {
+  h->file = s;
+  h->on = true;
+  const size_t comma = h->file.rfind(',');
+  if (comma == std::string::npos) return true;
+  const std::string tail = h->file.substr(comma + 1);
+  if (tail.empty() || tail.find_first_not_of("0123456789") != std::string::npos) return true;
+  h->file.resize(comma);
+  h->params.maxHistory = (unsigned)strtoul(tail.c_str(), nullptr, 10);
+  return tail.size() <= 5 && h->params.maxHistory >= 1 && h->params.maxHistory <= 65535;
+}
+
+// One frame of a history on the default stream: the state `to` from the
+// frame's records and signal and the state `from` (null: a reset frame).
+struct HistoryState {
+  rtg_camera pose;
+  rtg_hit* hits;
+  float* acc;
+  unsigned short* len;
+};
+static void accumulate_frame(rtg_context* ctx, const History& h, unsigned W, unsigned H, float zoom,
+                             const void* src, const HistoryState* from, const HistoryState& to) {
+  check(rtg_accumulate_device(ctx, to.hits, W, H, &h.params, src, from ? &from->pose : nullptr,
+                              zoom, from ? from->hits : nullptr, from ? from->acc : nullptr,
+                              from ? from->len : nullptr, nullptr, to.acc, to.len, nullptr, nullptr),
+        "rtg_accumulate_device");
+}
+
 static bool parse_uint(const char* s, unsigned* out) {
   char* end;
   unsigned long v = strtoul(s, &end, 10);
@@ -154,6 +230,7 @@ int main(int argc, char** argv) {
   rtg_ao_params aoParams = {0, 0.f, 1.0e-3f, 0, 0};
   bool aoFilter = false, gatherFilter = false;
   rtg_filter_params aoFilterParams = {}, gatherFilterParams = {};
+  History aoHistory, gatherHistory;
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   bool posed = false;
@@ -280,6 +357,11 @@ int main(int argc, char** argv) {
         return 1;
       }
       (forAo ? aoFilter : gatherFilter) = true;
+    } else if (!strcmp(a, "--ao-history") || !strcmp(a, "--gather-history")) {
+      if (!parse_history(need(a), a[2] == 'a' ? &aoHistory : &gatherHistory)) {
+        printf("Invalid history (FILE[,maxHistory], maxHistory in 1..65535)\n");
+        return 1;
+      }
     } else if (!strcmp(a, "--matte")) {
       matteOut = need(a);
       matte = true;
@@ -335,9 +417,19 @@ int main(int argc, char** argv) {
     printf("--ao-filter needs --ao, --gather-filter needs --gather\n");
     return 1;
   }
-  aoFilterParams.kind = RTG_FILTER_COUNT;
+  if ((aoHistory.on && !ao) || (gatherHistory.on && !gather)) {
+    printf("--ao-history needs --ao, --gather-history needs --gather\n");
+    return 1;
+  }
+  // (an accumulated frame is floats: the filter then takes it as GRAY)
+  aoFilterParams.kind = aoHistory.on ? RTG_FILTER_GRAY : RTG_FILTER_COUNT;
   gatherFilterParams.kind = RTG_FILTER_RGB;
   if (gatherSkip) gatherFilterParams.flags |= RTG_FILTER_SKIP_NONFINITE;
+  aoHistory.params.kind = RTG_FILTER_COUNT;
+  gatherHistory.params.kind = RTG_FILTER_RGB;
+  if (gatherSkip) gatherHistory.params.flags |= RTG_ACCUM_SKIP_NONFINITE;
+  if (aoHistory.on) aoHistory.poses = read_poses(aoHistory.file);
+  if (gatherHistory.on) gatherHistory.poses = read_poses(gatherHistory.file);
 
   if (posed && gpus) {
     printf("--camera renders on one device\n");
@@ -370,25 +462,7 @@ int main(int argc, char** argv) {
     views.resize(6);
     check(rtg_camera_cube(&cubeEye, views.data()), "rtg_camera_cube");
   } else if (manyViews) {
-    FILE* f = fopen(viewsIn.c_str(), "r");
-    if (!f) {
-      fprintf(stderr, "Error: can't read %s\n", viewsIn.c_str());
-      exit(EXIT_FAILURE);
-    }
-    char line[512];
-    while (fgets(line, sizeof line, f)) {
-      size_t len = strlen(line);
-      while (len && strchr(" \t\r\n", line[len - 1])) line[--len] = 0;
-      if (line[strspn(line, " \t")] == 0) continue;  // a blank line
-      rtg_camera c;
-      if (!parse_pose(line, &c)) {
-        printf("Invalid pose on line %zu of %s (ex,ey,ez,tx,ty,tz[,ux,uy,uz])\n", views.size() + 1,
-               viewsIn.c_str());
-        return 1;
-      }
-      views.push_back(c);
-    }
-    fclose(f);
+    views = read_poses(viewsIn);
   }
 
   std::vector<rtg_sphere> spheres;
@@ -587,36 +661,58 @@ int main(int argc, char** argv) {
     check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
           "rtg_context_set_scene");
     rtg_ray* dr = nullptr;
-    rtg_hit* dh = nullptr;
     rtg_vec* dd = nullptr;
     unsigned short* dc = nullptr;
+    // the frames of --ao-history ping-pong between two states; without it
+    // there is one frame and only its records
+    const size_t frames = aoHistory.on ? aoHistory.poses.size() + 1 : 1;
+    HistoryState st[2] = {};
     if (hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
-        hipMalloc(&dh, n * sizeof(rtg_hit)) != hipSuccess ||
         hipMalloc(&dd, K * sizeof(rtg_vec)) != hipSuccess ||
         hipMalloc(&dc, n * sizeof(unsigned short)) != hipSuccess)
       check(RTG_ERR_NOMEM, "hipMalloc");
+    for (size_t k = 0; k < (frames > 1 ? 2u : 1u); ++k)
+      if (hipMalloc(&st[k].hits, n * sizeof(rtg_hit)) != hipSuccess ||
+          (aoHistory.on && (hipMalloc(&st[k].acc, n * sizeof(float)) != hipSuccess ||
+                            hipMalloc(&st[k].len, n * sizeof(unsigned short)) != hipSuccess)))
+        check(RTG_ERR_NOMEM, "hipMalloc");
     if (hipMemcpy(dd, table.data(), K * sizeof(rtg_vec), hipMemcpyHostToDevice) != hipSuccess)
       check(RTG_ERR_HIP, "upload");
-    check(rtg_camera_rays_device(ctx, &camera, W, H, zoom, 1.f, dr, nullptr),
-          "rtg_camera_rays_device");
-    check(rtg_intersect_device(ctx, dr, n, dh, nullptr), "rtg_intersect_device");
-    check(rtg_ao_device(ctx, dh, n, &aoParams, dd, K, dc, nullptr), "rtg_ao_device");
+    for (size_t k = 0; k < frames; ++k) {
+      HistoryState& cur = st[k & 1];
+      cur.pose = k + 1 < frames ? aoHistory.poses[k] : camera;
+      rtg_ao_params ap = aoParams;
+      ap.seed += (unsigned)k;
+      check(rtg_camera_rays_device(ctx, &cur.pose, W, H, zoom, 1.f, dr, nullptr),
+            "rtg_camera_rays_device");
+      check(rtg_intersect_device(ctx, dr, n, cur.hits, nullptr), "rtg_intersect_device");
+      check(rtg_ao_device(ctx, cur.hits, n, &ap, dd, K, dc, nullptr), "rtg_ao_device");
+      if (aoHistory.on)
+        accumulate_frame(ctx, aoHistory, W, H, zoom, dc, k ? &st[(k - 1) & 1] : nullptr, cur);
+    }
+    const HistoryState& last = st[(frames - 1) & 1];
     std::vector<unsigned short> counts(n);
     std::vector<float> smooth;
     if (hipMemcpy(counts.data(), dc, n * sizeof(unsigned short), hipMemcpyDeviceToHost) !=
         hipSuccess)
       check(RTG_ERR_HIP, "readback");
-    if (aoFilter) {  // the counts never leave the device on their way through the filter
-      void* df = filter_frame(ctx, dh, W, H, aoFilterParams, dc);
+    if (aoFilter || aoHistory.on) {  // the frame never leaves the device on its way to the filter
+      void* df = aoFilter ? filter_frame(ctx, last.hits, W, H, aoFilterParams,
+                                         aoHistory.on ? (const void*)last.acc : dc)
+                          : last.acc;
       smooth.resize(n);
       if (hipMemcpy(smooth.data(), df, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
         check(RTG_ERR_HIP, "readback");
-      (void)hipFree(df);
+      if (aoFilter) (void)hipFree(df);
     }
     (void)hipFree(dr);
-    (void)hipFree(dh);
     (void)hipFree(dd);
     (void)hipFree(dc);
+    for (HistoryState& s : st) {
+      (void)hipFree(s.hits);
+      (void)hipFree(s.acc);
+      (void)hipFree(s.len);
+    }
     rtg_context_destroy(ctx);
     std::vector<unsigned char> grey(n);
     for (size_t k = 0; k < n; ++k) grey[k] = (unsigned char)((255u * counts[k]) / K);
@@ -630,8 +726,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "Error: can't write %s\n", aoOut.c_str());
       exit(EXIT_FAILURE);
     }
-    printf("Wrote %s (%ux%u, %u probes of length %.8g per primary hit)\n", aoOut.c_str(), W, H, K,
+    printf("Wrote %s (%ux%u, %u probes of length %.8g per primary hit", aoOut.c_str(), W, H, K,
            (double)aoParams.radius);
+    if (aoHistory.on) printf(", accumulated over %zu frames", frames);
+    printf(")\n");
   }
 
   if (matte) {  // pose -> primary rays -> hits -> direct light -> bytes, all on the device
@@ -691,14 +789,19 @@ int main(int argc, char** argv) {
     check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
           "rtg_context_set_scene");
     rtg_ray* dr = nullptr;
-    rtg_hit* dh = nullptr;
     rtg_vec* dd = nullptr;
     float* dw = nullptr;
     rtg_vec* dl = nullptr;
     float* dmax = nullptr;
     unsigned char* db = nullptr;
+    const size_t frames = gatherHistory.on ? gatherHistory.poses.size() + 1 : 1;  // as for --ao
+    HistoryState st[2] = {};
+    for (size_t k = 0; k < (frames > 1 ? 2u : 1u); ++k)
+      if (hipMalloc(&st[k].hits, n * sizeof(rtg_hit)) != hipSuccess ||
+          (gatherHistory.on && (hipMalloc(&st[k].acc, n * sizeof(rtg_vec)) != hipSuccess ||
+                                hipMalloc(&st[k].len, n * sizeof(unsigned short)) != hipSuccess)))
+        check(RTG_ERR_NOMEM, "hipMalloc");
     if (hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
-        hipMalloc(&dh, n * sizeof(rtg_hit)) != hipSuccess ||
         hipMalloc(&dd, K * sizeof(rtg_vec)) != hipSuccess ||
         hipMalloc(&dw, K * sizeof(float)) != hipSuccess ||
         hipMalloc(&dl, n * sizeof(rtg_vec)) != hipSuccess ||
@@ -707,14 +810,26 @@ int main(int argc, char** argv) {
     if (hipMemcpy(dd, table.data(), K * sizeof(rtg_vec), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dw, weights.data(), K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       check(RTG_ERR_HIP, "upload");
-    check(rtg_camera_rays_device(ctx, &camera, W, H, zoom, 1.f, dr, nullptr),
-          "rtg_camera_rays_device");
-    check(rtg_intersect_device(ctx, dr, n, dh, nullptr), "rtg_intersect_device");
-    check(rtg_gather_device(ctx, dh, n, &gatherParams, dd, dw, K, (int)depth + 1, dl, nullptr,
-                            nullptr),
-          "rtg_gather_device");
+    for (size_t k = 0; k < frames; ++k) {
+      HistoryState& cur = st[k & 1];
+      cur.pose = k + 1 < frames ? gatherHistory.poses[k] : camera;
+      rtg_gather_params gp = gatherParams;
+      gp.seed += (unsigned)k;
+      check(rtg_camera_rays_device(ctx, &cur.pose, W, H, zoom, 1.f, dr, nullptr),
+            "rtg_camera_rays_device");
+      check(rtg_intersect_device(ctx, dr, n, cur.hits, nullptr), "rtg_intersect_device");
+      check(rtg_gather_device(ctx, cur.hits, n, &gp, dd, dw, K, (int)depth + 1, dl, nullptr,
+                              nullptr),
+            "rtg_gather_device");
+      if (gatherHistory.on)
+        accumulate_frame(ctx, gatherHistory, W, H, zoom, dl, k ? &st[(k - 1) & 1] : nullptr, cur);
+    }
+    const HistoryState& last = st[(frames - 1) & 1];
+    if (gatherHistory.on &&  // the accumulated frame takes the gathered one's place
+        hipMemcpy(dl, last.acc, n * sizeof(rtg_vec), hipMemcpyDeviceToDevice) != hipSuccess)
+      check(RTG_ERR_HIP, "copy");
     if (gatherFilter) {
-      rtg_vec* smooth = (rtg_vec*)filter_frame(ctx, dh, W, H, gatherFilterParams, dl);
+      rtg_vec* smooth = (rtg_vec*)filter_frame(ctx, last.hits, W, H, gatherFilterParams, dl);
       (void)hipFree(dl);
       dl = smooth;
     }
@@ -726,7 +841,11 @@ int main(int argc, char** argv) {
         hipMemcpy(&lightMax, dmax, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
       check(RTG_ERR_HIP, "readback");
     (void)hipFree(dr);
-    (void)hipFree(dh);
+    for (HistoryState& s : st) {
+      (void)hipFree(s.hits);
+      (void)hipFree(s.acc);
+      (void)hipFree(s.len);
+    }
     (void)hipFree(dd);
     (void)hipFree(dw);
     (void)hipFree(dl);
@@ -739,8 +858,10 @@ int main(int argc, char** argv) {
       fprintf(stderr, "Error: can't write %s\n", gatherOut.c_str());
       exit(EXIT_FAILURE);
     }
-    printf("Wrote %s (%ux%u, %u probes per primary hit, depth %u, max %.8g)\n",
+    printf("Wrote %s (%ux%u, %u probes per primary hit, depth %u, max %.8g",
            gatherOut.c_str(), W, H, K, depth, (double)lightMax);
+    if (gatherHistory.on) printf(", accumulated over %zu frames", frames);
+    printf(")\n");
   }
 
   if (!raysIn.empty()) {  // records as they lie in memory, like the G-buffer's

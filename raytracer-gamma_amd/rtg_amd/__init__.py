@@ -79,6 +79,11 @@ assert FILTER_PARAMS_DTYPE.itemsize == 20
 FILTER_MAX_PASSES = 8  # RTG_FILTER_*
 FILTER_RGB, FILTER_GRAY, FILTER_COUNT = 0, 1, 2
 FILTER_SAME_ID, FILTER_NORMAL, FILTER_PLANE, FILTER_SKIP_NONFINITE = 1, 2, 4, 8
+# rtg_accumulate_params (include/rtg.h): temporal accumulation by reprojection
+ACCUM_PARAMS_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("normalLog2", "<u4"),
+                               ("planeScale", "<f4"), ("maxHistory", "<u4")])
+assert ACCUM_PARAMS_DTYPE.itemsize == 20
+ACCUM_SAME_ID, ACCUM_NORMAL, ACCUM_PLANE, ACCUM_SKIP_NONFINITE = 1, 2, 4, 8  # RTG_ACCUM_*
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -105,6 +110,7 @@ EXPORTED = [
     "rtg_intersect_indexed_device", "rtg_visible_indexed_device", "rtg_raytrace_indexed_device",
     "rtg_camera_identity", "rtg_camera_look_at", "rtg_camera_sample_count",
     "rtg_camera_rays_host", "rtg_camera_rays_device",
+    "rtg_camera_project_host", "rtg_camera_project_device", "rtg_camera_project",
     "rtg_render_camera_device", "rtg_render_camera", "rtg_render_camera_host",
     "rtg_render_views_device", "rtg_render_views", "rtg_render_views_host", "rtg_camera_cube",
     "rtg_views_fold_scratch", "rtg_views_fold_host", "rtg_views_fold_device",
@@ -116,6 +122,7 @@ EXPORTED = [
     "rtg_gather_rays_host", "rtg_gather_rays_device", "rtg_gather_device", "rtg_gather",
     "rtg_gather_host",
     "rtg_filter_scratch", "rtg_filter_host", "rtg_filter_device", "rtg_filter",
+    "rtg_accumulate_host", "rtg_accumulate_device", "rtg_accumulate",
     "rtg_contains_device", "rtg_contains", "rtg_contains_host",
 ]
 
@@ -273,6 +280,21 @@ def lib() -> ctypes.CDLL:
                 ("rtg_filter_host", [vp, u, u, vp, vp, vp, i]),
                 ("rtg_filter_device", [vp, vp, u, u, vp, vp, vp, vp, sz, vp]),
                 ("rtg_filter", [i, vp, u, u, vp, vp, vp])):
+            try:
+                getattr(L, name).argtypes = at
+            except AttributeError:
+                if not os.environ.get("RTG_LIB"):
+                    raise
+        # the accumulation and the projection; an RTG_LIB build of the commit before
+        # them (tools/ab_bench.sh against the parent) loads without them
+        for name, at in (
+                ("rtg_camera_project_host", [vp, u, u, f, vp, sz, vp, i]),
+                ("rtg_camera_project_device", [vp, vp, u, u, f, vp, sz, vp, vp]),
+                ("rtg_camera_project", [i, vp, u, u, f, vp, sz, vp]),
+                ("rtg_accumulate_host", [vp, u, u, vp, vp, vp, f, vp, vp, vp, vp, vp, vp, vp, i]),
+                ("rtg_accumulate_device",
+                 [vp, vp, u, u, vp, vp, vp, f, vp, vp, vp, vp, vp, vp, vp, vp]),
+                ("rtg_accumulate", [i, vp, u, u, vp, vp, vp, f, vp, vp, vp, vp, vp, vp, vp])):
             try:
                 getattr(L, name).argtypes = at
             except AttributeError:
@@ -1058,6 +1080,100 @@ def filter(hits, width: int, height: int, params, src, device: int = 0) -> np.nd
     return out
 
 
+def accumulate_params(kind: int = FILTER_RGB, flags: int = 0, plane_scale: float = 0.0,
+                      normal_log2: int = 0, max_history: int = 65535) -> np.ndarray:
+    """One rtg_accumulate_params record (kind: FILTER_RGB / GRAY / COUNT; flags:
+    ACCUM_SAME_ID | NORMAL | PLANE | SKIP_NONFINITE)."""
+    p = np.zeros(1, ACCUM_PARAMS_DTYPE)
+    p[0] = (kind, flags, normal_log2, plane_scale, max_history)
+    return p
+
+
+def _accumulate_args(hits, width: int, height: int, params, src, prev, m2: bool):
+    """The current records, params and source as contiguous arrays, the previous
+    state (None on a reset frame, else (camera, hits, acc, len[, m2])) likewise,
+    and the outputs: acc (H, W, 3) or (H, W) float32, len (H, W) uint16, m2 as
+    acc or None."""
+    p = np.ascontiguousarray(params, ACCUM_PARAMS_DTYPE).reshape(1)
+    kind = int(p["kind"][0])
+    C = 3 if kind == FILTER_RGB else 1
+    n = width * height
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    s = np.ascontiguousarray(src, np.uint16 if kind == FILTER_COUNT else np.float32).reshape(-1)
+    if len(h) != n or len(s) != n * C:
+        raise ValueError(f"accumulate: {len(h)} hit records and {len(s)} source words for a "
+                         f"{width} x {height} frame of kind {kind}")
+    pv = [None] * 5
+    if prev is not None:
+        pv[0] = np.ascontiguousarray(prev[0], CAMERA_DTYPE).reshape(1)
+        pv[1] = np.ascontiguousarray(prev[1], HIT_DTYPE).reshape(-1)
+        pv[2] = np.ascontiguousarray(prev[2], np.float32).reshape(-1)
+        pv[3] = np.ascontiguousarray(prev[3], np.uint16).reshape(-1)
+        if len(prev) > 4 and prev[4] is not None:
+            pv[4] = np.ascontiguousarray(prev[4], np.float32).reshape(-1)
+        if len(pv[1]) != n or len(pv[3]) != n or len(pv[2]) != n * C or \
+                (pv[4] is not None and len(pv[4]) != n * C):
+            raise ValueError(f"accumulate: previous state of another size than the "
+                             f"{width} x {height} frame of kind {kind}")
+    shape = (height, width, 3) if C == 3 else (height, width)
+    acc = np.empty(shape, np.float32)
+    ln = np.empty((height, width), np.uint16)
+    return h, p, s, pv, acc, ln, (np.empty(shape, np.float32) if m2 else None)
+
+
+def accumulate_host(hits, width: int, height: int, params, src, prev=None, zoom: float = -4.0,
+                    m2: bool = False, threads: int = 1):
+    """Temporal accumulation by reprojection on the host (rtg_accumulate_host; no
+    GPU needed): HIT_DTYPE records of the current pose's aa-1 primary rays, src
+    the current signal (float32 (H, W, 3) or (H, W), or uint16 counts), params
+    from accumulate_params(), `prev` the previous frame's (camera, hits, acc,
+    len[, m2]) or None for a reset frame.  Returns (acc, len) or, with m2, (acc,
+    len, m2)."""
+    h, p, s, pv, acc, ln, o2 = _accumulate_args(hits, width, height, params, src, prev, m2)
+    _check(lib().rtg_accumulate_host(_ptr(h), width, height, _ptr(p), _ptr(s), _ptr(pv[0]),
+                                     float(zoom), _ptr(pv[1]), _ptr(pv[2]), _ptr(pv[3]),
+                                     _ptr(pv[4]), _ptr(acc), _ptr(ln), _ptr(o2), threads),
+           "rtg_accumulate_host")
+    return (acc, ln, o2) if m2 else (acc, ln)
+
+
+def accumulate(hits, width: int, height: int, params, src, prev=None, zoom: float = -4.0,
+               m2: bool = False, device: int = 0):
+    """The same on the GPU, one-shot (rtg_accumulate)."""
+    h, p, s, pv, acc, ln, o2 = _accumulate_args(hits, width, height, params, src, prev, m2)
+    _check(lib().rtg_accumulate(device, _ptr(h), width, height, _ptr(p), _ptr(s), _ptr(pv[0]),
+                                float(zoom), _ptr(pv[1]), _ptr(pv[2]), _ptr(pv[3]), _ptr(pv[4]),
+                                _ptr(acc), _ptr(ln), _ptr(o2)),
+           "rtg_accumulate")
+    return (acc, ln, o2) if m2 else (acc, ln)
+
+
+def _project_args(camera, points):
+    c = np.ascontiguousarray(camera, CAMERA_DTYPE).reshape(1)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    return c, p, np.empty((len(p), 3), np.float32)
+
+
+def camera_project_host(camera, width: int, height: int, points, zoom: float = -4.0,
+                        threads: int = 1) -> np.ndarray:
+    """Where the points lie in the pose's width x height frame
+    (rtg_camera_project_host; no GPU needed): (n, 3) float32 rows {fx, fy, k};
+    a point is in front of the camera exactly when k > 0."""
+    c, p, out = _project_args(camera, points)
+    _check(lib().rtg_camera_project_host(_ptr(c), width, height, float(zoom), _ptr(p), len(p),
+                                         _ptr(out), threads), "rtg_camera_project_host")
+    return out
+
+
+def camera_project(camera, width: int, height: int, points, zoom: float = -4.0,
+                   device: int = 0) -> np.ndarray:
+    """The same on the GPU, one-shot (rtg_camera_project)."""
+    c, p, out = _project_args(camera, points)
+    _check(lib().rtg_camera_project(device, _ptr(c), width, height, float(zoom), _ptr(p), len(p),
+                                    _ptr(out)), "rtg_camera_project")
+    return out
+
+
 def _points(points):
     """Points as a contiguous (n, 3) float32 array, n, the int32 result and
     pointers that are never null for an empty batch."""
@@ -1438,6 +1554,40 @@ class Context:
                                        ctypes.c_void_p(scratch_ptr), scratch_bytes,
                                        ctypes.c_void_p(stream) if stream else None),
                "rtg_filter_device")
+
+    def accumulate_device(self, hits_ptr: int, width: int, height: int, params, src_ptr: int,
+                          out_acc_ptr: int, out_len_ptr: int, prev=None, zoom: float = -4.0,
+                          out_m2_ptr: int = 0, stream: int = 0):
+        """Temporal accumulation by reprojection of a width x height frame: the
+        current records at hits_ptr and signal at src_ptr (device, as
+        filter_device takes them), `prev` the previous frame's (camera,
+        hits_ptr, acc_ptr, len_ptr[, m2_ptr]) or None for a reset frame, into
+        out_acc_ptr (float32 per channel), out_len_ptr (uint16) and, when given,
+        out_m2_ptr, asynchronously on `stream` (rtg_accumulate_device; params
+        from accumulate_params(); the context needs no scene)."""
+        p = np.ascontiguousarray(params, ACCUM_PARAMS_DTYPE).reshape(1)
+        cam = None if prev is None or prev[0] is None else \
+            np.ascontiguousarray(prev[0], CAMERA_DTYPE).reshape(1)
+        pv = [0, 0, 0, 0] if prev is None else (list(prev[1:]) + [0])[:4]
+        v = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        _check(lib().rtg_accumulate_device(self._h, v(hits_ptr), width, height, _ptr(p),
+                                           v(src_ptr), _ptr(cam), float(zoom), v(pv[0]), v(pv[1]),
+                                           v(pv[2]), v(pv[3]), v(out_acc_ptr), v(out_len_ptr),
+                                           v(out_m2_ptr), v(stream)),
+               "rtg_accumulate_device")
+
+    def camera_project_device(self, camera, width: int, height: int, points_ptr: int, n: int,
+                              dst_ptr: int, zoom: float = -4.0, stream: int = 0):
+        """Where n points at points_ptr (device, an (n, 3) float32 tensor) lie in
+        the pose's frame, into dst_ptr (device, (n, 3) float32 rows {fx, fy, k}),
+        asynchronously on `stream` (rtg_camera_project_device; the context needs
+        no scene)."""
+        c = np.ascontiguousarray(camera, CAMERA_DTYPE).reshape(1)
+        _check(lib().rtg_camera_project_device(self._h, _ptr(c), width, height, float(zoom),
+                                               ctypes.c_void_p(points_ptr), n,
+                                               ctypes.c_void_p(dst_ptr),
+                                               ctypes.c_void_p(stream) if stream else None),
+               "rtg_camera_project_device")
 
     def matte_device(self, hits_ptr: int, n: int, dst_ptr: int, lit_ptr: int = 0,
                      stream: int = 0):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
                        [--only-order] [--only-ao] [--only-matte] [--only-views]
-                       [--only-fold] [--only-gather] [--only-filter]
+                       [--only-fold] [--only-gather] [--only-filter] [--only-accumulate]
                        [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
@@ -91,6 +91,12 @@ rows under "filter" (filter_rows below): five passes over the frame's AO counts
 and gathered light, the total and each pass, the tiled and the direct form of
 the pass kernel side by side per step, and a torch chain of the same
 arithmetic.  --only-filter runs these alone and keeps FILE's other sections.
+
+Temporal accumulation (rtg_accumulate_device, csrc/rtg_accumulate.hip) gets
+rows under "accumulate" (accumulate_rows below): one frame blended onto the
+previous one under a small pan and under a roll, both wave shapes of the kernel
+side by side, a torch chain of the same arithmetic and the streaming floor.
+--only-accumulate runs these alone and keeps FILE's other sections.
 GPU only.
 """
 import argparse
@@ -634,6 +640,200 @@ def filter_rows(args, stream):
     return out, ok
 
 
+def torch_accumulate(cur, prev, pose, W, H, zoom, flags, nlog, scale, max_history):
+    """rtg_accumulate* (include/rtg.h) as a chain of torch operations in the
+    definition's operand order: the projection, index gathers for the four taps,
+    `where` for the rules and a lerp.  cur = (ids, P, N, value planes), prev =
+    (ids, P, N, acc planes, len), planes of (H, W); returns (planes, len)."""
+    ids, P, N, val = cur
+    pid, pP, pN, pacc, plen = prev
+    eye, right, up, back = (tuple(float(v) for v in pose[k].reshape(-1)) for k in
+                            ("eye", "right", "up", "back"))
+    dot = lambda a, b: (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]  # noqa: E731
+    zero = torch.zeros((), dtype=torch.float32, device="cuda")
+    e = [P[q] - eye[q] for q in range(3)]
+    k = float(zoom) / dot(e, back)
+    fx = (dot(e, right) * k) * float(F(W) * F(0.046875)) + float(F(W) * F(0.5))
+    fy = float(F(H) * F(0.5)) - (dot(e, up) * k) * float(F(H) / F(12))
+    ok = (k > 0) & (fx > -1) & (fx < W) & (fy > -1) & (fy < H) & (ids >= 0)
+    xf, yf = torch.floor(fx), torch.floor(fy)
+    tx, ty = fx - xf, fy - yf
+    x0 = torch.where(ok, xf, zero).to(torch.int64)
+    y0 = torch.where(ok, yf, zero).to(torch.int64)
+    acc = [torch.zeros_like(v) for v in val]
+    sw = torch.zeros_like(fx)
+    nmin = torch.full_like(x0, 65535)
+    for dy in (0, 1):
+        for dx in (0, 1):
+            xq, yq = x0 + dx, y0 + dy
+            keep = ok & (xq >= 0) & (xq < W) & (yq >= 0) & (yq < H)
+            xs, ys = xq.clamp(0, W - 1), yq.clamp(0, H - 1)
+            w = (ty if dy else 1.0 - ty) * (tx if dx else 1.0 - tx)
+            idq, lq = pid[ys, xs], plen[ys, xs]
+            keep &= (idq >= 0) & (lq != 0)
+            if flags & R.ACCUM_SAME_ID:
+                keep &= idq == ids
+            if flags & R.ACCUM_NORMAL:
+                c = dot(N, [pN[q][ys, xs] for q in range(3)])
+                c = torch.where(c > 0, c, zero)
+                for _ in range(nlog):
+                    c = c * c
+                w = w * c
+            if flags & R.ACCUM_PLANE:
+                d = dot(N, [pP[q][ys, xs] - P[q] for q in range(3)]).abs()
+                z = 1.0 - d * scale
+                w = w * torch.where(z > 0, z, zero)
+            keep &= w > 0
+            for q in range(len(val)):
+                acc[q] = torch.where(keep, acc[q] + w * pacc[q][ys, xs], acc[q])
+            sw = torch.where(keep, sw + w, sw)
+            nmin = torch.where(keep, torch.minimum(nmin, lq), nmin)
+    found = sw > 0
+    n = torch.minimum(nmin + 1, torch.full_like(nmin, max_history))
+    alpha = 1.0 / n.to(torch.float32)
+    out = []
+    for q in range(len(val)):
+        hist = acc[q] / sw
+        out.append(torch.where(found, hist + alpha * (val[q] - hist), val[q]))
+    ln = torch.where(ids >= 0, torch.where(found, n, torch.ones_like(n)), torch.zeros_like(n))
+    return out, ln
+
+
+def accumulate_rows(args, stream):
+    """Temporal accumulation (csrc/rtg_accumulate.hip) with SAME_ID | NORMAL |
+    PLANE, planeScale 1 / (the scene's largest |radius|), normalLog2 3 and
+    maxHistory 64: the K = 16 jittered AO counts and the K = 16 gathered light
+    of the aa = 1 primary hits, 3840 x 2160 on C3 and 1920 x 1080 on C5, blended
+    onto the state of a previous pose a small pan away and of one a roll away
+    (that pose's own records and signal, every length 3).  Round by round in one
+    process: the call as it chooses its wave shape, the call with each shape
+    forced (RTG_ACCUM_FORM), and a torch chain of the same arithmetic.
+    Reported, not gated: every time, and the distance from the streaming floor
+    (the current and the previous records, src, prevAcc, prevLen, outAcc and
+    outLen once each at 6 TB/s; next to it the same with the previous state
+    counted for the pixels that have a point only, which is what a frame with
+    background moves).  Gated: the call's lengths are the chain's and
+    its values agree to 1e-4 relative on finite pixels."""
+    K, nlog, max_history = 16, 3, 64
+    FORMS = ("tile", "row")
+    flags = R.ACCUM_SAME_ID | R.ACCUM_NORMAL | R.ACCUM_PLANE
+    table = torch.from_numpy(R.ao_directions(K)).cuda()
+    wt = torch.full((K,), 1.0 / K, dtype=torch.float32, device="cuda")
+    eye, target = np.array((0.0, 0.0, 0.0)), np.array((0.0, 0.0, -10.0))
+    moves = {"pan": R.camera_look_at(eye + (0.05, 0.02, 0.0), target + (0.03, 0.01, 0.0)),
+             "roll": R.camera_look_at(eye, target, (0.03, 1.0, 0.0))}
+    now = R.camera_look_at(eye, target)
+    out, ok = {"flags": flags, "normalLog2": nlog, "maxHistory": max_history, "samples": K,
+               "floor_bandwidth_TBps": 6.0, "moves": {
+                   "pan": "eye +(0.05, 0.02, 0), target +(0.03, 0.01, 0)", "roll": "up (0.03, 1, 0)"}}, True
+    for name, cfg, (W, H), kind in (("c3_count", "c3", CONFIGS["c3"][:2], R.FILTER_COUNT),
+                                    ("c3_rgb", "c3", CONFIGS["c3"][:2], R.FILTER_RGB),
+                                    ("c5_count_1080p", "c5", (1920, 1080), R.FILTER_COUNT),
+                                    ("c5_rgb_1080p", "c5", (1920, 1080), R.FILTER_RGB)):
+        n, S, C = W * H, CONFIGS[cfg][4] + 1, 3 if kind == R.FILTER_RGB else 1
+        sph, lg = R.generate_scene(CONFIGS[cfg][2], CONFIGS[cfg][3], 42)
+        scale = float(F(1) / np.abs(sph["radius"]).max())
+        radius = float(F(2.5) * np.abs(sph["radius"]).max())
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        rays = torch.empty((n, 6), dtype=torch.float32, device="cuda")
+
+        def frame(cam, seed):
+            """(records, signal) of a pose."""
+            hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+            ctx.camera_rays(cam, W, H, rays.data_ptr(), alias_factor=1.0, stream=stream)
+            ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream)
+            if kind == R.FILTER_COUNT:
+                src = torch.empty((n,), dtype=torch.int16, device="cuda")
+                ctx.ao_device(hits.data_ptr(), n, R.ao_params(K, radius, 1e-3, seed, R.AO_JITTER),
+                              table.data_ptr(), K, src.data_ptr(), stream)
+            else:
+                src = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+                gp = R.gather_params(K, 1e-3, seed, R.GATHER_JITTER | R.GATHER_SKIP_NONFINITE)
+                ctx.gather_device(hits.data_ptr(), n, gp, table.data_ptr(), wt.data_ptr(), K,
+                                  src.data_ptr(), stack_size=S, stream=stream)
+            torch.cuda.synchronize()
+            return hits, src
+
+        def planes(hits, src):
+            h = hits.view(torch.float32)
+            val = [(src.to(torch.int32) & 0xFFFF).to(torch.float32).reshape(H, W)] \
+                if kind == R.FILTER_COUNT else [src[:, q].reshape(H, W).contiguous() for q in range(3)]
+            return (hits[:, 0].reshape(H, W).contiguous(),
+                    [h[:, 2 + q].reshape(H, W).contiguous() for q in range(3)],
+                    [h[:, 5 + q].reshape(H, W).contiguous() for q in range(3)], val)
+
+        hits, src = frame(now, 43)
+        cur = planes(hits, src)
+        p = R.accumulate_params(kind, flags, scale, nlog, max_history)
+        o_acc = torch.empty((n, C), dtype=torch.float32, device="cuda")
+        o_len = torch.empty((n,), dtype=torch.int16, device="cuda")
+        bytes_px = 32 + (2 if kind == R.FILTER_COUNT else 12) + 32 + 4 * C + 2 + 4 * C + 2
+        floor = n * bytes_px / 6.0e12 * 1e3
+        # (a pixel without a point reads no previous state: the floor of this frame's traffic)
+        n_hit = int((hits[:, 0] >= 0).sum())
+        prev_px = 32 + 4 * C + 2
+        floor_hit = (n * (bytes_px - prev_px) + n_hit * prev_px) / 6.0e12 * 1e3
+        row = {"W": W, "H": H, "kind": int(kind), "hit_points": n_hit,
+               "plane_scale": scale, "bytes_per_pixel": bytes_px, "floor_ms": round(floor, 5),
+               "floor_ms_previous_state_of_hits_only": round(floor_hit, 5)}
+        for move, cam in moves.items():
+            p_hits, p_src = frame(cam, 42)
+            pv = planes(p_hits, p_src)
+            p_acc = torch.stack(pv[3], -1).reshape(n, C).contiguous()
+            p_len = torch.full((n,), 3, dtype=torch.int16, device="cuda")
+            prev = (cam, p_hits.data_ptr(), p_acc.data_ptr(), p_len.data_ptr())
+
+            def call(form):
+                if form:
+                    os.environ["RTG_ACCUM_FORM"] = form
+                else:
+                    os.environ.pop("RTG_ACCUM_FORM", None)
+                ctx.accumulate_device(hits.data_ptr(), W, H, p, src.data_ptr(), o_acc.data_ptr(),
+                                      o_len.data_ptr(), prev, stream=stream)
+
+            m = measure([lambda: call("")] + [(lambda f=f: call(f)) for f in FORMS], args.rounds,
+                        window_ms=100.0,
+                        names=[f"accumulate {name} {move} {f}" for f in ("default",) + FORMS])
+            os.environ.pop("RTG_ACCUM_FORM", None)
+            call("")
+            torch.cuda.synchronize()
+            got, got_len = o_acc.clone(), o_len.to(torch.int64) & 0xFFFF
+            tp = (pv[0], pv[1], pv[2], pv[3], p_len.to(torch.int64).reshape(H, W))
+            chain = lambda: torch_accumulate(cur, tp, cam, W, H, -4.0, flags, nlog, scale,  # noqa: E731
+                                             max_history)
+            ref, ref_len = chain()
+            ref = torch.stack(ref, -1).reshape(n, C)
+            tm = measure([chain], args.rounds, window_ms=100.0, min_reps=1,
+                         names=[f"accumulate {name} {move} torch chain"])[0]
+            fin = torch.isfinite(got) & torch.isfinite(ref)
+            same_len = bool((got_len == ref_len.reshape(-1)).all())
+            rel = ((got - ref).abs() / ref.abs().clamp_min(1e-30))[fin]
+            worst = float(rel.max()) if rel.numel() else 0.0
+            agree = same_len and worst <= 1e-4 and \
+                bool((torch.isfinite(got) == torch.isfinite(ref)).all())
+            ok = ok and agree
+            real = hits[:, 0] >= 0
+            row[move] = {
+                "default": m[0], "forms": dict(zip(FORMS, m[1:])),
+                "default_over_floor": round(m[0]["ms_median"] / floor, 2),
+                "forms_over_floor": {f: round(x["ms_median"] / floor, 2) for f, x in zip(FORMS, m[1:])},
+                "torch_chain": tm, "torch_over_accumulate": round(tm["ms_median"] / m[0]["ms_median"], 2),
+                "found_share_of_hit_pixels": round(float(((got_len == 4) & real).sum() / real.sum()), 4),
+                "lengths_equal": same_len, "largest_relative_difference": worst,
+                "bit_equal": bool((got.view(torch.int32) == ref.view(torch.int32))[fin].all()),
+                "agree_to_1e-4": agree}
+            print(f"accumulate {name} {move}: {m[0]['ms_median']} ms (floor {floor:.4f}), torch "
+                  f"{tm['ms_median']} ms, largest relative difference {worst:.3g}",
+                  file=sys.stderr, flush=True)
+            del p_hits, p_src, pv, p_acc, p_len, tp, ref, ref_len, got, got_len, fin, rel
+        out[name] = row
+        ctx.close()
+        del hits, src, cur, rays, o_acc, o_len
+        torch.cuda.empty_cache()
+    return out, ok
+
+
 def matte_rows(args, W, H, rays, stream):
     """Direct light (csrc/rtg_matte.hip) of the frame's 8.3 M aa = 1 primary
     hits on C3 (3 lights) and C5 (4 lights).  Round by round in one process: the
@@ -973,8 +1173,10 @@ def main():
                     help="the gather's rows alone, put into FILE next to what it holds")
     ap.add_argument("--only-filter", action="store_true",
                     help="the filter's rows alone, put into FILE next to what it holds")
+    ap.add_argument("--only-accumulate", action="store_true",
+                    help="the temporal accumulation's rows alone, put into FILE next to what it holds")
     ap.add_argument("--parent-commit", default="",
-                    help="recorded with --only-fold, --only-gather or --only-filter as the parent "
+                    help="recorded with --only-fold, --only-gather, --only-filter or --only-accumulate as the parent "
                          "of --commit")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
@@ -1021,6 +1223,15 @@ def main():
         res["filter_commit"], res["filter_parent_commit"] = args.commit, args.parent_commit
         res["filter"], ok = filter_rows(args, torch.cuda.current_stream().cuda_stream)
         res["filter"]["rounds"] = args.rounds
+        finish(args, res, ok)
+    if args.only_accumulate:  # (the same: it makes the frames of its own poses)
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["accumulate_commit"], res["accumulate_parent_commit"] = args.commit, args.parent_commit
+        res["accumulate"], ok = accumulate_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["accumulate"]["rounds"] = args.rounds
         finish(args, res, ok)
     W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
     assert (W, H) == CONFIGS["c5"][:2]
