@@ -15,13 +15,10 @@
 // the camera move.  Under a coherent move a wave's taps fall into a window of
 // the previous frame about the size of the wave's own footprint plus one
 // pixel, so the wave's shape decides how many cache lines the gathers touch.
-// Two shapes, workgroups of 256 lanes in a one-dimensional grid either way:
-//   row:  a wave is 64 pixels of a row, a workgroup 64 x 4;
-//   tile: a wave is an 8 x 8 tile as in the camera kernels, a workgroup 32 x 8.
-// The row shape is the default: it was 7 to 16 % faster on every measured frame
-// (DESIGN.md §25), its streams being whole cache lines where the tile's are
-// eight short runs.  env RTG_ACCUM_FORM=tile|row forces one (a performance
-// knob: the words are the same either way).
+// A wave is 64 pixels of a row, a workgroup of 256 lanes 64 x 4 pixels, in a
+// one-dimensional grid: its streams are whole cache lines.  (An 8 x 8 tile per
+// wave, as in the camera kernels, was 7 to 16 % slower on every measured
+// frame, DESIGN.md §25, and is gone.)
 //
 // Bounds: a lane outside the frame leaves before any load or store; a tap is
 // read only after the frame test on its integer position; a pixel index is
@@ -33,8 +30,6 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "rtg.h"
 #include "rtg_accumulate.h"
@@ -48,12 +43,8 @@ static_assert(sizeof(rtg_hit) == 32 && offsetof(rtg_hit, id) == 0 && offsetof(rt
 namespace rtg {
 
 constexpr unsigned kAccumThreads = 256;
-// The wave shape taken by default.
-constexpr bool kAccumDefaultTile = false;
-
-// A workgroup's footprint in pixels for a wave shape.
-constexpr unsigned accum_group_w(bool tile) { return tile ? 32 : 64; }
-constexpr unsigned accum_group_h(bool tile) { return tile ? 8 : 4; }
+// A workgroup's footprint in pixels: a wave per row.
+constexpr unsigned kAccumGroupW = 64, kAccumGroupH = kAccumThreads / 64;
 
 // What the kernel takes.
 struct AccumArgs {
@@ -67,16 +58,10 @@ struct AccumArgs {
   unsigned groupsX;
 };
 
-// (filter_load_guide's loads; the entry point checks the alignment)
+// (the entry point checks the alignment)
 struct AccumLoadGuide {
   __device__ __forceinline__ FilterGuide operator()(const rtg_hit* h) const {
-    const uint4* r = reinterpret_cast<const uint4*>(h);
-    const uint4 a = r[0], b = r[1];
-    FilterGuide g;
-    g.id = (int)a.x;
-    g.p = v3(__uint_as_float(a.z), __uint_as_float(a.w), __uint_as_float(b.x));
-    g.n = v3(__uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w));
-    return g;
+    return filter_load_guide(h);
   }
 };
 
@@ -84,12 +69,12 @@ struct AccumHostGuide {
   FilterGuide operator()(const rtg_hit* h) const { return filter_guide(h); }
 };
 
-template <int C, bool kCount, bool kM2, bool kTile>
+template <int C, bool kCount, bool kM2>
 __global__ __launch_bounds__(kAccumThreads) void accum_kernel(const AccumArgs k) {
   const unsigned wave = threadIdx.x / 64, l = threadIdx.x % 64;
   const size_t gx = blockIdx.x % k.groupsX, gy = blockIdx.x / k.groupsX;
-  const size_t x = gx * accum_group_w(kTile) + (kTile ? wave * 8 + l % 8 : l);
-  const size_t y = gy * accum_group_h(kTile) + (kTile ? l / 8 : wave);
+  const size_t x = gx * kAccumGroupW + l;
+  const size_t y = gy * kAccumGroupH + wave;
   if (x >= k.a.W || y >= k.a.H) return;
   const size_t i = y * k.a.W + x;  // < W H
   const FilterGuide c = AccumLoadGuide()(k.hits + i);
@@ -132,18 +117,6 @@ static void accum_host_rows(const AccumArgs& k, unsigned kind, size_t y0, size_t
 
 using namespace rtg;
 
-static int accum_channels(unsigned kind) { return kind == RTG_FILTER_RGB ? 3 : 1; }
-static size_t accum_src_size(unsigned kind) {
-  return kind == RTG_FILTER_RGB ? sizeof(rtg_vec)
-                                : kind == RTG_FILTER_GRAY ? sizeof(float) : sizeof(unsigned short);
-}
-
-// Byte ranges [a, a + na) and [b, b + nb), addresses as numbers.
-static bool accum_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a && b && na && nb && x < y + nb && y < x + na;
-}
-
 // What the three forms share, in the order it is reported in; fills `k` but
 // for its grid.
 static int check_accumulate(const rtg_hit* hits, unsigned W, unsigned H,
@@ -183,32 +156,20 @@ static int check_accumulate(const rtg_hit* hits, unsigned W, unsigned H,
     rtg_set_error("accumulate: frame %u x %u (at most 2^24 each way)", W, H);
     return RTG_ERR_INVALID;
   }
-  if (p->normalLog2 > 8) {
-    rtg_set_error("accumulate: normalLog2 %u outside [0, 8]", p->normalLog2);
-    return RTG_ERR_INVALID;
-  }
-  if (p->kind > RTG_FILTER_COUNT) {
-    rtg_set_error("accumulate: kind %u (0: RGB, 1: GRAY, 2: COUNT)", p->kind);
-    return RTG_ERR_INVALID;
-  }
-  const unsigned known =
-      RTG_ACCUM_SAME_ID | RTG_ACCUM_NORMAL | RTG_ACCUM_PLANE | RTG_ACCUM_SKIP_NONFINITE;
-  if (p->flags & ~known) {
-    rtg_set_error("accumulate: unknown flags 0x%x", p->flags & ~known);
-    return RTG_ERR_INVALID;
-  }
+  const int rc = check_filter_terms("accumulate", p->normalLog2, p->kind, p->flags);
+  if (rc) return rc;
   if (p->maxHistory < 1 || p->maxHistory > 65535) {
     rtg_set_error("accumulate: maxHistory %u outside [1, 65535]", p->maxHistory);
     return RTG_ERR_INVALID;
   }
   const size_t n = (size_t)W * H;  // <= 2^48
-  const size_t vals = n * (size_t)accum_channels(p->kind) * sizeof(float);
+  const size_t vals = n * (size_t)filter_channels(p->kind) * sizeof(float);
   const struct { const char* name; const void* at; size_t bytes; bool out; } r[] = {
       {"outAcc", outAcc, vals, true},
       {"outLen", outLen, n * sizeof(unsigned short), true},
       {"outM2", outM2, vals, true},
       {"hits", hits, n * sizeof(rtg_hit), false},
-      {"src", src, n * accum_src_size(p->kind), false},
+      {"src", src, n * filter_src_size(p->kind), false},
       {"prevHits", prevHits, n * sizeof(rtg_hit), false},
       {"prevAcc", prevAcc, vals, false},
       {"prevLen", prevLen, n * sizeof(unsigned short), false},
@@ -216,7 +177,7 @@ static int check_accumulate(const rtg_hit* hits, unsigned W, unsigned H,
   };
   for (size_t i = 0; i < 3; ++i)  // each output against every later range
     for (size_t j = i + 1; j < sizeof r / sizeof r[0]; ++j)
-      if (accum_overlap(r[i].at, r[i].bytes, r[j].at, r[j].bytes)) {
+      if (filter_overlap(r[i].at, r[i].bytes, r[j].at, r[j].bytes)) {
         rtg_set_error("accumulate: %s overlaps %s", r[i].name, r[j].name);
         return RTG_ERR_INVALID;
       }
@@ -241,19 +202,18 @@ static int check_accumulate(const rtg_hit* hits, unsigned W, unsigned H,
   return RTG_OK;
 }
 
-template <bool kTile>
 static void launch_accum(const AccumArgs& k, unsigned kind, unsigned blocks, hipStream_t st) {
   const dim3 g(blocks), b(kAccumThreads);
   const bool m2 = k.outM2 != nullptr;
   if (kind == RTG_FILTER_RGB) {
-    if (m2) hipLaunchKernelGGL((accum_kernel<3, false, true, kTile>), g, b, 0, st, k);
-    else hipLaunchKernelGGL((accum_kernel<3, false, false, kTile>), g, b, 0, st, k);
+    if (m2) hipLaunchKernelGGL((accum_kernel<3, false, true>), g, b, 0, st, k);
+    else hipLaunchKernelGGL((accum_kernel<3, false, false>), g, b, 0, st, k);
   } else if (kind == RTG_FILTER_COUNT) {
-    if (m2) hipLaunchKernelGGL((accum_kernel<1, true, true, kTile>), g, b, 0, st, k);
-    else hipLaunchKernelGGL((accum_kernel<1, true, false, kTile>), g, b, 0, st, k);
+    if (m2) hipLaunchKernelGGL((accum_kernel<1, true, true>), g, b, 0, st, k);
+    else hipLaunchKernelGGL((accum_kernel<1, true, false>), g, b, 0, st, k);
   } else {
-    if (m2) hipLaunchKernelGGL((accum_kernel<1, false, true, kTile>), g, b, 0, st, k);
-    else hipLaunchKernelGGL((accum_kernel<1, false, false, kTile>), g, b, 0, st, k);
+    if (m2) hipLaunchKernelGGL((accum_kernel<1, false, true>), g, b, 0, st, k);
+    else hipLaunchKernelGGL((accum_kernel<1, false, false>), g, b, 0, st, k);
   }
 }
 
@@ -306,20 +266,15 @@ int rtg_accumulate_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned 
                   ((uintptr_t)hitsDevice & 15) ? "hit buffer" : "previous hit buffer");
     return RTG_ERR_INVALID;
   }
-  bool tile = kAccumDefaultTile;
-  if (const char* v = getenv("RTG_ACCUM_FORM")) {  // A/B knob (performance only)
-    tile = !strcmp(v, "tile") ? true : !strcmp(v, "row") ? false : tile;
-  }
-  const size_t groupsX = ((size_t)width + accum_group_w(tile) - 1) / accum_group_w(tile);
-  const size_t groups = groupsX * (((size_t)height + accum_group_h(tile) - 1) / accum_group_h(tile));
+  const size_t groupsX = ((size_t)width + kAccumGroupW - 1) / kAccumGroupW;
+  const size_t groups = groupsX * (((size_t)height + kAccumGroupH - 1) / kAccumGroupH);
   if (groups > 0x7FFFFFFFu) {
     rtg_set_error("accumulate: frame too large (%zu workgroups)", groups);
     return RTG_ERR_INVALID;
   }
   k.groupsX = (unsigned)groupsX;
   HIP_TRY(hipSetDevice(device));
-  if (tile) launch_accum<true>(k, params->kind, (unsigned)groups, (hipStream_t)stream);
-  else launch_accum<false>(k, params->kind, (unsigned)groups, (hipStream_t)stream);
+  launch_accum(k, params->kind, (unsigned)groups, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return RTG_OK;
 }
@@ -337,56 +292,25 @@ int rtg_accumulate(int device, const rtg_hit* hits, unsigned width, unsigned hei
   if (rc) return rc;
   const bool reset = !prevHits;
   const size_t n = (size_t)width * height;
-  const size_t vals = n * (size_t)accum_channels(params->kind) * sizeof(float);
-  // one allocation, each part 16-byte aligned: the inputs up, the outputs down
-  struct Part { const void* from; void* to; size_t bytes, at; };
-  Part parts[] = {
-      {hits, nullptr, n * sizeof(rtg_hit), 0},
-      {src, nullptr, n * accum_src_size(params->kind), 0},
-      {prevHits, nullptr, reset ? 0 : n * sizeof(rtg_hit), 0},
-      {prevAcc, nullptr, reset ? 0 : vals, 0},
-      {prevLen, nullptr, reset ? 0 : n * sizeof(unsigned short), 0},
-      {prevM2, nullptr, reset || !prevM2 ? 0 : vals, 0},
-      {nullptr, outAcc, vals, 0},
-      {nullptr, outLen, n * sizeof(unsigned short), 0},
-      {nullptr, outM2, outM2 ? vals : 0, 0},
-  };
-  size_t total = 0;
-  for (Part& p : parts) {
-    p.at = total;
-    total = (total + p.bytes + 15) & ~(size_t)15;
-  }
-  rtg_context* ctx = nullptr;
-  rc = rtg_context_create(device, &ctx);
-  if (rc) return rc;
-  unsigned char* d = nullptr;
-  if (hipSetDevice(device) != hipSuccess || hipMalloc(&d, total) != hipSuccess) {
-    rtg_set_error("accumulate: hipMalloc(%zu) failed", total);
-    rc = RTG_ERR_NOMEM;
-  }
-  for (const Part& p : parts)
-    if (!rc && p.from && p.bytes &&
-        hipMemcpy(d + p.at, p.from, p.bytes, hipMemcpyHostToDevice) != hipSuccess) {
-      rtg_set_error("accumulate: upload of %zu bytes failed", p.bytes);
-      rc = RTG_ERR_HIP;
-    }
-  auto at = [&](int i) -> void* { return parts[i].bytes ? d + parts[i].at : nullptr; };
-  if (!rc)
-    rc = rtg_accumulate_device(ctx, (const rtg_hit*)at(0), width, height, params, at(1), prevCam,
-                               zoom, (const rtg_hit*)at(2), (const float*)at(3),
-                               (const unsigned short*)at(4), (const float*)at(5), (float*)at(6),
-                               (unsigned short*)at(7), (float*)at(8), nullptr);
-  for (const Part& p : parts)
-    if (!rc && p.to && p.bytes) {
-      const hipError_t e = hipMemcpy(p.to, d + p.at, p.bytes, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) {
-        rtg_set_error("accumulate: kernel/readback failed: %s", hipGetErrorString(e));
-        rc = RTG_ERR_HIP;
-      }
-    }
-  (void)hipFree(d);
-  rtg_context_destroy(ctx);
-  return rc;
+  const size_t vals = n * (size_t)filter_channels(params->kind) * sizeof(float);
+  const size_t recs = n * sizeof(rtg_hit), lens = n * sizeof(unsigned short);
+  return one_shot(
+      "accumulate", device, nullptr,
+      {{recs, hits, nullptr},
+       {n * filter_src_size(params->kind), src, nullptr},
+       {reset ? 0 : recs, prevHits, nullptr},
+       {reset ? 0 : vals, prevAcc, nullptr},
+       {reset ? 0 : lens, prevLen, nullptr},
+       {reset || !prevM2 ? 0 : vals, prevM2, nullptr},
+       {vals, nullptr, outAcc},
+       {lens, nullptr, outLen},
+       {outM2 ? vals : 0, nullptr, outM2}},
+      [&](rtg_context* ctx, void* const* d) {
+        return rtg_accumulate_device(ctx, (const rtg_hit*)d[0], width, height, params, d[1],
+                                     prevCam, zoom, (const rtg_hit*)d[2], (const float*)d[3],
+                                     (const unsigned short*)d[4], (const float*)d[5],
+                                     (float*)d[6], (unsigned short*)d[7], (float*)d[8], nullptr);
+      });
 }
 
 }  // extern "C"

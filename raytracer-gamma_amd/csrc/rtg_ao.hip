@@ -26,7 +26,7 @@
 // past n read record n - 1 and store nothing), a table index < nDirs
 // (ao_dir_index), an output index < n.
 //
-// ao_segments_kernel: one lane per segment, 24 B out; it needs no scene.
+// The segment generator is rtg_probes.h's, with the far end as its tail.
 //
 // rtg_ao_host: walk 0 = plain loops (blocked over the caller's array), the
 // yardstick; walk 1 = the kernel's own path (ray_blocked with the hoisted
@@ -40,12 +40,11 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <vector>
-
 #include "rtg.h"
 #include "rtg_ao.h"
 #include "rtg_entry.h"
 #include "rtg_host_scene.h"
+#include "rtg_probes.h"
 #include "rtg_rays.h"
 #include "rtg_scene_pack.h"
 #include "rtg_trace_kernels.h"
@@ -59,32 +58,12 @@ static_assert(RTG_AO_MAX_SAMPLES <= 0xFFFF, "a count fits an unsigned short");
 
 namespace rtg {
 
-// Segment k of point i as six words; a record without a point: zeros.
-RTG_HD void ao_segment(const rtg_hit* hits, size_t i, unsigned k, const rtg_ao_params& p,
-                       const rtg_vec* dirs, unsigned nDirs, unsigned* w) {
-  const AoPoint pt = ao_point(hits + i, p.bias);
-  V3 a = v3(0.f, 0.f, 0.f), b = v3(0.f, 0.f, 0.f);
-  if (pt.id >= 0) {
-    a = pt.a;
-    b = ao_end(pt, ao_dir(dirs, ao_dir_index(ao_window(p, i, nDirs), k, nDirs)), p.radius);
-  }
-  w[0] = nan_bits(a.x); w[1] = nan_bits(a.y); w[2] = nan_bits(a.z);
-  w[3] = nan_bits(b.x); w[4] = nan_bits(b.y); w[5] = nan_bits(b.z);
-}
-
-// One lane per segment; total = n * K > 0.
-__global__ __launch_bounds__(64) void ao_segments_kernel(const rtg_hit* __restrict__ hits,
-                                                         size_t total, const rtg_ao_params p,
-                                                         const rtg_vec* __restrict__ dirs,
-                                                         unsigned nDirs,
-                                                         rtg_segment* __restrict__ segs) {
-  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (k >= total) return;
-  unsigned w[6];
-  ao_segment(hits, k / p.samples, (unsigned)(k % p.samples), p, dirs, nDirs, w);  // k / K < n
-  unsigned* o = reinterpret_cast<unsigned*>(segs + k);  // k < total: 24 B of the batch
-  for (int q = 0; q < 6; ++q) o[q] = w[q];
-}
+// A probe segment's last three words: its far end.
+struct AoEnd {
+  float radius;
+  RTG_HD V3 operator()(const AoPoint& pt, V3 l) const { return ao_end(pt, l, radius); }
+};
+static AoEnd ao_end_of(const rtg_ao_params& p) { return AoEnd{p.radius}; }
 
 // One lane per point; n > 0.
 template <bool kBvh, bool kJitter>
@@ -161,42 +140,10 @@ static void ao_host_range(const Scene& sc, const RayBox& box, const rtg_hit* hit
 using namespace rtg;
 
 // The checks every form shares, in the order they are reported in.
-static int check_ao(const char* what, const void* hits, const rtg_ao_params* p,
-                    const void* dirs, unsigned nDirs, const void* out) {
-  if (!hits || !p || !dirs || !out) {
-    rtg_set_error("%s: null %s", what,
-                  !hits ? "hit buffer" : !p ? "params" : !dirs ? "direction table" : "output buffer");
-    return RTG_ERR_INVALID;
-  }
-  if (p->samples < 1 || p->samples > RTG_AO_MAX_SAMPLES) {
-    rtg_set_error("%s: %u samples outside [1, %d]", what, p->samples, RTG_AO_MAX_SAMPLES);
-    return RTG_ERR_INVALID;
-  }
-  if (nDirs < p->samples || nDirs > RTG_AO_MAX_DIRS) {
-    rtg_set_error("%s: %u directions outside [samples = %u, %d]", what, nDirs, p->samples,
-                  RTG_AO_MAX_DIRS);
-    return RTG_ERR_INVALID;
-  }
-  if (p->flags & ~(unsigned)RTG_AO_JITTER) {
-    rtg_set_error("%s: unknown flags 0x%x", what, p->flags & ~(unsigned)RTG_AO_JITTER);
-    return RTG_ERR_INVALID;
-  }
-  return RTG_OK;
-}
-
-// n as the window hash takes it.
-static int check_ao_points(const char* what, size_t n) {
-  if (n <= 0xFFFFFFFFull) return RTG_OK;
-  rtg_set_error("%s: %zu points (at most 2^32 - 1)", what, n);
-  return RTG_ERR_INVALID;
-}
-
-// The segments' n * K (reported before the point count: every n whose product
-// overflows is above 2^32 - 1 too).
-static int check_ao_product(const char* what, size_t n, unsigned K) {
-  if (n <= SIZE_MAX / K) return check_ao_points(what, n);
-  rtg_set_error("%s: %zu points x %u samples overflows size_t", what, n, K);
-  return RTG_ERR_INVALID;
+static int check_ao(const rtg_hit* hits, const rtg_ao_params* p, const rtg_vec* dirs,
+                    unsigned nDirs, const void* out, size_t n) {
+  const int rc = check_probes("ao", RTG_AO_JITTER, hits, p, dirs, false, nullptr, nDirs, out);
+  return rc ? rc : check_probe_points("ao", n);
 }
 
 extern "C" {
@@ -225,47 +172,15 @@ int rtg_ao_directions(unsigned nDirs, rtg_vec* out) {
 int rtg_ao_segments_host(const rtg_hit* hits, size_t n, const rtg_ao_params* params,
                          const rtg_vec* dirs, unsigned nDirs, rtg_segment* segsHost,
                          int nthreads) {
-  rtg_clear_error();
-  int rc = check_ao("ao_segments", hits, params, dirs, nDirs, segsHost);
-  if (!rc) rc = check_ao_product("ao_segments", n, params->samples);
-  if (rc) return rc;
-  if (n == 0) return RTG_OK;
-  const rtg_ao_params p = *params;
-  host_bands(n, nthreads, [&](size_t i0, size_t i1) {
-    for (size_t i = i0; i < i1; ++i) {
-      for (unsigned k = 0; k < p.samples; ++k) {
-        unsigned w[6];
-        ao_segment(hits, i, k, p, dirs, nDirs, w);
-        memcpy(segsHost + i * p.samples + k, w, sizeof w);
-      }
-    }
-  });
-  return RTG_OK;
+  return probes_host("ao_segments", RTG_AO_JITTER, hits, n, params, ao_end_of, dirs, nDirs,
+                     segsHost, nthreads);
 }
 
 int rtg_ao_segments_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
                            const rtg_ao_params* params, const rtg_vec* dirsDevice,
                            unsigned nDirs, rtg_segment* segsDevice, void* stream) {
-  DeviceGuard deviceGuard;  // the caller's current device is restored on return
-  rtg_clear_error();
-  int device = 0;
-  if (!rtg_context_device(ctx, &device)) {
-    rtg_set_error("ao_segments: no context");
-    return RTG_ERR_INVALID;
-  }
-  int rc = check_ao("ao_segments", hitsDevice, params, dirsDevice, nDirs, segsDevice);
-  if (!rc) rc = check_ao_product("ao_segments", n, params->samples);
-  if (rc) return rc;
-  if (n == 0) return RTG_OK;
-  const size_t total = n * params->samples;
-  unsigned blocks;
-  rc = ray_blocks("ao_segments", "batch", total, &blocks);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(ao_segments_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream,
-                     hitsDevice, total, *params, dirsDevice, nDirs, segsDevice);
-  HIP_TRY(hipGetLastError());
-  return RTG_OK;
+  return probes_device("ao_segments", RTG_AO_JITTER, ctx, hitsDevice, n, params, ao_end_of,
+                       dirsDevice, nDirs, segsDevice, stream);
 }
 
 int rtg_ao_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
@@ -280,8 +195,7 @@ int rtg_ao_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
     rtg_set_error("ao: no context/scene");
     return RTG_ERR_INVALID;
   }
-  int rc = check_ao("ao", hitsDevice, params, dirsDevice, nDirs, outDevice);
-  if (!rc) rc = check_ao_points("ao", n);
+  int rc = check_ao(hitsDevice, params, dirsDevice, nDirs, outDevice, n);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
   unsigned blocks;
@@ -303,8 +217,7 @@ int rtg_ao_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_hit* hits,
                 const rtg_ao_params* params, const rtg_vec* dirs, unsigned nDirs,
                 unsigned short* outHost, int walk, int nthreads) {
   rtg_clear_error();
-  int rc = check_ao("ao", hits, params, dirs, nDirs, outHost);
-  if (!rc) rc = check_ao_points("ao", n);
+  int rc = check_ao(hits, params, dirs, nDirs, outHost, n);
   if (!rc) rc = check_scene_arrays("ao", spheres, sphNum);
   if (!rc) rc = check_walk("ao", walk);
   if (!rc && walk == 1) rc = check_sphere_count("ao", sphNum);
@@ -333,22 +246,19 @@ int rtg_ao(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_hit
            unsigned short* outHost) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
-  int rc = check_ao("ao", hits, params, dirs, nDirs, outHost);
-  if (!rc) rc = check_ao_points("ao", n);
+  int rc = check_ao(hits, params, dirs, nDirs, outHost, n);
   if (!rc) rc = check_scene_arrays("ao", spheres, sphNum);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
-  // one upload: the hit records, then the table
-  const size_t hitBytes = n * sizeof(rtg_hit), dirBytes = (size_t)nDirs * sizeof(rtg_vec);
-  std::vector<unsigned char> in(hitBytes + dirBytes);
-  memcpy(in.data(), hits, hitBytes);
-  memcpy(in.data() + hitBytes, dirs, dirBytes);
-  return one_shot(device, spheres, sphNum, nullptr, 0, in.data(), in.size(), outHost,
-                  n * sizeof(unsigned short), [&](rtg_context* ctx, const void* dIn, void* out) {
-                    const unsigned char* d = (const unsigned char*)dIn;
-                    return rtg_ao_device(ctx, (const rtg_hit*)d, n, params,
-                                         (const rtg_vec*)(d + hitBytes), nDirs,
-                                         (unsigned short*)out, nullptr);
+  const StageScene scene{spheres, sphNum, nullptr, 0};
+  return one_shot("ao", device, &scene,
+                  {{n * sizeof(rtg_hit), hits, nullptr},
+                   {(size_t)nDirs * sizeof(rtg_vec), dirs, nullptr},
+                   {n * sizeof(unsigned short), nullptr, outHost}},
+                  [&](rtg_context* ctx, void* const* d) {
+                    return rtg_ao_device(ctx, (const rtg_hit*)d[0], n, params,
+                                         (const rtg_vec*)d[1], nDirs, (unsigned short*)d[2],
+                                         nullptr);
                   });
 }
 

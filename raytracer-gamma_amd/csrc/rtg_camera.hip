@@ -369,32 +369,14 @@ int rtg_camera_project(int device, const rtg_camera* cam, unsigned width, unsign
   rtg_clear_error();
   int rc = check_project(cam, width, height, points, n, outHost);
   if (rc || n == 0) return rc;
-  rtg_context* ctx = nullptr;
-  rc = rtg_context_create(device, &ctx);
-  if (rc) return rc;
   const size_t bytes = n * sizeof(rtg_vec);
-  unsigned char* d = nullptr;  // the points, then the results
-  if (hipSetDevice(device) != hipSuccess || hipMalloc(&d, 2 * bytes) != hipSuccess) {
-    rtg_set_error("camera_project: hipMalloc(%zu) failed", 2 * bytes);
-    rc = RTG_ERR_NOMEM;
-  }
-  if (!rc && hipMemcpy(d, points, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-    rtg_set_error("camera_project: upload of %zu bytes failed", bytes);
-    rc = RTG_ERR_HIP;
-  }
-  if (!rc)
-    rc = rtg_camera_project_device(ctx, cam, width, height, zoom, (const rtg_vec*)d, n,
-                                   (rtg_vec*)(d + bytes), nullptr);
-  if (!rc) {
-    const hipError_t e = hipMemcpy(outHost, d + bytes, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rtg_set_error("camera_project: kernel/readback failed: %s", hipGetErrorString(e));
-      rc = RTG_ERR_HIP;
-    }
-  }
-  (void)hipFree(d);
-  rtg_context_destroy(ctx);
-  return rc;
+  return one_shot("camera_project", device, nullptr,
+                  {{bytes, points, nullptr}, {bytes, nullptr, outHost}},
+                  [&](rtg_context* ctx, void* const* d) {
+                    return rtg_camera_project_device(ctx, cam, width, height, zoom,
+                                                     (const rtg_vec*)d[0], n, (rtg_vec*)d[1],
+                                                     nullptr);
+                  });
 }
 
 int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
@@ -478,7 +460,7 @@ int rtg_render_camera(int device, const rtg_sphere* spheres, unsigned sphNum,
     rtg_set_error("render_camera: frame too large (more than 2^31-1 workgroups)");
     return RTG_ERR_INVALID;
   }
-  return one_shot(device, spheres, sphNum, lights, lgtNum, nullptr, 0, dstHost,
+  return one_shot("render_camera", device, {spheres, sphNum, lights, lgtNum}, nullptr, 0, dstHost,
                   (size_t)width * height * sizeof(rtg_vec),
                   [&](rtg_context* ctx, const void*, void* out) {
                     return rtg_render_camera_device(ctx, cam, width, height, zoom, aliasFactor,
@@ -597,8 +579,8 @@ int rtg_render_views(int device, const rtg_sphere* spheres, unsigned sphNum,
   if (rc) return rc;
   if (nViews == 0) return RTG_OK;
   DeviceGuard deviceGuard;  // (after the checks: no GPU call before them)
-  return one_shot(device, spheres, sphNum, lights, lgtNum, poses, nViews * sizeof(rtg_camera),
-                  dstHost, nViews * width * height * sizeof(rtg_vec),
+  return one_shot("render_views", device, {spheres, sphNum, lights, lgtNum}, poses,
+                  nViews * sizeof(rtg_camera), dstHost, nViews * width * height * sizeof(rtg_vec),
                   [&](rtg_context* ctx, const void* in, void* out) {
                     return rtg_render_views_device(ctx, (const rtg_camera*)in, nViews, width,
                                                    height, zoom, aliasFactor, stackSize,
@@ -707,40 +689,19 @@ int rtg_render_views_fold(int device, const rtg_sphere* spheres, unsigned sphNum
   const size_t K = params->weights, nGroups = nViews / params->viewsPerGroup;
   const size_t tableBytes = (size_t)params->viewsPerGroup * width * height * K * sizeof(float);
   const size_t scratchBytes = nViews * tilesPerView * fold_tile_words(params->weights) * 4;
-  const size_t outBytes = nGroups * K * sizeof(rtg_vec);
-  // the poses go up through one_shot; the table, the counts and the scratch here
-  void *dW = nullptr, *dSkipped = nullptr, *dScratch = nullptr;
-  HIP_TRY(hipSetDevice(device));
-  rc = RTG_OK;
-  if (hipMalloc(&dW, tableBytes) != hipSuccess || hipMalloc(&dScratch, scratchBytes) != hipSuccess ||
-      (skippedHost && hipMalloc(&dSkipped, nGroups * sizeof(unsigned)) != hipSuccess)) {
-    rtg_set_error("hipMalloc(%zu + %zu) failed", tableBytes, scratchBytes);
-    rc = RTG_ERR_NOMEM;
-  }
-  if (!rc && hipMemcpy(dW, weights, tableBytes, hipMemcpyHostToDevice) != hipSuccess) {
-    rtg_set_error("upload of %zu bytes failed", tableBytes);
-    rc = RTG_ERR_HIP;
-  }
-  if (!rc)
-    rc = one_shot(device, spheres, sphNum, lights, lgtNum, poses, nViews * sizeof(rtg_camera),
-                  outHost, outBytes, [&](rtg_context* ctx, const void* in, void* out) {
-                    const int r = rtg_render_views_fold_device(
-                        ctx, (const rtg_camera*)in, nViews, width, height, zoom, aliasFactor,
-                        stackSize, params, (const float*)dW, (rtg_vec*)out, (unsigned*)dSkipped,
-                        dScratch, scratchBytes, nullptr);
-                    if (r || !skippedHost) return r;
-                    // (a blocking copy on the null stream: after both kernels)
-                    if (hipMemcpy(skippedHost, dSkipped, nGroups * sizeof(unsigned),
-                                  hipMemcpyDeviceToHost) != hipSuccess) {
-                      rtg_set_error("readback of the skip counts failed");
-                      return RTG_ERR_HIP;
-                    }
-                    return RTG_OK;
+  const StageScene scene{spheres, sphNum, lights, lgtNum};
+  return one_shot("render_views_fold", device, &scene,
+                  {{nViews * sizeof(rtg_camera), poses, nullptr},
+                   {tableBytes, weights, nullptr},
+                   {scratchBytes, nullptr, nullptr},
+                   {nGroups * K * sizeof(rtg_vec), nullptr, outHost},
+                   {skippedHost ? nGroups * sizeof(unsigned) : 0, nullptr, skippedHost}},
+                  [&](rtg_context* ctx, void* const* d) {
+                    return rtg_render_views_fold_device(
+                        ctx, (const rtg_camera*)d[0], nViews, width, height, zoom, aliasFactor,
+                        stackSize, params, (const float*)d[1], (rtg_vec*)d[3], (unsigned*)d[4],
+                        d[2], scratchBytes, nullptr);
                   });
-  (void)hipFree(dW);
-  (void)hipFree(dSkipped);
-  (void)hipFree(dScratch);
-  return rc;
 }
 
 // Real SH of bands l = 0 .. bands-1 at the unit vector (x, y, z), k = l(l+1)+m.

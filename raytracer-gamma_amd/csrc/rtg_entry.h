@@ -1,6 +1,5 @@
-// rtg_entry.h — what the C ABI entry points of librtg.so share (rtg_kernel.hip,
-// rtg_gbuffer.hip, rtg_rays.hip, rtg_raytrace.hip, rtg_order.hip, rtg_camera.hip, rtg_ao.hip, rtg_matte.hip, rtg_gather.hip, rtg_filter.hip,
-// rtg_accumulate.hip): the HIP error
+// rtg_entry.h — what the C ABI entry points of librtg.so share (every .hip of
+// this directory but the rtg_trace_s<S> instantiations): the HIP error
 // return, the records' NaN form, the colour and 32-byte record stores, the
 // host forms' plain scene and thread bands, the argument checks that differ
 // between entry points only in their prefix, and the one-shot body.  HIP
@@ -13,11 +12,13 @@
 #include <string.h>
 
 #include <functional>
+#include <initializer_list>
 #include <thread>
 #include <vector>
 
 #include "rtg.h"
 #include "rtg_internal.h"
+#include "rtg_stage.h"
 #include "rtg_trace.h"
 
 #define HIP_TRY(expr)                                                              \
@@ -128,12 +129,41 @@ inline int ray_blocks(const char* what, const char* noun, size_t n, unsigned* bl
   return RTG_OK;
 }
 
-// One-shot body (rtg_kernel.hip): a context on `device` with the scene,
-// `inBytes` of input up (none: dIn is null), `launch` on the context,
-// `outBytes` down, everything freed.  The caller has checked its arguments.
-int one_shot(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
-             unsigned lgtNum, const void* in, size_t inBytes, void* out, size_t outBytes,
-             const std::function<int(rtg_context* ctx, const void* dIn, void* dOut)>& launch);
+// ---- one-shot body (rtg_kernel.hip) ----
+
+// The scene of a one-shot call; the calls without one pass none.
+struct StageScene {
+  const rtg_sphere* spheres;
+  unsigned sphNum;
+  const rtg_light* lights;
+  unsigned lgtNum;
+};
+
+// One array of a one-shot call on the device: uploaded from `from` before the
+// launch, downloaded to `to` after it, device scratch with neither.  A part
+// of 0 bytes has a null device pointer and no copy.
+struct StagePart {
+  size_t bytes;
+  const void* from;
+  void* to;
+};
+
+// A context on `device`, with the scene if there is one; the parts in one
+// allocation (rtg_stage.h has the layout), the uploads, `launch` on the
+// context with part i's device pointer in d[i], the downloads, everything
+// freed.  The caller has checked its arguments; `what` prefixes the failures.
+int one_shot(const char* what, int device, const StageScene* scene,
+             std::initializer_list<StagePart> parts,
+             const std::function<int(rtg_context* ctx, void* const* d)>& launch);
+
+// One array up (none: dIn is null), one down.
+inline int one_shot(
+    const char* what, int device, const StageScene& scene, const void* in, size_t inBytes,
+    void* out, size_t outBytes,
+    const std::function<int(rtg_context* ctx, const void* dIn, void* dOut)>& launch) {
+  return one_shot(what, device, &scene, {{inBytes, in, nullptr}, {outBytes, nullptr, out}},
+                  [&](rtg_context* ctx, void* const* d) { return launch(ctx, d[0], d[1]); });
+}
 
 }  // namespace rtg
 

@@ -1,6 +1,9 @@
 // rtg_filter.h — the edge-stopping a-trous filter (rtg_filter*, rtg.h): the
 // per-tap code, ONE definition for the pass kernels and the host loops
-// (rtg_filter.hip), the way gather_add and ao_world are shared.
+// (rtg_filter.hip), the way gather_add and ao_world are shared, and what a
+// frame of a kind is to the filter and to the accumulation alike
+// (rtg_accumulate.hip): its sizes, the overlap test, the record loader and the
+// check of the terms.
 //
 // A pass visits 25 taps per pixel.  filter_admits is the part of the tap rule
 // that needs the ids alone (the forms read nothing else of a tap it rejects),
@@ -10,8 +13,12 @@
 // FP contract: the Makefile's FPFLAGS, as every kernel.
 #pragma once
 
+#include <stddef.h>
+#include <stdint.h>
+
 #include "rtg.h"
 #include "rtg_fold.h"
+#include "rtg_internal.h"
 #include "rtg_trace.h"
 
 namespace rtg {
@@ -41,6 +48,55 @@ RTG_HD FilterGuide filter_guide(const rtg_hit* h) {
   g.p = v3(h->point.x, h->point.y, h->point.z);
   g.n = v3(h->normal.x, h->normal.y, h->normal.z);
   return g;
+}
+
+#if defined(__HIPCC__)
+// The same words as two 16-byte loads; `h` is 16-byte aligned (the device
+// entry points check).
+__device__ __forceinline__ FilterGuide filter_load_guide(const rtg_hit* h) {
+  const uint4* r = reinterpret_cast<const uint4*>(h);
+  const uint4 a = r[0], b = r[1];
+  FilterGuide g;
+  g.id = (int)a.x;
+  g.p = v3(__uint_as_float(a.z), __uint_as_float(a.w), __uint_as_float(b.x));
+  g.n = v3(__uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w));
+  return g;
+}
+#endif
+
+// Channels and bytes per source value of a kind.
+inline int filter_channels(unsigned kind) { return kind == RTG_FILTER_RGB ? 3 : 1; }
+inline size_t filter_src_size(unsigned kind) {
+  return kind == RTG_FILTER_RGB ? sizeof(rtg_vec)
+                                : kind == RTG_FILTER_GRAY ? sizeof(float) : sizeof(unsigned short);
+}
+
+// Byte ranges [a, a + na) and [b, b + nb), addresses as numbers; a null or
+// empty range overlaps nothing.
+inline bool filter_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a && b && na && nb && x < y + nb && y < x + na;
+}
+
+// normalLog2, the kind and the flags (RTG_ACCUM_* are the same bits,
+// rtg_accumulate.h), in the order they are reported in.
+inline int check_filter_terms(const char* what, unsigned normalLog2, unsigned kind,
+                              unsigned flags) {
+  if (normalLog2 > 8) {
+    rtg_set_error("%s: normalLog2 %u outside [0, 8]", what, normalLog2);
+    return RTG_ERR_INVALID;
+  }
+  if (kind > RTG_FILTER_COUNT) {
+    rtg_set_error("%s: kind %u (0: RGB, 1: GRAY, 2: COUNT)", what, kind);
+    return RTG_ERR_INVALID;
+  }
+  const unsigned known =
+      RTG_FILTER_SAME_ID | RTG_FILTER_NORMAL | RTG_FILTER_PLANE | RTG_FILTER_SKIP_NONFINITE;
+  if (flags & ~known) {
+    rtg_set_error("%s: unknown flags 0x%x", what, flags & ~known);
+    return RTG_ERR_INVALID;
+  }
+  return RTG_OK;
 }
 
 // h[i + 2] of the definition, i = -2 .. 2.

@@ -84,16 +84,6 @@ constexpr size_t filter_stage_bytes(unsigned s, int C) {
   return filter_stage_cells(s) * (7 + C) * sizeof(unsigned);
 }
 
-__device__ __forceinline__ FilterGuide filter_load_guide(const rtg_hit* h) {
-  const uint4* r = reinterpret_cast<const uint4*>(h);  // 16-byte aligned: the entry point checks
-  const uint4 a = r[0], b = r[1];
-  FilterGuide g;
-  g.id = (int)a.x;
-  g.p = v3(__uint_as_float(a.z), __uint_as_float(a.w), __uint_as_float(b.x));
-  g.n = v3(__uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w));
-  return g;
-}
-
 template <int C, bool kCount>
 __device__ __forceinline__ void filter_load_value(const void* in, size_t i, float* v) {
   if constexpr (kCount) {
@@ -282,13 +272,6 @@ static void filter_host_rows(const rtg_hit* hits, unsigned W, unsigned H, unsign
 
 using namespace rtg;
 
-// Channels and bytes per source value of a kind.
-static int filter_channels(unsigned kind) { return kind == RTG_FILTER_RGB ? 3 : 1; }
-static size_t filter_src_size(unsigned kind) {
-  return kind == RTG_FILTER_RGB ? sizeof(rtg_vec)
-                                : kind == RTG_FILTER_GRAY ? sizeof(float) : sizeof(unsigned short);
-}
-
 // The frame and the parameters, in the order they are reported in; *n = W H.
 static int check_filter_frame(const char* what, unsigned W, unsigned H, const rtg_filter_params* p,
                               size_t* n) {
@@ -309,28 +292,10 @@ static int check_filter_frame(const char* what, unsigned W, unsigned H, const rt
     rtg_set_error("%s: %u passes outside [1, %d]", what, p->passes, RTG_FILTER_MAX_PASSES);
     return RTG_ERR_INVALID;
   }
-  if (p->normalLog2 > 8) {
-    rtg_set_error("%s: normalLog2 %u outside [0, 8]", what, p->normalLog2);
-    return RTG_ERR_INVALID;
-  }
-  if (p->kind > RTG_FILTER_COUNT) {
-    rtg_set_error("%s: kind %u (0: RGB, 1: GRAY, 2: COUNT)", what, p->kind);
-    return RTG_ERR_INVALID;
-  }
-  const unsigned known =
-      RTG_FILTER_SAME_ID | RTG_FILTER_NORMAL | RTG_FILTER_PLANE | RTG_FILTER_SKIP_NONFINITE;
-  if (p->flags & ~known) {
-    rtg_set_error("%s: unknown flags 0x%x", what, p->flags & ~known);
-    return RTG_ERR_INVALID;
-  }
+  const int rc = check_filter_terms(what, p->normalLog2, p->kind, p->flags);
+  if (rc) return rc;
   *n = (size_t)px;
   return RTG_OK;
-}
-
-// Byte ranges [a, a + na) and [b, b + nb), addresses as numbers.
-static bool filter_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return na && nb && x < y + nb && y < x + na;
 }
 
 static size_t filter_scratch_bytes(size_t n, const rtg_filter_params& p) {
@@ -502,38 +467,16 @@ int rtg_filter(int device, const rtg_hit* hits, unsigned width, unsigned height,
   size_t n = 0;
   int rc = check_filter("filter", hits, width, height, params, src, dstHost, &n);
   if (rc) return rc;
-  const size_t hitBytes = n * sizeof(rtg_hit), srcBytes = n * filter_src_size(params->kind);
-  const size_t dstBytes = n * (size_t)filter_channels(params->kind) * sizeof(float);
   const size_t scratchBytes = filter_scratch_bytes(n, *params);
-  rtg_context* ctx = nullptr;
-  rc = rtg_context_create(device, &ctx);
-  if (rc) return rc;
-  // one allocation: the hits, src, dst and the scratch, each 16-byte aligned
-  const size_t oSrc = hitBytes, oDst = (oSrc + srcBytes + 15) & ~(size_t)15;
-  const size_t oScratch = (oDst + dstBytes + 15) & ~(size_t)15;
-  unsigned char* d = nullptr;
-  if (hipSetDevice(device) != hipSuccess || hipMalloc(&d, oScratch + scratchBytes) != hipSuccess) {
-    rtg_set_error("filter: hipMalloc(%zu) failed", oScratch + scratchBytes);
-    rc = RTG_ERR_NOMEM;
-  }
-  if (!rc && (hipMemcpy(d, hits, hitBytes, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(d + oSrc, src, srcBytes, hipMemcpyHostToDevice) != hipSuccess)) {
-    rtg_set_error("filter: upload of %zu bytes failed", hitBytes + srcBytes);
-    rc = RTG_ERR_HIP;
-  }
-  if (!rc)
-    rc = rtg_filter_device(ctx, (const rtg_hit*)d, width, height, params, d + oSrc, d + oDst,
-                           scratchBytes ? d + oScratch : nullptr, scratchBytes, nullptr);
-  if (!rc) {
-    const hipError_t e = hipMemcpy(dstHost, d + oDst, dstBytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rtg_set_error("filter: kernel/readback failed: %s", hipGetErrorString(e));
-      rc = RTG_ERR_HIP;
-    }
-  }
-  (void)hipFree(d);
-  rtg_context_destroy(ctx);
-  return rc;
+  return one_shot("filter", device, nullptr,
+                  {{n * sizeof(rtg_hit), hits, nullptr},
+                   {n * filter_src_size(params->kind), src, nullptr},
+                   {n * (size_t)filter_channels(params->kind) * sizeof(float), nullptr, dstHost},
+                   {scratchBytes, nullptr, nullptr}},
+                  [&](rtg_context* ctx, void* const* d) {
+                    return rtg_filter_device(ctx, (const rtg_hit*)d[0], width, height, params,
+                                             d[1], d[2], d[3], scratchBytes, nullptr);
+                  });
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 //
 // gather_kernel (rtg_gather_kernels.h, instantiated per stack size in
 // rtg_trace_s<S>.hip): one lane per point in one-wave workgroups.
-// gather_rays_kernel: one lane per ray, 24 B out; it needs no scene.
+// The ray generator is rtg_probes.h's, with the direction as its tail.
 //
 // rtg_gather_host: walk 0 = trace_ray_plain, plain loops over every sphere for
 // every query, the yardstick; walk 1 = the kernel's own path (trace_ray) over
@@ -29,13 +29,12 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <vector>
-
 #include "rtg.h"
 #include "rtg_ao.h"
 #include "rtg_entry.h"
 #include "rtg_gather_kernels.h"
 #include "rtg_host_scene.h"
+#include "rtg_probes.h"
 #include "rtg_rays.h"
 #include "rtg_scene_pack.h"
 
@@ -48,32 +47,11 @@ static_assert(RTG_GATHER_MAX_SAMPLES <= 0xFFFF, "a skip count fits an unsigned s
 
 namespace rtg {
 
-// Ray k of point i as six words; a record without a point: zeros.
-RTG_HD void gather_ray(const rtg_hit* hits, size_t i, unsigned k, const rtg_gather_params& p,
-                       const rtg_vec* dirs, unsigned nDirs, unsigned* w) {
-  const AoPoint pt = ao_point(hits + i, p.bias);
-  V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 0.f);
-  if (pt.id >= 0) {
-    o = pt.a;
-    d = gather_dir(pt, ao_dir(dirs, ao_dir_index(ao_window(p.flags, p.seed, i, nDirs), k, nDirs)));
-  }
-  w[0] = nan_bits(o.x); w[1] = nan_bits(o.y); w[2] = nan_bits(o.z);
-  w[3] = nan_bits(d.x); w[4] = nan_bits(d.y); w[5] = nan_bits(d.z);
-}
-
-// One lane per ray; total = n * K > 0.
-__global__ __launch_bounds__(64) void gather_rays_kernel(const rtg_hit* __restrict__ hits,
-                                                         size_t total, const rtg_gather_params p,
-                                                         const rtg_vec* __restrict__ dirs,
-                                                         unsigned nDirs,
-                                                         rtg_ray* __restrict__ rays) {
-  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (k >= total) return;
-  unsigned w[6];
-  gather_ray(hits, k / p.samples, (unsigned)(k % p.samples), p, dirs, nDirs, w);  // k / K < n
-  unsigned* o = reinterpret_cast<unsigned*>(rays + k);  // k < total: 24 B of the batch
-  for (int q = 0; q < 6; ++q) o[q] = w[q];
-}
+// A probe ray's last three words: its direction.
+struct GatherDir {
+  RTG_HD V3 operator()(const AoPoint& pt, V3 l) const { return gather_dir(pt, l); }
+};
+static GatherDir gather_dir_of(const rtg_gather_params&) { return GatherDir{}; }
 
 // ---- host forms ----
 
@@ -109,95 +87,28 @@ typedef void (*HostGatherFn)(const PackedScene&, const RayBox&, const GatherArgs
 
 using namespace rtg;
 
-// The checks every form shares, in the order they are reported in; the
-// generator has no weights and no stack (`fused` false).
-static int check_gather(const char* what, const void* hits, const rtg_gather_params* p,
-                        const void* dirs, bool fused, const void* weights, unsigned nDirs,
-                        const void* out, int stackSize) {
-  if (!hits || !p || !dirs || (fused && !weights) || !out) {
-    rtg_set_error("%s: null %s", what,
-                  !hits ? "hit buffer" : !p ? "params" : !dirs ? "direction table"
-                  : (fused && !weights) ? "weight table" : "output buffer");
-    return RTG_ERR_INVALID;
-  }
-  if (p->samples < 1 || p->samples > RTG_GATHER_MAX_SAMPLES) {
-    rtg_set_error("%s: %u samples outside [1, %d]", what, p->samples, RTG_GATHER_MAX_SAMPLES);
-    return RTG_ERR_INVALID;
-  }
-  if (nDirs < p->samples || nDirs > RTG_GATHER_MAX_DIRS) {
-    rtg_set_error("%s: %u directions outside [samples = %u, %d]", what, nDirs, p->samples,
-                  RTG_GATHER_MAX_DIRS);
-    return RTG_ERR_INVALID;
-  }
-  const unsigned known = RTG_GATHER_JITTER | RTG_GATHER_SKIP_NONFINITE;
-  if (p->flags & ~known) {
-    rtg_set_error("%s: unknown flags 0x%x", what, p->flags & ~known);
-    return RTG_ERR_INVALID;
-  }
-  return fused ? check_stack(what, stackSize) : RTG_OK;
-}
+constexpr unsigned kGatherFlags = RTG_GATHER_JITTER | RTG_GATHER_SKIP_NONFINITE;
 
-// n as the window hash takes it.
-static int check_gather_points(const char* what, size_t n) {
-  if (n <= 0xFFFFFFFFull) return RTG_OK;
-  rtg_set_error("%s: %zu points (at most 2^32 - 1)", what, n);
-  return RTG_ERR_INVALID;
-}
-
-// The rays' n * K (reported before the point count: every n whose product
-// overflows is above 2^32 - 1 too).
-static int check_gather_product(const char* what, size_t n, unsigned K) {
-  if (n <= SIZE_MAX / K) return check_gather_points(what, n);
-  rtg_set_error("%s: %zu points x %u samples overflows size_t", what, n, K);
-  return RTG_ERR_INVALID;
+// The checks the fused forms share, in the order they are reported in.
+static int check_gather(const rtg_hit* hits, const rtg_gather_params* p, const rtg_vec* dirs,
+                        const float* weights, unsigned nDirs, const void* out, int stackSize) {
+  const int rc = check_probes("gather", kGatherFlags, hits, p, dirs, true, weights, nDirs, out);
+  return rc ? rc : check_stack("gather", stackSize);
 }
 
 extern "C" {
 
 int rtg_gather_rays_host(const rtg_hit* hits, size_t n, const rtg_gather_params* params,
                          const rtg_vec* dirs, unsigned nDirs, rtg_ray* raysHost, int nthreads) {
-  rtg_clear_error();
-  int rc = check_gather("gather_rays", hits, params, dirs, false, nullptr, nDirs, raysHost, 0);
-  if (!rc) rc = check_gather_product("gather_rays", n, params->samples);
-  if (rc) return rc;
-  if (n == 0) return RTG_OK;
-  const rtg_gather_params p = *params;
-  host_bands(n, nthreads, [&](size_t i0, size_t i1) {
-    for (size_t i = i0; i < i1; ++i) {
-      for (unsigned k = 0; k < p.samples; ++k) {
-        unsigned w[6];
-        gather_ray(hits, i, k, p, dirs, nDirs, w);
-        memcpy(raysHost + i * p.samples + k, w, sizeof w);
-      }
-    }
-  });
-  return RTG_OK;
+  return probes_host("gather_rays", kGatherFlags, hits, n, params, gather_dir_of, dirs, nDirs,
+                     raysHost, nthreads);
 }
 
 int rtg_gather_rays_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
                            const rtg_gather_params* params, const rtg_vec* dirsDevice,
                            unsigned nDirs, rtg_ray* raysDevice, void* stream) {
-  DeviceGuard deviceGuard;  // the caller's current device is restored on return
-  rtg_clear_error();
-  int device = 0;
-  if (!rtg_context_device(ctx, &device)) {
-    rtg_set_error("gather_rays: no context");
-    return RTG_ERR_INVALID;
-  }
-  int rc = check_gather("gather_rays", hitsDevice, params, dirsDevice, false, nullptr, nDirs,
-                        raysDevice, 0);
-  if (!rc) rc = check_gather_product("gather_rays", n, params->samples);
-  if (rc) return rc;
-  if (n == 0) return RTG_OK;
-  const size_t total = n * params->samples;
-  unsigned blocks;
-  rc = ray_blocks("gather_rays", "batch", total, &blocks);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(gather_rays_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream,
-                     hitsDevice, total, *params, dirsDevice, nDirs, raysDevice);
-  HIP_TRY(hipGetLastError());
-  return RTG_OK;
+  return probes_device("gather_rays", kGatherFlags, ctx, hitsDevice, n, params, gather_dir_of,
+                       dirsDevice, nDirs, raysDevice, stream);
 }
 
 int rtg_gather_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
@@ -213,9 +124,9 @@ int rtg_gather_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
     rtg_set_error("gather: no context/scene");
     return RTG_ERR_INVALID;
   }
-  int rc = check_gather("gather", hitsDevice, params, dirsDevice, true, weightsDevice, nDirs,
-                        outDevice, stackSize);
-  if (!rc) rc = check_gather_points("gather", n);
+  int rc = check_gather(hitsDevice, params, dirsDevice, weightsDevice, nDirs, outDevice,
+                        stackSize);
+  if (!rc) rc = check_probe_points("gather", n);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
   unsigned blocks;
@@ -243,10 +154,10 @@ int rtg_gather_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light*
                     unsigned nDirs, int stackSize, int semantics, rtg_vec* outHost,
                     unsigned short* skippedHost, int walk, int nthreads) {
   rtg_clear_error();
-  int rc = check_gather("gather", hits, params, dirs, true, weights, nDirs, outHost, stackSize);
+  int rc = check_gather(hits, params, dirs, weights, nDirs, outHost, stackSize);
   if (!rc) rc = check_semantics("gather", semantics);
   if (!rc) rc = check_walk("gather", walk);
-  if (!rc) rc = check_gather_points("gather", n);
+  if (!rc) rc = check_probe_points("gather", n);
   if (!rc) rc = check_scene_arrays("gather", spheres, sphNum, lights, lgtNum);
   if (!rc) rc = check_sphere_count("gather", sphNum);
   if (rc) return rc;
@@ -271,33 +182,24 @@ int rtg_gather(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg
                rtg_vec* outHost, unsigned short* skippedHost) {
   DeviceGuard deviceGuard;  // the caller's current device is restored on return
   rtg_clear_error();
-  int rc = check_gather("gather", hits, params, dirs, true, weights, nDirs, outHost, stackSize);
-  if (!rc) rc = check_gather_points("gather", n);
+  int rc = check_gather(hits, params, dirs, weights, nDirs, outHost, stackSize);
+  if (!rc) rc = check_probe_points("gather", n);
   if (!rc) rc = check_scene_arrays("gather", spheres, sphNum, lights, lgtNum);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
-  // one upload: the hit records, then the two tables; one download: the sums,
-  // then the counts
-  const size_t hitBytes = n * sizeof(rtg_hit), dirBytes = (size_t)nDirs * sizeof(rtg_vec),
-               wBytes = (size_t)nDirs * sizeof(float), outBytes = n * sizeof(rtg_vec),
-               skipBytes = skippedHost ? n * sizeof(unsigned short) : 0;
-  std::vector<unsigned char> in(hitBytes + dirBytes + wBytes), back(outBytes + skipBytes);
-  memcpy(in.data(), hits, hitBytes);
-  memcpy(in.data() + hitBytes, dirs, dirBytes);
-  memcpy(in.data() + hitBytes + dirBytes, weights, wBytes);
-  rc = one_shot(device, spheres, sphNum, lights, lgtNum, in.data(), in.size(), back.data(),
-                back.size(), [&](rtg_context* ctx, const void* dIn, void* out) {
-                  const unsigned char* d = (const unsigned char*)dIn;
-                  unsigned char* o = (unsigned char*)out;
-                  return rtg_gather_device(
-                      ctx, (const rtg_hit*)d, n, params, (const rtg_vec*)(d + hitBytes),
-                      (const float*)(d + hitBytes + dirBytes), nDirs, stackSize, (rtg_vec*)o,
-                      skippedHost ? (unsigned short*)(o + outBytes) : nullptr, nullptr);
-                });
-  if (rc) return rc;
-  memcpy(outHost, back.data(), outBytes);
-  if (skipBytes) memcpy(skippedHost, back.data() + outBytes, skipBytes);
-  return RTG_OK;
+  const StageScene scene{spheres, sphNum, lights, lgtNum};
+  return one_shot("gather", device, &scene,
+                  {{n * sizeof(rtg_hit), hits, nullptr},
+                   {(size_t)nDirs * sizeof(rtg_vec), dirs, nullptr},
+                   {(size_t)nDirs * sizeof(float), weights, nullptr},
+                   {n * sizeof(rtg_vec), nullptr, outHost},
+                   {skippedHost ? n * sizeof(unsigned short) : 0, nullptr, skippedHost}},
+                  [&](rtg_context* ctx, void* const* d) {
+                    return rtg_gather_device(ctx, (const rtg_hit*)d[0], n, params,
+                                             (const rtg_vec*)d[1], (const float*)d[2], nDirs,
+                                             stackSize, (rtg_vec*)d[3], (unsigned short*)d[4],
+                                             nullptr);
+                  });
 }
 
 }  // extern "C"

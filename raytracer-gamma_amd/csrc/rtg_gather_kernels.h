@@ -11,6 +11,9 @@
 #include "rtg_raytrace_kernels.h"
 
 static_assert(RTG_GATHER_JITTER == RTG_AO_JITTER, "ao_window reads the jitter bit");
+static_assert(RTG_GATHER_MAX_SAMPLES == RTG_AO_MAX_SAMPLES &&
+                  RTG_GATHER_MAX_DIRS == RTG_AO_MAX_DIRS,
+              "check_probes (rtg_probes.h) states one pair of limits");
 
 namespace rtg {
 

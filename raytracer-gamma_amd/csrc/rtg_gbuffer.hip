@@ -347,7 +347,7 @@ int rtg_gbuffer(int device, const rtg_sphere* spheres, unsigned sphNum, unsigned
   const int rc0 = check_gbuffer_args(spheres, sphNum, width, height, zoom, aliasFactor, dstHost,
                                      &cam);
   if (rc0) return rc0;
-  return one_shot(device, spheres, sphNum, nullptr, 0, nullptr, 0, dstHost,
+  return one_shot("gbuffer", device, {spheres, sphNum, nullptr, 0}, nullptr, 0, dstHost,
                   (size_t)width * height * sizeof(rtg_gbuf_px),
                   [&](rtg_context* ctx, const void*, void* d) {
                     return rtg_gbuffer_device(ctx, width, height, zoom, aliasFactor, 16, 0, 1,

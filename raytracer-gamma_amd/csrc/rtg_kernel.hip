@@ -405,33 +405,46 @@ bool rtg_context_device(const rtg_context* ctx, int* device) {
   return true;
 }
 
-int rtg::one_shot(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
-                  unsigned lgtNum, const void* in, size_t inBytes, void* out, size_t outBytes,
-                  const std::function<int(rtg_context*, const void*, void*)>& launch) {
+int rtg::one_shot(const char* what, int device, const StageScene* scene,
+                  std::initializer_list<StagePart> parts,
+                  const std::function<int(rtg_context*, void* const*)>& launch) {
+  const size_t count = parts.size();
+  const StagePart* part = parts.begin();
+  std::vector<size_t> bytes(count), at(count);
+  for (size_t i = 0; i < count; ++i) bytes[i] = part[i].bytes;
+  const size_t total = stage_layout(bytes.data(), count, at.data());
   rtg_context* ctx = nullptr;
   int rc = rtg_context_create(device, &ctx);
   if (rc) return rc;
-  void *dIn = nullptr, *dOut = nullptr;
-  rc = rtg_context_set_scene(ctx, spheres, sphNum, lights, lgtNum);
-  if (!rc && ((inBytes && hipMalloc(&dIn, inBytes) != hipSuccess) ||
-              hipMalloc(&dOut, outBytes ? outBytes : 4) != hipSuccess)) {
-    rtg_set_error("hipMalloc(%zu + %zu) failed", inBytes, outBytes);
+  if (scene)
+    rc = rtg_context_set_scene(ctx, scene->spheres, scene->sphNum, scene->lights, scene->lgtNum);
+  unsigned char* base = nullptr;
+  if (!rc && (hipSetDevice(device) != hipSuccess ||
+              (total && hipMalloc(&base, total) != hipSuccess))) {
+    rtg_set_error("%s: hipMalloc(%zu) failed", what, total);
     rc = RTG_ERR_NOMEM;
   }
-  if (!rc && inBytes && hipMemcpy(dIn, in, inBytes, hipMemcpyHostToDevice) != hipSuccess) {
-    rtg_set_error("upload of %zu bytes failed", inBytes);
-    rc = RTG_ERR_HIP;
-  }
-  if (!rc) rc = launch(ctx, dIn, dOut);
-  if (!rc) {
-    hipError_t e = hipMemcpy(out, dOut, outBytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      rtg_set_error("kernel/readback failed: %s", hipGetErrorString(e));
+  std::vector<void*> d(count, nullptr);  // an empty part: null
+  for (size_t i = 0; i < count && !rc; ++i) {
+    if (!bytes[i]) continue;
+    d[i] = base + at[i];  // at[i] + bytes[i] <= total
+    if (part[i].from &&
+        hipMemcpy(d[i], part[i].from, bytes[i], hipMemcpyHostToDevice) != hipSuccess) {
+      rtg_set_error("%s: upload of %zu bytes failed", what, bytes[i]);
       rc = RTG_ERR_HIP;
     }
   }
-  (void)hipFree(dIn);
-  (void)hipFree(dOut);
+  if (!rc) rc = launch(ctx, d.data());
+  for (size_t i = 0; i < count && !rc; ++i) {
+    if (!bytes[i] || !part[i].to) continue;
+    // (a blocking copy on the null stream: after the launch's kernels)
+    const hipError_t e = hipMemcpy(part[i].to, d[i], bytes[i], hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+      rtg_set_error("%s: kernel/readback failed: %s", what, hipGetErrorString(e));
+      rc = RTG_ERR_HIP;
+    }
+  }
+  (void)hipFree(base);
   rtg_context_destroy(ctx);
   return rc;
 }
@@ -1151,8 +1164,8 @@ int rtg_render_rows(int device, const rtg_sphere* spheres, unsigned sphNum,
       return RTG_ERR_INVALID;
     }
   if (nRows == 0) return RTG_OK;
-  return one_shot(device, spheres, sphNum, lights, lgtNum, rows, nRows * sizeof(unsigned), dstHost,
-                  (size_t)width * nRows * sizeof(rtg_vec),
+  return one_shot("render_rows", device, {spheres, sphNum, lights, lgtNum}, rows,
+                  nRows * sizeof(unsigned), dstHost, (size_t)width * nRows * sizeof(rtg_vec),
                   [&](rtg_context* ctx, const void* drows, void* d) {
                     return rtg_render_rows_device(ctx, width, height, zoom, aliasFactor, stackSize,
                                                   (const unsigned*)drows, nRows, (rtg_vec*)d,
@@ -1279,7 +1292,7 @@ int rtg_render(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg
   int rc0 = check_render_args(spheres, sphNum, lights, lgtNum, width, height, zoom, aliasFactor,
                               stackSize, dstHost);
   if (rc0) return rc0;
-  return one_shot(device, spheres, sphNum, lights, lgtNum, nullptr, 0, dstHost,
+  return one_shot("render", device, {spheres, sphNum, lights, lgtNum}, nullptr, 0, dstHost,
                   (size_t)width * height * sizeof(rtg_vec),
                   [&](rtg_context* ctx, const void*, void* d) {
                     return rtg_render_device(ctx, width, height, zoom, aliasFactor, stackSize, 16,

@@ -50,8 +50,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <vector>
-
 #include "rtg.h"
 #include "rtg_entry.h"
 #include "rtg_host_scene.h"
@@ -304,19 +302,15 @@ int rtg_matte(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_
   int rc = check_points("matte", "hit", hits, outHost, n);
   if (!rc) rc = check_scene_arrays("matte", spheres, sphNum, lights, lgtNum);
   if (rc || n == 0) return rc;
-  // one download: the masks (8-byte aligned at the head), then the sums
-  const size_t litBytes = litHost ? n * sizeof(unsigned long long) : 0;
-  std::vector<unsigned char> back(litBytes + n * sizeof(rtg_vec));
-  rc = one_shot(device, spheres, sphNum, lights, lgtNum, hits, n * sizeof(rtg_hit), back.data(),
-                back.size(), [&](rtg_context* ctx, const void* in, void* out) {
-                  unsigned char* d = (unsigned char*)out;
-                  return rtg_matte_device(ctx, (const rtg_hit*)in, n, (rtg_vec*)(d + litBytes),
-                                          litHost ? (unsigned long long*)d : nullptr, nullptr);
-                });
-  if (rc) return rc;
-  if (litBytes) memcpy(litHost, back.data(), litBytes);
-  memcpy(outHost, back.data() + litBytes, n * sizeof(rtg_vec));
-  return RTG_OK;
+  const StageScene scene{spheres, sphNum, lights, lgtNum};
+  return one_shot("matte", device, &scene,
+                  {{n * sizeof(rtg_hit), hits, nullptr},
+                   {n * sizeof(rtg_vec), nullptr, outHost},
+                   {litHost ? n * sizeof(unsigned long long) : 0, nullptr, litHost}},
+                  [&](rtg_context* ctx, void* const* d) {
+                    return rtg_matte_device(ctx, (const rtg_hit*)d[0], n, (rtg_vec*)d[1],
+                                            (unsigned long long*)d[2], nullptr);
+                  });
 }
 
 int rtg_contains_device(rtg_context* ctx, const rtg_vec* pointsDevice, size_t n, int* outDevice,
@@ -370,8 +364,8 @@ int rtg_contains(int device, const rtg_sphere* spheres, unsigned sphNum, const r
   int rc = check_points("contains", "point", points, outHost, n);
   if (!rc) rc = check_scene_arrays("contains", spheres, sphNum);
   if (rc || n == 0) return rc;
-  return one_shot(device, spheres, sphNum, nullptr, 0, points, n * sizeof(rtg_vec), outHost,
-                  n * sizeof(int), [&](rtg_context* ctx, const void* in, void* out) {
+  return one_shot("contains", device, {spheres, sphNum, nullptr, 0}, points, n * sizeof(rtg_vec),
+                  outHost, n * sizeof(int), [&](rtg_context* ctx, const void* in, void* out) {
                     return rtg_contains_device(ctx, (const rtg_vec*)in, n, (int*)out, nullptr);
                   });
 }

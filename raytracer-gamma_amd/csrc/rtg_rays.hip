@@ -491,8 +491,8 @@ int rtg_intersect(int device, const rtg_sphere* spheres, unsigned sphNum, const 
   const int rc = check_ray_args("intersect", spheres, sphNum, rays, hitsHost);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
-  return one_shot(device, spheres, sphNum, nullptr, 0, rays, n * sizeof(rtg_ray), hitsHost,
-                  n * sizeof(rtg_hit), [&](rtg_context* ctx, const void* in, void* out) {
+  return one_shot("intersect", device, {spheres, sphNum, nullptr, 0}, rays, n * sizeof(rtg_ray),
+                  hitsHost, n * sizeof(rtg_hit), [&](rtg_context* ctx, const void* in, void* out) {
                     return rtg_intersect_device(ctx, (const rtg_ray*)in, n, (rtg_hit*)out, nullptr);
                   });
 }
@@ -504,7 +504,8 @@ int rtg_visible(int device, const rtg_sphere* spheres, unsigned sphNum, const rt
   const int rc = check_ray_args("visible", spheres, sphNum, segs, outHost);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
-  return one_shot(device, spheres, sphNum, nullptr, 0, segs, n * sizeof(rtg_segment), outHost, n,
+  return one_shot("visible", device, {spheres, sphNum, nullptr, 0}, segs, n * sizeof(rtg_segment),
+                  outHost, n,
                   [&](rtg_context* ctx, const void* in, void* out) {
                     return rtg_visible_device(ctx, (const rtg_segment*)in, n, (unsigned char*)out,
                                               nullptr);

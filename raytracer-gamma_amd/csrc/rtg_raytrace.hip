@@ -238,8 +238,9 @@ int rtg_raytrace(int device, const rtg_sphere* spheres, unsigned sphNum, const r
   const int rc = check_raytrace_args(spheres, sphNum, lights, lgtNum, rays, dstHost, stackSize);
   if (rc) return rc;
   if (n == 0) return RTG_OK;
-  return one_shot(device, spheres, sphNum, lights, lgtNum, rays, n * sizeof(rtg_ray), dstHost,
-                  n * sizeof(rtg_vec), [&](rtg_context* ctx, const void* in, void* out) {
+  return one_shot("raytrace", device, {spheres, sphNum, lights, lgtNum}, rays,
+                  n * sizeof(rtg_ray), dstHost, n * sizeof(rtg_vec),
+                  [&](rtg_context* ctx, const void* in, void* out) {
                     return rtg_raytrace_device(ctx, (const rtg_ray*)in, n, stackSize,
                                                (rtg_vec*)out, nullptr);
                   });

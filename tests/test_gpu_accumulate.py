@@ -7,15 +7,14 @@ must stay.
 
   1. accumulate_device == accumulate_host (outAcc, outLen, outM2) on every frame,
      previous pose, signal and parameter set of accumgen;
-  2. both wave shapes, forced by RTG_ACCUM_FORM, on the 67 x 35 frame;
-  3. camera_project_device == camera_project_host on the records' points, the
+  2. camera_project_device == camera_project_host on the records' points, the
      planted NaN point and the eye itself among them;
-  4. the one-shot forms;
-  5. a launch on a stream of its own between two renders of the context;
-  6. the device chain camera_rays -> intersect -> ao -> accumulate over four
+  3. the one-shot forms;
+  4. a launch on a stream of its own between two renders of the context;
+  5. the device chain camera_rays -> intersect -> ao -> accumulate over four
      poses and seeds, then the filter, against the host chain;
-  7. rtg_main --ao-history and --gather-history, with and without the filter;
-  8. the device entry point's argument checks.
+  6. rtg_main --ao-history and --gather-history, with and without the filter;
+  7. the device entry point's argument checks.
 """
 from __future__ import annotations
 
@@ -127,19 +126,7 @@ def test_device_equals_host(R, torch_cuda, ctx, name, kind):
     _check_cases(torch_cuda, R, ctx, name, kind, FRAMES)
 
 
-# ---- 2. both wave shapes ----
-
-@pytest.mark.parametrize("form", ["tile", "row"])
-def test_forced_form_equals_host(R, torch_cuda, ctx, form, monkeypatch):
-    """RTG_ACCUM_FORM is read by every call: `tile` makes a wave an 8 x 8 tile,
-    `row` 64 pixels of a row."""
-    monkeypatch.setenv("RTG_ACCUM_FORM", form)
-    for name in SCENES:
-        for kind in SIGNALS:
-            _check_cases(torch_cuda, R, ctx, name, kind, [FULL])
-
-
-# ---- 3. the projection ----
+# ---- 2. the projection ----
 
 @pytest.mark.parametrize("name", SCENES)
 def test_project_device_equals_host(R, torch_cuda, ctx, name):
@@ -166,14 +153,15 @@ def test_project_device_equals_host(R, torch_cuda, ctx, name):
     ctx.camera_project_device(A.pose(name, "pan"), 8, 8, 0, 0, 0)
 
 
-# ---- 4. the one-shot forms ----
+# ---- 3. the one-shot forms ----
 
 def test_one_shot(R, torch_cuda):
     for name, (W, H), kind, pk, st in (("reference", FULL, "count", "pan", A.SETS[0]),
                                        ("c5", FULL, "rgb", "roll", A.SETS[1]),
                                        (12, (33, 17), "gray", "dolly", A.SETS[6]),
                                        (12, (1, 1), "rgb", "same", A.SETS[2]),
-                                       ("c5", (8, 8), "rgb", "same", A.SETS[13])):
+                                       ("c5", (8, 8), "rgb", "same", A.SETS[13]),
+                                       ("c5", (8, 8), "rgb", "same", A.SETS[14])):
         got = R.accumulate(G.guides(name, W, H), W, H, A.params(R, name, kind, st),
                            G.signal(name, W, H, kind), A.prev(name, W, H, pk, kind, st),
                            zoom=A.ZOOM, m2=st[4])
@@ -189,7 +177,7 @@ def test_one_shot(R, torch_cuda):
     assert got.shape == (len(pts), 3) and got.view(np.uint32).tobytes() == want.view(np.uint32).tobytes()
 
 
-# ---- 5. a stream of its own, between two renders ----
+# ---- 4. a stream of its own, between two renders ----
 
 def test_own_stream_between_renders(R, torch_cuda):
     torch = torch_cuda
@@ -217,7 +205,7 @@ def test_own_stream_between_renders(R, torch_cuda):
         c.close()
 
 
-# ---- 6. the device chain ----
+# ---- 5. the device chain ----
 
 def _path(name, frames):
     eye, target = (np.array(v, np.float64) for v in G.POSES[name])
@@ -281,7 +269,7 @@ def test_device_chain_equals_host_chain(R, torch_cuda):
         c.close()
 
 
-# ---- 7. the driver ----
+# ---- 6. the driver ----
 
 def _pgm_of(v, K, W, H):
     x = F(255) * v.reshape(-1).astype(F) / F(K)
@@ -364,7 +352,7 @@ def test_host_driver_history_options(R, torch_cuda, tmp_path):
     assert "--ao-history" in r.stdout and "--gather-history" in r.stdout
 
 
-# ---- 8. entry-point errors ----
+# ---- 7. entry-point errors ----
 
 def test_device_entry_point_errors(R, torch_cuda, ctx):
     torch = torch_cuda

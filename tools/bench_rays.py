@@ -706,8 +706,7 @@ def accumulate_rows(args, stream):
     of the aa = 1 primary hits, 3840 x 2160 on C3 and 1920 x 1080 on C5, blended
     onto the state of a previous pose a small pan away and of one a roll away
     (that pose's own records and signal, every length 3).  Round by round in one
-    process: the call as it chooses its wave shape, the call with each shape
-    forced (RTG_ACCUM_FORM), and a torch chain of the same arithmetic.
+    process: the call, and a torch chain of the same arithmetic.
     Reported, not gated: every time, and the distance from the streaming floor
     (the current and the previous records, src, prevAcc, prevLen, outAcc and
     outLen once each at 6 TB/s; next to it the same with the previous state
@@ -715,7 +714,6 @@ def accumulate_rows(args, stream):
     background moves).  Gated: the call's lengths are the chain's and
     its values agree to 1e-4 relative on finite pixels."""
     K, nlog, max_history = 16, 3, 64
-    FORMS = ("tile", "row")
     flags = R.ACCUM_SAME_ID | R.ACCUM_NORMAL | R.ACCUM_PLANE
     table = torch.from_numpy(R.ao_directions(K)).cuda()
     wt = torch.full((K,), 1.0 / K, dtype=torch.float32, device="cuda")
@@ -784,19 +782,13 @@ def accumulate_rows(args, stream):
             p_len = torch.full((n,), 3, dtype=torch.int16, device="cuda")
             prev = (cam, p_hits.data_ptr(), p_acc.data_ptr(), p_len.data_ptr())
 
-            def call(form):
-                if form:
-                    os.environ["RTG_ACCUM_FORM"] = form
-                else:
-                    os.environ.pop("RTG_ACCUM_FORM", None)
+            def call():
                 ctx.accumulate_device(hits.data_ptr(), W, H, p, src.data_ptr(), o_acc.data_ptr(),
                                       o_len.data_ptr(), prev, stream=stream)
 
-            m = measure([lambda: call("")] + [(lambda f=f: call(f)) for f in FORMS], args.rounds,
-                        window_ms=100.0,
-                        names=[f"accumulate {name} {move} {f}" for f in ("default",) + FORMS])
-            os.environ.pop("RTG_ACCUM_FORM", None)
-            call("")
+            m = measure([call], args.rounds, window_ms=100.0,
+                        names=[f"accumulate {name} {move} default"])
+            call()
             torch.cuda.synchronize()
             got, got_len = o_acc.clone(), o_len.to(torch.int64) & 0xFFFF
             tp = (pv[0], pv[1], pv[2], pv[3], p_len.to(torch.int64).reshape(H, W))
@@ -815,9 +807,8 @@ def accumulate_rows(args, stream):
             ok = ok and agree
             real = hits[:, 0] >= 0
             row[move] = {
-                "default": m[0], "forms": dict(zip(FORMS, m[1:])),
+                "default": m[0],
                 "default_over_floor": round(m[0]["ms_median"] / floor, 2),
-                "forms_over_floor": {f: round(x["ms_median"] / floor, 2) for f, x in zip(FORMS, m[1:])},
                 "torch_chain": tm, "torch_over_accumulate": round(tm["ms_median"] / m[0]["ms_median"], 2),
                 "found_share_of_hit_pixels": round(float(((got_len == 4) & real).sum() / real.sum()), 4),
                 "lengths_equal": same_len, "largest_relative_difference": worst,
