@@ -160,8 +160,12 @@ int rtg_multi_set_gather(rtg_multi* mg, int mode);
  * such a stream (or the device) before destroying it. */
 typedef struct rtg_context rtg_context;
 int rtg_context_create(int device, rtg_context** out);
+/* Waits for the context's pending work on every stream before it frees
+ * anything: a caller may destroy a context right behind its launches. */
 int rtg_context_destroy(rtg_context* ctx);
-/* Copies the scene into device memory (kept until the next call / destroy). */
+/* Copies the scene into device memory (kept until the next call / destroy).
+ * Waits for the context's pending work on every stream before it frees the
+ * old scene: launches already enqueued finish on the scene they were given. */
 int rtg_context_set_scene(rtg_context* ctx, const rtg_sphere* spheres, unsigned sphNum,
                           const rtg_light* lights, unsigned lgtNum);
 
@@ -432,7 +436,9 @@ int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum,
  * owned by the call until it has finished on the stream.  The sort is a radix
  * sort by 8-bit digits in tiles of RTG_ORDER_TILE_RAYS rays, with a scan over
  * RTG_ORDER_SCAN_TILES tiles a step; a digit position on which every key
- * agrees costs nothing.  n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID
+ * agrees costs nothing.  The keys are made by at most RTG_ORDER_KEY_GRID
+ * workgroups: a batch of more tiles gives each several, tile-strided.  n == 0
+ * is RTG_OK with no launch.  RTG_ERR_INVALID
  * with a message, before any GPU call, for a null ray, order or scratch
  * buffer, an unknown kind, n > 2^32 - 1, a scratch that is too small or not
  * 16-byte aligned, or a context without a scene.
@@ -451,6 +457,7 @@ int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum,
 #define RTG_ORDER_SEGMENTS 1  /* the batch holds rtg_segment records */
 #define RTG_ORDER_TILE_RAYS 1024
 #define RTG_ORDER_SCAN_TILES 256
+#define RTG_ORDER_KEY_GRID 2048
 int rtg_ray_order_scratch(size_t n, size_t* bytes);
 int rtg_ray_order_device(rtg_context* ctx, const void* raysDevice, size_t n, int kind,
                          unsigned* orderDevice, unsigned long long* keysDevice /* may be NULL */,

@@ -382,6 +382,9 @@ static const SceneTable kSceneTables[] = {
 #undef RTG_TABLE_U
 
 static void free_scene(rtg_context* c) {
+  // launches of any stream may still read the tables (rtg.h: set_scene and
+  // destroy wait for the context's pending work); said here, not left to hipFree
+  if (c->hasScene) (void)hipDeviceSynchronize();
   for (const SceneTable& e : kSceneTables) (void)hipFree(e.get(c->scene));
   c->scene = SceneTables{};
   c->hasScene = false;

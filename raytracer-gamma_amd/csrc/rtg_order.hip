@@ -76,7 +76,7 @@ constexpr int kPasses = (kKeyBits + 7) / 8;     // digit positions of the used b
 constexpr int kRounds = RTG_ORDER_TILE_RAYS / 64;
 constexpr unsigned kTile = RTG_ORDER_TILE_RAYS;  // keys per workgroup
 constexpr unsigned kScanTiles = RTG_ORDER_SCAN_TILES;  // tiles per scan step: 64 lanes x 4
-constexpr unsigned kKeyGrid = 2048;             // workgroups of the keys kernel (tile-strided)
+constexpr unsigned kKeyGrid = RTG_ORDER_KEY_GRID;  // workgroups of the keys kernel (tile-strided)
 static_assert(kTile == 64u * kRounds && kScanTiles == 256u, "one wave: 64 lanes");
 // plan words per pass: {skipped, executed passes before it, is the last executed}
 constexpr int kPlanWords = 4;

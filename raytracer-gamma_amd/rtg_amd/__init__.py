@@ -577,10 +577,12 @@ def raytrace_host(spheres, lights, rays, stack_size: int = 6, semantics: int = 0
 
 # The ray order (include/rtg.h): RTG_ORDER_RAYS / RTG_ORDER_SEGMENTS, and the
 # device sort's geometry: rays per tile (RTG_ORDER_TILE_RAYS) and tiles per
-# scan step (RTG_ORDER_SCAN_TILES).
+# scan step (RTG_ORDER_SCAN_TILES), and the keys kernel's largest grid
+# (RTG_ORDER_KEY_GRID workgroups: a batch of more tiles strides over them).
 ORDER_RAYS, ORDER_SEGMENTS = 0, 1
 ORDER_TILE_RAYS = 1024
 ORDER_SCAN_TILES = 256
+ORDER_KEY_GRID = 2048
 ORDER_ORIGIN_BITS, ORDER_DIR_BITS = 10, 10  # key bits per origin axis / direction axis
 ORDER_KEY_BITS = 3 * ORDER_ORIGIN_BITS + 2 * ORDER_DIR_BITS  # the key's used bits
 

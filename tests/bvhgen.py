@@ -585,13 +585,107 @@ def view_table(R, name):
 
 
 @functools.lru_cache(maxsize=None)
-def views0(name):
+def views0(name, sem=0):
     import rtg_amd as R
     sph, lg = _scene(name)
     out = R.render_views_host(sph, lg, view_table(R, name), VW, VH, alias_factor=2.0,
-                              stack_size=trace_stack(name), walk=0, threads=THREADS)
+                              stack_size=trace_stack(name), semantics=sem, walk=0,
+                              threads=THREADS)
     out.setflags(write=False)
     return out
+
+
+# The gather over hits(name): K = 7 of gathergen.dirs(8) (a zero, a NaN and a
+# x1000 direction among them), plain finite weights (gathergen.weights plants a
+# NaN weight, which turns most sums into NaN), plain and with both flags.
+GATHER_K, GATHER_DIRS = 7, 8
+GATHER_FLAGS = (0, 1 | 2)  # RTG_GATHER_JITTER | RTG_GATHER_SKIP_NONFINITE
+GATHER_SKIP = 2
+
+
+def gather_weights():
+    w = np.full(GATHER_DIRS, 1.0 / GATHER_DIRS, F)
+    w.setflags(write=False)
+    return w
+
+
+def gather_params(R, flags):
+    import aogen
+    return R.gather_params(GATHER_K, aogen.BIAS, aogen.SEED, flags)
+
+
+@functools.lru_cache(maxsize=None)
+def gather0(name, flags, sem=0):
+    """(sums, skip counts) of hits(name) by the plain loops."""
+    import gathergen
+    import rtg_amd as R
+    sph, lg = _scene(name)
+    out, skp = R.gather_host(sph, lg, hits(name), gathergen.dirs(GATHER_DIRS), gather_weights(),
+                             gather_params(R, flags), stack_size=trace_stack(name), semantics=sem,
+                             walk=0, threads=THREADS, skipped=True)
+    out.setflags(write=False)
+    skp.setflags(write=False)
+    return out, skp
+
+
+# The fold of views0(name)'s four frames: two groups of two views (the NaN pose
+# is the second view of the second group), K = 4 seeded weights a texel.
+FOLD_G, FOLD_K = 2, 4
+FOLD_SKIP = 1  # RTG_FOLD_SKIP_NONFINITE
+NAN_GROUP = 1
+
+
+@functools.lru_cache(maxsize=None)
+def fold_weights():
+    from test_views_fold_host import random_weights
+    w = random_weights(np.random.default_rng(6500), FOLD_G, VW, VH, FOLD_K)
+    w.setflags(write=False)
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def fold0(name, flags, sem=0):
+    """(coefficients (2, FOLD_K, 3) float32, skip counts) of views_fold_host
+    over views0(name, sem)."""
+    import rtg_amd as R
+    out, cnt = R.views_fold_host(views0(name, sem), fold_weights(),
+                                 R.fold_params(FOLD_G, FOLD_K, flags), threads=THREADS,
+                                 skipped=True)
+    out.setflags(write=False)
+    cnt.setflags(write=False)
+    return out, cnt
+
+
+def gather_shares(name):
+    """Of the points with id >= 0: the share with a finite non-zero sum with
+    flags 0, the same with both flags, and the points with a skipped probe."""
+    real = hits(name)["id"] >= 0
+
+    def share(s):
+        return float((np.isfinite(s).all(1) & (s != 0).any(1))[real].mean())
+    plain, none = gather0(name, GATHER_FLAGS[0])
+    both, skp = gather0(name, GATHER_FLAGS[1])
+    assert not none.any()  # no flag: no count
+    return share(plain), share(both), int((skp[real] > 0).sum())
+
+
+def check_gather_fold_non_vacuous(name):
+    """On the REFERENCE answers: at least 5 % of the points with a finite
+    non-zero sum plain and 15 % with the skip flag; coefficients that are not
+    all zero; without the flag no count, with it each group's count is the
+    number of its pixels with a non-finite word, counted here in numpy.  (The
+    NaN pose's rays meet nothing, so its own frame is black, not NaN: the
+    non-finite pixels of a group are the scene's, and the deep scenes,
+    wide_deep and many_lights have none in the NaN pose's group.  The counts
+    across the scenes: test_bvh_shapes_host.py.)"""
+    from test_views_fold_host import nonfinite_pixels
+    plain, both, _ = gather_shares(name)
+    assert plain >= 0.05 and both >= 0.15, (name, plain, both)
+    bad = nonfinite_pixels(views0(name)).reshape(2, -1).sum(1)
+    for flags in (0, FOLD_SKIP):
+        out, cnt = fold0(name, flags)
+        assert (out.view(np.uint32) << 1).any(), (name, flags, "the coefficients are all zero")
+        assert (cnt == (bad if flags else 0)).all(), (name, flags, cnt, bad)
 
 
 # ---- non-vacuity: conditions on the REFERENCE answers ----

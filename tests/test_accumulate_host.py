@@ -249,11 +249,19 @@ def test_entry_point_errors(rtg):
     W, H = 33, 17
     n = W * H
     L = R.lib()
-    h = np.ascontiguousarray(G.guides("reference", W, H))
-    ph = np.ascontiguousarray(A.prev_hits("reference", W, H, "pan"))
+
+    def roomy(a):
+        """`a` as the first half of an allocation twice its size: a range that
+        starts inside it and runs past its end (the straddling cases below)
+        lies in memory of its own, not in whichever argument the heap put next
+        (which named that argument in the message, on some runs)."""
+        return np.concatenate([a, np.zeros_like(a)])[:len(a)]
+
+    h = roomy(np.ascontiguousarray(G.guides("reference", W, H)))
+    ph = roomy(np.ascontiguousarray(A.prev_hits("reference", W, H, "pan")))
     src = np.zeros(n, F)
-    pacc, pm2, plen = np.zeros(n, F), np.zeros(n, F), np.ones(n, np.uint16)
-    acc, m2, ln = np.full(n, 7, F), np.full(n, 7, F), np.full(n, 7, np.uint16)
+    pacc, pm2, plen = roomy(np.zeros(n, F)), np.zeros(n, F), np.ones(n, np.uint16)
+    acc, m2, ln = np.full(n, 7, F), roomy(np.full(n, 7, F)), np.full(n, 7, np.uint16)
     cam = np.ascontiguousarray(A.pose("reference", "pan"))
     ok = R.accumulate_params(R.FILTER_GRAY, A.ALL, 1.0, 3, 3)
     P = lambda a: None if a is None else a.ctypes.data  # noqa: E731

@@ -8,8 +8,9 @@ lattices and 256 lights.  No GPU:
      and the tile kernel's variants) equals the oracle's frame, and BvhStack
      never holds more than 3 * depth + 3 of its 64 entries;
   3. the batch and point queries' kernel path (walk 1) equals the plain loops
-     (walk 0), byte for byte;
-  4. the posed camera's walk 1 equals walk 0, from outside and from within.
+     (walk 0), byte for byte, the gather with its skip counts among them;
+  4. the posed camera's walk 1 equals walk 0, from outside and from within,
+     and so do the views folded into coefficients.
 
 test_gpu_bvh_shapes.py holds the device to the same references.
 """
@@ -182,6 +183,40 @@ def test_point_queries_walk1_equals_walk0(rtg, name):
     assert (want >= 0).any() and (want < 0).any()
 
 
+@pytest.mark.parametrize("name", G.NAMES)
+def test_gather_walk1_equals_walk0(rtg, name):
+    """The gather's kernel path over the packed tables against the plain
+    loops, plain and with jitter and the skip flag, the skip counts included."""
+    import gathergen
+    sph, lg = G.scene(name)
+    G.check_gather_fold_non_vacuous(name)
+    for sem in ((0, 1) if name in ("mirror_x", "deep19") else (0,)):
+        for flags in G.GATHER_FLAGS:
+            want, want_skp = G.gather0(name, flags, sem)
+            got, skp = rtg.gather_host(sph, lg, G.hits(name), gathergen.dirs(G.GATHER_DIRS),
+                                       G.gather_weights(), G.gather_params(rtg, flags),
+                                       stack_size=G.trace_stack(name), semantics=sem, walk=1,
+                                       threads=THREADS, skipped=True)
+            assert gathergen.same_words(got, want) is None, (sem, flags,
+                                                             gathergen.same_words(got, want))
+            assert skp.tobytes() == want_skp.tobytes(), (sem, flags)
+            assert bool(want_skp.any()) <= bool(flags & G.GATHER_SKIP)
+
+
+def test_gather_skips_on_most_scenes(rtg):
+    """With the skip flag a probe is left out on at least ten of the thirteen
+    scenes (measured: all but wide_deep), and the shares of points with a
+    finite non-zero sum are at least 5 % plain and 15 % with the flag
+    (measured minima: 11 % on lattice_overlap, 20 % on deep19)."""
+    shares = {name: G.gather_shares(name) for name in G.NAMES}
+    assert len(G.NAMES) == 13
+    assert sum(s[2] > 0 for s in shares.values()) >= 10, shares
+    assert min(s[0] for s in shares.values()) >= 0.05, shares
+    assert min(s[1] for s in shares.values()) >= 0.15, shares
+    folds = [int(G.fold0(name, G.FOLD_SKIP)[1].sum()) for name in G.NAMES]
+    assert sum(c > 0 for c in folds) >= 10, folds
+
+
 # ---- 4. the posed camera ----
 
 @pytest.mark.parametrize("name", G.NAMES)
@@ -202,3 +237,21 @@ def test_posed_camera_walk1_equals_walk0(rtg, name):
                                 stack_size=s, walk=1, threads=THREADS)
     assert bits_equal(got, want), first_mismatch(got, want)
     assert want[3].tobytes() != want[0].tobytes()  # the NaN pose: not the outside pose's frame
+
+
+@pytest.mark.parametrize("name", G.NAMES)
+def test_views_fold_walk1_equals_walk0(rtg, name):
+    """render_views_fold_host over the kernel's path (walk 1) against the fold
+    of the plain loops' frames, with and without the skip flag, counts included."""
+    sph, lg = G.scene(name)
+    G.check_gather_fold_non_vacuous(name)
+    for sem in ((0, 1) if name in ("mirror_x", "deep19") else (0,)):
+        for flags in (0, G.FOLD_SKIP):
+            want, want_cnt = G.fold0(name, flags, sem)
+            got, cnt = rtg.render_views_fold_host(
+                sph, lg, G.view_table(rtg, name), G.VW, G.VH, G.fold_weights(),
+                rtg.fold_params(G.FOLD_G, G.FOLD_K, flags), alias_factor=2.0,
+                stack_size=G.trace_stack(name), semantics=sem, walk=1, threads=THREADS,
+                skipped=True)
+            assert got.view(np.uint32).tobytes() == want.view(np.uint32).tobytes(), (sem, flags)
+            assert (cnt == want_cnt).all(), (sem, flags, cnt, want_cnt)

@@ -3,7 +3,8 @@ at the depth limit, the finite scenes build_bvh refuses, exact ties across
 subtrees, lattices and 256 lights, through every device entry point that walks
 the BVH, against the references test_bvh_shapes_host.py pins on the CPU (the
 oracle's frames, the plain loops' hits, visibilities, colours, counts, sums and
-indices, the host forms of the G-buffer and the posed views), bit for bit.
+indices, the host forms of the G-buffer and the posed views, the gather's sums
+and the views' folded coefficients with their skip counts), bit for bit.
 
 One context per scene, kept for the module.  Every destination is pre-filled
 and PAD records longer than its result; the tail must stay.  The batches run
@@ -20,13 +21,18 @@ import pytest
 
 import aogen
 import bvhgen as G
+import gathergen
 from conftest import bits_equal, first_mismatch
 from raygen import diff_hits
 from test_gpu_ao import _counts
+from test_gpu_gather import FILL16, FILL32
+from test_gpu_gather import _same as _same_gather
 from test_gpu_hostile import _check_frame, _frame, _sharded, _words
 from test_gpu_matte import _contains, _dev, _matte
-from test_gpu_order import _run, _same_as_host, _stream
+from test_gpu_order import PAD, _run, _same_as_host, _stream
 from test_gpu_views import _views
+from test_gpu_views_fold import _fold, _fused
+from test_gpu_views_fold import _same as _same_fold
 
 pytestmark = pytest.mark.gpu
 
@@ -183,3 +189,85 @@ def test_point_queries(R, torch_cuda, contexts, name):
     want = G.contains0(name)
     bad = np.flatnonzero(got != want)
     assert not len(bad), f"{len(bad)} points differ, first {bad[0]}: {pts[bad[0]]}"
+
+
+# ---- the gather and the views folded into coefficients ----
+
+def _with_semantics(R, ctx, name, body):
+    """body(sem) under the scene's semantics in turn; the context is left with
+    the CPU's."""
+    for sem in ((0, 1) if name in OPENCL else (0,)):
+        ctx.set_semantics(sem)
+        try:
+            body(sem)
+        finally:
+            ctx.set_semantics(R.Context.SEMANTICS_CPU)
+
+
+def _gathers(torch, ctx, d_hits, n, params, d_dirs, d_w, nd, S):
+    """One fused call per params record, each on a stream of its own and all in
+    flight at once: [(sums, skipped), ...].  (A launch over many_lights takes
+    0.7 s whether it holds 64 points or 600: a wave's 7 traces a lane under 256
+    lights, one after the other.  Side by side the launches cost one.)"""
+    out = [(torch.full(((n + PAD) * 3,), FILL32, dtype=torch.int32, device="cuda"),
+            torch.full((n + PAD,), FILL16, dtype=torch.int16, device="cuda")) for _ in params]
+    own = [torch.cuda.Stream() for _ in params]
+    torch.cuda.synchronize()  # the fills, before a launch on another stream
+    for p, (dst, skp), st in zip(params, out, own):
+        ctx.gather_device(d_hits.data_ptr(), n, p, d_dirs.data_ptr(), d_w.data_ptr(), nd,
+                          dst.data_ptr(), skipped_ptr=skp.data_ptr(), stack_size=S,
+                          stream=st.cuda_stream)
+    torch.cuda.synchronize()
+    res = []
+    for dst, skp in out:
+        sums, cnt = dst.cpu().numpy(), skp.cpu().numpy().view(np.uint16)
+        assert (sums[n * 3:] == FILL32).all(), "sums past the batch were written"
+        assert (cnt[n:] == FILL16).all(), "counts past the batch were written"
+        res.append((sums[:n * 3].view(np.float32).reshape(n, 3), cnt[:n]))
+    return res
+
+
+@pytest.mark.parametrize("name", G.NAMES)
+def test_gather(R, torch_cuda, contexts, name):
+    """gather_kernel<S, kBvh, kCL> on the structured scenes: 64 unrelated
+    points a wave, K = 7 traces each, lanes with id < 0 and past n stepping
+    round the trace; sums and skip counts word for word."""
+    torch = torch_cuda
+    G.check_gather_fold_non_vacuous(name)
+    ctx = contexts(name)
+    h = G.hits(name)
+    n = len(h)
+    assert n % 64 and (h["id"] < 0).any() and (h["id"] >= 0).any()  # a ragged last wave
+    d_hits, d_dirs = _dev(torch, h), _dev(torch, gathergen.dirs(G.GATHER_DIRS))
+    d_w = _dev(torch, G.gather_weights())
+
+    def body(sem):
+        got = _gathers(torch, ctx, d_hits, n, [G.gather_params(R, f) for f in G.GATHER_FLAGS],
+                       d_dirs, d_w, G.GATHER_DIRS, G.trace_stack(name))
+        for flags, (sums, skp) in zip(G.GATHER_FLAGS, got):
+            want, want_skp = G.gather0(name, flags, sem)
+            _same_gather(sums, want, skp, want_skp, (sem, flags))
+    _with_semantics(R, ctx, name, body)
+
+
+@pytest.mark.parametrize("name", G.NAMES)
+def test_views_fold(R, torch_cuda, contexts, name):
+    """views_fold_kernel on the structured scenes: the fused call equals the
+    fold of the plain loops' frames, and the device fold of the frames
+    render_views writes (test_views holds those to the same frames)."""
+    torch = torch_cuda
+    G.check_gather_fold_non_vacuous(name)
+    ctx = contexts(name)
+    table, w, s = G.view_table(R, name), G.fold_weights(), G.trace_stack(name)
+
+    def body(sem):
+        frames = _views(torch, ctx, table, G.VW, G.VH, -4.0, 2.0, s)
+        for flags in (0, G.FOLD_SKIP):
+            want, want_cnt = G.fold0(name, flags, sem)
+            want = (want.view(np.uint32), want_cnt)
+            got = _fused(torch, R, ctx, table, G.VW, G.VH, -4.0, 2.0, s, w, G.FOLD_G, G.FOLD_K,
+                         flags)
+            _same_fold(got, want, ("fused", sem, flags))
+            unfused = _fold(torch, R, ctx, frames, w, G.FOLD_G, G.FOLD_K, flags)
+            _same_fold(unfused, want, ("render_views + views_fold", sem, flags))
+    _with_semantics(R, ctx, name, body)

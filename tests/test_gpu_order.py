@@ -94,6 +94,28 @@ def _one_digit_batch(n):
 
 # ---- 1. device == host ----
 
+def _past_the_key_grid(R, torch, ctx, sph):
+    """Two batches of ORDER_KEY_GRID + 2 tiles, the last ragged: the keys
+    kernel's workgroups 0 and 1 take a second tile each and add both to one LDS
+    histogram.  Random rays (every pass runs), then shuffled primary rays
+    tiled to that length (one origin: the skipped-pass plan at that tile
+    count)."""
+    T, G = R.ORDER_TILE_RAYS, R.ORDER_KEY_GRID
+    n = G * T + T + 1
+    assert -(-n // T) == G + 2 and n % T == 1 and n < 1 << 32
+    rays = raygen.inside(np.random.default_rng(42), sph, n)
+    order, keys = _same_as_host(R, torch, ctx, sph, rays)
+    check_order(order, keys, n)
+    assert sum(_digits(keys)) >= 5
+    prim = raygen.primary(64, 48)
+    prim = prim[np.random.default_rng(8).permutation(len(prim))]
+    prim = np.ascontiguousarray(np.tile(prim, (-(-n // len(prim)), 1))[:n])
+    order, keys = _same_as_host(R, torch, ctx, sph, prim)
+    check_order(order, keys, n)
+    dpos = -(-2 * R.ORDER_DIR_BITS // 8)
+    assert _digits(keys) == [True] * dpos + [False] * (len(_digits(keys)) - dpos)
+
+
 @pytest.mark.parametrize("name", ["reference", 200, "c5"])
 def test_device_order_equals_host(R, torch_cuda, name):
     """Ragged waves, one tile -1 / 0 / +1, and one batch with more tiles than
@@ -114,6 +136,8 @@ def test_device_order_equals_host(R, torch_cuda, name):
         check_order(order, keys, big)
         segs = raygen.segments(np.random.default_rng(41), sph, 4097)
         _same_as_host(R, torch_cuda, ctx, sph, segs, kind=R.ORDER_SEGMENTS)
+        if name == 200:
+            _past_the_key_grid(R, torch_cuda, ctx, sph)
     finally:
         ctx.close()
 

@@ -157,6 +157,14 @@ def test_argument_errors_and_scratch(rtg):
     # 256-bin table of every tile, and is refused past 2^32 - 1 rays
     T = rtg.ORDER_TILE_RAYS
     assert T % 64 == 0 and rtg.ORDER_SCAN_TILES == 256
+    # the binding's copies of the sort's geometry are the header's
+    import os
+    import re
+    from conftest import ROOT
+    header = open(os.path.join(ROOT, "include", "rtg.h")).read()
+    for name in ("TILE_RAYS", "SCAN_TILES", "KEY_GRID"):
+        value = re.search(rf"^#define RTG_ORDER_{name} (\d+)$", header, re.M)
+        assert value and int(value.group(1)) == getattr(rtg, f"ORDER_{name}"), name
     prev = rtg.ray_order_scratch(0)
     for n in (1, T, T + 1, 100 * T, 300000):
         b = rtg.ray_order_scratch(n)
