@@ -40,6 +40,8 @@
  *     its surfaces, guided by the frame's hit records)    rtg_filter_scratch
  *   (such a signal carried from frame to frame while     rtg_accumulate[_device|_host],
  *     the camera moves: reprojection by the hit points)   rtg_camera_project[_device|_host]
+ *   (a variance per pixel from the carried moments, and  rtg_variance[_device|_host],
+ *     the filter guided by it: edges inside a surface)    rtg_svgf[_device|_host], rtg_svgf_scratch
  *   primaryContainer for a caller's own points         rtg_contains[_device|_host]
  *     raytracer.h:245-270
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
@@ -1112,9 +1114,10 @@ int rtg_gather_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light*
  * overlapping src's or the scratch's (addresses compared as numbers, on the
  * host and on the device alike).
  *
- * Out of scope: a value- or variance-driven term (SVGF), rtg_gbuf_px records
- * as guides, per-pass parameters, filtering ray batches that are not a frame,
- * views and multi-GPU. */
+ * A value- and variance-driven term is rtg_svgf*'s, below, with parameter
+ * records of its own.  Out of scope: rtg_gbuf_px records as guides, per-pass
+ * parameters, filtering ray batches that are not a frame, views and
+ * multi-GPU. */
 #define RTG_FILTER_MAX_PASSES 8
 #define RTG_FILTER_RGB   0           /* kind: src and dst are rtg_vec */
 #define RTG_FILTER_GRAY  1           /* kind: src and dst are float */
@@ -1225,8 +1228,8 @@ int rtg_filter(int device, const rtg_hit* hits, unsigned width, unsigned height,
  * the previous state, so in-place use is a race (addresses compared as
  * numbers, on the host and on the device alike).
  *
- * Out of scope: moving spheres and motion vectors, a variance-guided filter
- * term, per-pixel alpha clamps, views and multi-GPU. */
+ * outM2 is what rtg_variance* reads, below.  Out of scope: moving spheres and
+ * motion vectors, per-pixel alpha clamps, views and multi-GPU. */
 #define RTG_ACCUM_SAME_ID 1         /* a tap of another id is left out */
 #define RTG_ACCUM_NORMAL 2          /* the normal term */
 #define RTG_ACCUM_PLANE 4           /* the plane-distance term */
@@ -1259,6 +1262,136 @@ int rtg_accumulate(int device, const rtg_hit* hits, unsigned width, unsigned hei
                    const rtg_camera* prevCam, float zoom, const rtg_hit* prevHits,
                    const float* prevAcc, const unsigned short* prevLen, const float* prevM2,
                    float* outAcc, unsigned short* outLen, float* outM2);
+
+/* ---- variance and svgf: the variance-guided a-trous filter ----
+ * rtg_filter* stops at geometric edges: id, normal and plane.  The signals it
+ * is meant for have their edges inside one sphere: contact shadows, shadow
+ * boundaries, indirect light.  These calls are the stage SVGF adds:
+ * rtg_variance* turns rtg_accumulate*'s moments into one variance per pixel,
+ * and rtg_svgf* runs the filter's passes with one more edge-stopping term, on
+ * the signal itself and scaled by the local standard deviation, carrying the
+ * variance from pass to pass so that the term tightens as the noise goes down.
+ * The chain is rtg_ao* / rtg_gather* -> rtg_accumulate* (with outM2) ->
+ * rtg_variance* -> rtg_svgf*.  Float arithmetic that is defined here: the same
+ * words on the host and on every GPU.  Frames, records, kinds, the tap rule's
+ * bits and dot(a, b) are rtg_filter*'s; C = 3 channels for RTG_FILTER_RGB, 1
+ * for RTG_FILTER_GRAY; RTG_FILTER_COUNT is RTG_ERR_INVALID here (the states
+ * are floats).  lum(v) = v for GRAY and (0.2126f * v.r + 0.7152f * v.g) +
+ * 0.0722f * v.b for RGB.
+ *
+ * VARIANCE.  `hits`: n records; `acc`, `m2`: n * C floats each,
+ * rtg_accumulate*'s outAcc and outM2; `len`: n unsigned short, its outLen.
+ * Output `var`: n floats.  Per pixel p:
+ *   id_p < 0:  var[p] = +0.f.
+ *   len_p >= minHistory:  m = acc[p], e = m2[p] (the temporal estimate).
+ *   otherwise the spatial estimate: s1.q = s2.q = sw = +0.f; for dy = -3 .. 3
+ *     (outer), dx = -3 .. 3 (inner), q = (x + dx, y + dy).  The tap is left out
+ *     when q is outside the frame, or id_q < 0, or SAME_ID is set and id_q !=
+ *     id_p, or SKIP_NONFINITE is set and any word of acc[q] or m2[q] has an
+ *     all-ones exponent field.  w = 1.f times rtg_filter*'s NORMAL and PLANE
+ *     terms, verbatim; the tap is left out when !(w > 0.f).  Otherwise
+ *       s1.q = s1.q + w * acc[q].q;  s2.q = s2.q + w * m2[q].q;  sw = sw + w
+ *     and then m.q = s1.q / sw, e.q = s2.q / sw if sw > 0.f, else m = acc[p],
+ *     e = m2[p].
+ *   d.q = e.q - m.q * m.q;  d.q = d.q > 0.f ? d.q : 0.f (a NaN goes to 0);
+ *   var[p] = lum(d): for RGB a luminance-weighted mean of the channel
+ *   variances (the second moment is per channel, so the variance of the
+ *   luminance cannot be had).  NaN words are stored as 0xFFC00000.
+ *
+ * SVGF, ONE PASS of step s reads `in` (n * C floats) and `vin` (n floats) and
+ * writes `out` and `vout`:
+ *   id_p < 0:  out[p] = in[p], vout[p] = vin[p]; there are no taps.
+ *   RTG_SVGF_LUMA only, the prefiltered variance at the centre: gs = gw =
+ *     +0.f; for dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), q = (x + dx,
+ *     y + dy), always at step 1, kw = k[dy + 1] * k[dx + 1], k = {1/4, 1/2,
+ *     1/4}.  The tap is left out when q is outside the frame, or id_q < 0, or
+ *     SAME_ID is set and id_q != id_p, or SKIP_NONFINITE is set and vin[q] has
+ *     an all-ones exponent field.  Otherwise gs = gs + kw * vin[q], gw = gw +
+ *     kw.  Then g = gw > 0.f ? gs / gw : vin[p];  den = sigmaL * sqrtf(g) +
+ *     epsL;  ls = 1.f / den, sqrtf and the quotient correctly rounded;
+ *     lp = lum(in[p]).
+ *   The 25 taps in rtg_filter*'s order and under its rule; SKIP_NONFINITE also
+ *     leaves a tap out when vin[q] has an all-ones exponent field.  w is
+ *     rtg_filter*'s weight; with LUMA then
+ *       l = fabsf(lum(in[q]) - lp);  z = 1.f - l * ls;  z = z > 0.f ? z : 0.f;
+ *       w = w * z
+ *     and the tap is left out when !(w > 0.f).  Otherwise
+ *       sum.q = sum.q + w * in[q].q;  sv = sv + (w * w) * vin[q];  sw = sw + w
+ *   result   sw > 0.f:  out[p].q = sum.q / sw, vout[p] = sv / (sw * sw);
+ *            otherwise  out[p] = in[p], vout[p] = vin[p].
+ * The luminance falloff is the plane term's clamped line, not SVGF's exp:
+ * there is no expf whose float words the host, numpy and the GPU share, and the
+ * same words everywhere is the contract.  Pass i = 0 .. passes - 1 has step
+ * 1 << i; pass 0 reads src and varSrc; dst and dstVar (required) receive the
+ * last pass, NaN words stored as 0xFFC00000.  NaN and infinite inputs follow
+ * the arithmetic and the comparisons as written.  With LUMA off and every
+ * vin finite the values are rtg_filter*'s.
+ *
+ * The _host forms restate this in plain loops: the yardstick.  The _device
+ * forms are asynchronous on `stream`, allocate nothing, need no scene and
+ * may be mixed with every other call on the context; `params` is host memory,
+ * read before return.  rtg_svgf_device needs a caller-owned scratch of
+ * rtg_svgf_scratch's bytes (a ping-pong value image and variance image, each
+ * rounded up to 16 bytes; 0 for one pass, and then the scratch may be null),
+ * 16-byte aligned, the call's until it has finished on the stream.
+ *
+ * RTG_ERR_INVALID with a message, before any GPU call, for a null pointer
+ * (varSrc and dstVar included), W or H equal to 0, W * H above 2^32 - 1 or
+ * (device) a grid above 2^31 - 1 workgroups, passes, normalLog2, minHistory or
+ * kind out of range, COUNT as the kind, an unknown flag, hits off 16-byte
+ * alignment (device), a scratch that is too small or misaligned, and any
+ * written byte range (var; dst, dstVar, the scratch) overlapping another of
+ * the call's value buffers (addresses compared as numbers).
+ *
+ * Out of scope: fusing the variance estimate into pass 0, feeding the first
+ * pass back as history, per-pass parameters, moving spheres, views and
+ * multi-GPU. */
+typedef struct rtg_variance_params { /* 20 B */
+  unsigned kind;        /* RTG_FILTER_RGB or RTG_FILTER_GRAY; COUNT is RTG_ERR_INVALID (states are floats) */
+  unsigned flags;       /* RTG_FILTER_SAME_ID | NORMAL | PLANE | SKIP_NONFINITE: the window's tap rule */
+  unsigned normalLog2;  /* 0..8 */
+  float planeScale;     /* used as given */
+  unsigned minHistory;  /* 0..65535: a hit pixel with len < minHistory takes the spatial estimate; 0: none does */
+} rtg_variance_params;
+/* Plain loops; the result does not depend on nthreads.  nthreads <= 0: 1. */
+int rtg_variance_host(const rtg_hit* hits, unsigned width, unsigned height,
+                      const rtg_variance_params* params, const float* acc, const float* m2,
+                      const unsigned short* len, float* varHost, int nthreads);
+int rtg_variance_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned width,
+                        unsigned height, const rtg_variance_params* params, const float* accDevice,
+                        const float* m2Device, const unsigned short* lenDevice, float* varDevice,
+                        void* stream);
+/* One-shot: uploads the inputs, runs on `device`, downloads n floats. */
+int rtg_variance(int device, const rtg_hit* hits, unsigned width, unsigned height,
+                 const rtg_variance_params* params, const float* acc, const float* m2,
+                 const unsigned short* len, float* varHost);
+
+#define RTG_SVGF_LUMA 16   /* next to the filter's four bits, which keep their meaning */
+typedef struct rtg_svgf_params { /* 28 B */
+  unsigned passes;      /* 1..RTG_FILTER_MAX_PASSES; pass i has step 1 << i */
+  unsigned normalLog2;  /* 0..8 */
+  float planeScale;     /* used as given */
+  unsigned kind;        /* RTG_FILTER_RGB or RTG_FILTER_GRAY; COUNT is RTG_ERR_INVALID */
+  unsigned flags;       /* the filter's bits | RTG_SVGF_LUMA */
+  float sigmaL;         /* used as given */
+  float epsL;           /* used as given */
+} rtg_svgf_params;
+/* Bytes of scratch rtg_svgf_device needs for such a frame. */
+int rtg_svgf_scratch(unsigned width, unsigned height, const rtg_svgf_params* params,
+                     size_t* bytes);
+/* Plain loops; the result does not depend on nthreads.  nthreads <= 0: 1. */
+int rtg_svgf_host(const rtg_hit* hits, unsigned width, unsigned height,
+                  const rtg_svgf_params* params, const float* src, const float* varSrc,
+                  float* dstHost, float* dstVarHost, int nthreads);
+int rtg_svgf_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned width, unsigned height,
+                    const rtg_svgf_params* params, const float* srcDevice,
+                    const float* varSrcDevice, float* dstDevice, float* dstVarDevice,
+                    void* scratchDevice, size_t scratchBytes, void* stream);
+/* One-shot: uploads the hits, src and varSrc, allocates its own scratch, runs
+ * on `device`, downloads dst and dstVar. */
+int rtg_svgf(int device, const rtg_hit* hits, unsigned width, unsigned height,
+             const rtg_svgf_params* params, const float* src, const float* varSrc, float* dstHost,
+             float* dstVarHost);
 
 /* ---- containment: primaryContainer per point ----
  * "Which medium is this point in": out[i] is the lowest sphere index s for

@@ -3,7 +3,8 @@
 // (rtg_filter.hip), the way gather_add and ao_world are shared, and what a
 // frame of a kind is to the filter and to the accumulation alike
 // (rtg_accumulate.hip): its sizes, the overlap test, the record loader and the
-// check of the terms.
+// check of the terms; and the tile geometry and the value store that the
+// variance-guided passes (rtg_svgf.hip) share with the filter's kernels.
 //
 // A pass visits 25 taps per pixel.  filter_admits is the part of the tap rule
 // that needs the ids alone (the forms read nothing else of a tap it rejects),
@@ -20,6 +21,9 @@
 #include "rtg_fold.h"
 #include "rtg_internal.h"
 #include "rtg_trace.h"
+#if defined(__HIPCC__)
+#include "rtg_entry.h"  // nan_bits, for the kernels' stores
+#endif
 
 namespace rtg {
 
@@ -160,5 +164,29 @@ template <int C>
 RTG_HD void filter_result(const FilterSum<C>& a, const float* in, float* out) {
   for (int q = 0; q < C; ++q) out[q] = a.sw > 0.f ? a.v[q] / a.sw : in[q];
 }
+
+#if defined(__HIPCC__)
+// ---- what the frame kernels share (rtg_filter.hip, rtg_svgf.hip) ----
+// One lane per pixel, workgroups of 256 lanes on 32 x 8 tiles of the frame,
+// tiles numbered row-major in a one-dimensional grid.
+constexpr unsigned kFilterTileW = 32, kFilterTileH = 8, kFilterThreads = 256;
+constexpr size_t kFilterLdsMax = 160 * 1024;  // a workgroup's LDS on gfx950
+
+// The lane's pixel of a pass record (its W, H and tilesX); false outside the frame.
+template <class Pass>
+__device__ __forceinline__ bool filter_pixel(const Pass& a, long long& x, long long& y) {
+  x = (long long)(blockIdx.x % a.tilesX) * kFilterTileW + threadIdx.x % kFilterTileW;
+  y = (long long)(blockIdx.x / a.tilesX) * kFilterTileH + threadIdx.x / kFilterTileW;
+  return x < (long long)a.W && y < (long long)a.H;
+}
+
+// A pixel's C words out; `last`: NaN words go out as 0xFFC00000.
+template <int C>
+__device__ __forceinline__ void filter_store_value(unsigned* out, size_t i, const float* v,
+                                                   unsigned last) {
+#pragma unroll
+  for (int q = 0; q < C; ++q) out[i * C + q] = last ? nan_bits(v[q]) : __float_as_uint(v[q]);
+}
+#endif
 
 }  // namespace rtg

@@ -61,8 +61,7 @@ static_assert(sizeof(rtg_vec) == 12, "three floats per colour");
 
 namespace rtg {
 
-constexpr unsigned kFilterTileW = 32, kFilterTileH = 8, kFilterThreads = 256;
-constexpr size_t kFilterLdsMax = 160 * 1024;  // a workgroup's LDS on gfx950
+// (the tile geometry, filter_pixel and filter_store_value are rtg_filter.h's)
 // The largest step the tiled form takes by default.
 constexpr unsigned kFilterTiledMaxStep = 4;
 
@@ -92,20 +91,6 @@ __device__ __forceinline__ void filter_load_value(const void* in, size_t i, floa
 #pragma unroll
     for (int q = 0; q < C; ++q) v[q] = static_cast<const float*>(in)[i * C + q];
   }
-}
-
-template <int C>
-__device__ __forceinline__ void filter_store_value(unsigned* out, size_t i, const float* v,
-                                                   unsigned last) {
-#pragma unroll
-  for (int q = 0; q < C; ++q) out[i * C + q] = last ? nan_bits(v[q]) : __float_as_uint(v[q]);
-}
-
-// The lane's pixel; false outside the frame.
-__device__ __forceinline__ bool filter_pixel(const FilterPass& a, long long& x, long long& y) {
-  x = (long long)(blockIdx.x % a.tilesX) * kFilterTileW + threadIdx.x % kFilterTileW;
-  y = (long long)(blockIdx.x / a.tilesX) * kFilterTileH + threadIdx.x / kFilterTileW;
-  return x < (long long)a.W && y < (long long)a.H;
 }
 
 template <int C, bool kCount>

@@ -83,7 +83,15 @@ static void usage() {
   printf("                           maxHistory 65535 unless given); the PGM is 255 * value / K as\n");
   printf("                           with --ao-filter, which then smooths the accumulated frame;\n");
   printf("                           needs --ao\n");
-  printf("      --matte      FILE    Also write the frame's direct light (rtg_matte_device of every\n");
+  printf("      --ao-variance SIGMA[,MINHISTORY]\n");
+  printf("                           Guide --ao-filter's passes by the variance of the counts: the\n");
+  printf("                           history carries the second moment (without --ao-history one\n");
+  printf("                           reset frame is accumulated), rtg_variance_device estimates a\n");
+  printf("                           variance per pixel with the filter's terms (spatially where the\n");
+  printf("                           history is shorter than MINHISTORY, 4 unless given) and the\n");
+  printf("                           passes run as rtg_svgf_device with RTG_SVGF_LUMA, sigmaL SIGMA and\n");
+  printf("                           epsL 1e-6; needs --ao-filter\n");
+  printf("      --matte      FILE   Also write the frame's direct light (rtg_matte_device of every\n");
   printf("                           primary hit at aa 1, from --camera or the identity pose) as a\n");
   printf("                           P6 PPM, scaled by its own largest component like the render\n");
   printf("      --gather     SPEC    Also write the frame's one-bounce indirect light: K[,bias[,seed]]\n");
@@ -100,6 +108,9 @@ static void usage() {
   printf("                           Accumulate the gathered light the same way (with\n");
   printf("                           RTG_ACCUM_SKIP_NONFINITE under --gather-skip) before it is\n");
   printf("                           filtered, scaled and written; needs --gather\n");
+  printf("      --gather-variance SIGMA[,MINHISTORY]\n");
+  printf("                           Guide --gather-filter's passes by the variance of the gathered\n");
+  printf("                           light, as --ao-variance does; needs --gather-filter\n");
   printf("      --repeat     K       Render K times, report the best time\n");
   printf("      --scene      FILE    Load the scene from FILE (format: include/rtg.h)\n");
   printf("      --save-scene FILE    Write the scene used to FILE\n");
@@ -202,13 +213,57 @@ struct HistoryState {
   rtg_hit* hits;
   float* acc;
   unsigned short* len;
+  float* m2;  // the second moment, carried under --ao-variance / --gather-variance only
 };
 static void accumulate_frame(rtg_context* ctx, const History& h, unsigned W, unsigned H, float zoom,
                              const void* src, const HistoryState* from, const HistoryState& to) {
   check(rtg_accumulate_device(ctx, to.hits, W, H, &h.params, src, from ? &from->pose : nullptr,
                               zoom, from ? from->hits : nullptr, from ? from->acc : nullptr,
-                              from ? from->len : nullptr, nullptr, to.acc, to.len, nullptr, nullptr),
+                              from ? from->len : nullptr, from ? from->m2 : nullptr, to.acc, to.len,
+                              to.m2, nullptr),
         "rtg_accumulate_device");
+}
+
+// "SIGMA[,minHistory]" of --ao-variance and --gather-variance; false when it is not that.
+struct Variance {
+  bool on = false;
+  float sigma = 0.f;
+  unsigned minHistory = 4;
+};
+static bool parse_variance(const char* s, Variance* v) {
+  char tail = 0;
+  const int k = sscanf(s, "%f,%u%c", &v->sigma, &v->minHistory, &tail);
+  v->on = true;
+  return k >= 1 && k <= 2 && v->minHistory <= 65535;
+}
+
+// rtg_variance_device of the accumulated state `s` with the filter's terms, then the filter's
+// passes as rtg_svgf_device with RTG_SVGF_LUMA, into a new device buffer, on the default stream.
+static void* svgf_frame(rtg_context* ctx, const HistoryState& s, unsigned W, unsigned H,
+                        const rtg_filter_params& fp, const Variance& v) {
+  const unsigned kind = fp.kind == RTG_FILTER_RGB ? RTG_FILTER_RGB : RTG_FILTER_GRAY;
+  const size_t n = (size_t)W * H, out = n * (kind == RTG_FILTER_RGB ? 3 : 1) * sizeof(float);
+  const rtg_variance_params vp = {kind, fp.flags, fp.normalLog2, fp.planeScale, v.minHistory};
+  const rtg_svgf_params sp = {fp.passes, fp.normalLog2, fp.planeScale, kind,
+                              fp.flags | RTG_SVGF_LUMA, v.sigma, 1e-6f};
+  size_t bytes = 0;
+  check(rtg_svgf_scratch(W, H, &sp, &bytes), "rtg_svgf_scratch");
+  void *dst = nullptr, *scratch = nullptr;
+  float *var = nullptr, *dstVar = nullptr;
+  if (hipMalloc(&dst, out) != hipSuccess || hipMalloc(&var, n * sizeof(float)) != hipSuccess ||
+      hipMalloc(&dstVar, n * sizeof(float)) != hipSuccess ||
+      (bytes && hipMalloc(&scratch, bytes) != hipSuccess))
+    check(RTG_ERR_NOMEM, "hipMalloc");
+  check(rtg_variance_device(ctx, s.hits, W, H, &vp, s.acc, s.m2, s.len, var, nullptr),
+        "rtg_variance_device");
+  check(rtg_svgf_device(ctx, s.hits, W, H, &sp, s.acc, var, (float*)dst, dstVar, scratch, bytes,
+                        nullptr),
+        "rtg_svgf_device");
+  if (hipDeviceSynchronize() != hipSuccess) check(RTG_ERR_HIP, "rtg_svgf_device");
+  (void)hipFree(scratch);
+  (void)hipFree(var);
+  (void)hipFree(dstVar);
+  return dst;
 }
 
 static bool parse_uint(const char* s, unsigned* out) {
@@ -231,6 +286,7 @@ int main(int argc, char** argv) {
   bool aoFilter = false, gatherFilter = false;
   rtg_filter_params aoFilterParams = {}, gatherFilterParams = {};
   History aoHistory, gatherHistory;
+  Variance aoVariance, gatherVariance;
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   bool posed = false;
@@ -362,6 +418,11 @@ int main(int argc, char** argv) {
         printf("Invalid history (FILE[,maxHistory], maxHistory in 1..65535)\n");
         return 1;
       }
+    } else if (!strcmp(a, "--ao-variance") || !strcmp(a, "--gather-variance")) {
+      if (!parse_variance(need(a), a[2] == 'a' ? &aoVariance : &gatherVariance)) {
+        printf("Invalid variance (SIGMA[,minHistory], minHistory in 0..65535)\n");
+        return 1;
+      }
     } else if (!strcmp(a, "--matte")) {
       matteOut = need(a);
       matte = true;
@@ -421,8 +482,15 @@ int main(int argc, char** argv) {
     printf("--ao-history needs --ao, --gather-history needs --gather\n");
     return 1;
   }
+  if ((aoVariance.on && !aoFilter) || (gatherVariance.on && !gatherFilter)) {
+    printf("--ao-variance needs --ao-filter, --gather-variance needs --gather-filter\n");
+    return 1;
+  }
+  // the variance needs the accumulated moments: without a history, of one reset frame
+  const bool aoAccum = aoHistory.on || aoVariance.on;
+  const bool gatherAccum = gatherHistory.on || gatherVariance.on;
   // (an accumulated frame is floats: the filter then takes it as GRAY)
-  aoFilterParams.kind = aoHistory.on ? RTG_FILTER_GRAY : RTG_FILTER_COUNT;
+  aoFilterParams.kind = aoAccum ? RTG_FILTER_GRAY : RTG_FILTER_COUNT;
   gatherFilterParams.kind = RTG_FILTER_RGB;
   if (gatherSkip) gatherFilterParams.flags |= RTG_FILTER_SKIP_NONFINITE;
   aoHistory.params.kind = RTG_FILTER_COUNT;
@@ -673,8 +741,9 @@ int main(int argc, char** argv) {
       check(RTG_ERR_NOMEM, "hipMalloc");
     for (size_t k = 0; k < (frames > 1 ? 2u : 1u); ++k)
       if (hipMalloc(&st[k].hits, n * sizeof(rtg_hit)) != hipSuccess ||
-          (aoHistory.on && (hipMalloc(&st[k].acc, n * sizeof(float)) != hipSuccess ||
-                            hipMalloc(&st[k].len, n * sizeof(unsigned short)) != hipSuccess)))
+          (aoAccum && (hipMalloc(&st[k].acc, n * sizeof(float)) != hipSuccess ||
+                       hipMalloc(&st[k].len, n * sizeof(unsigned short)) != hipSuccess)) ||
+          (aoVariance.on && hipMalloc(&st[k].m2, n * sizeof(float)) != hipSuccess))
         check(RTG_ERR_NOMEM, "hipMalloc");
     if (hipMemcpy(dd, table.data(), K * sizeof(rtg_vec), hipMemcpyHostToDevice) != hipSuccess)
       check(RTG_ERR_HIP, "upload");
@@ -687,7 +756,7 @@ int main(int argc, char** argv) {
             "rtg_camera_rays_device");
       check(rtg_intersect_device(ctx, dr, n, cur.hits, nullptr), "rtg_intersect_device");
       check(rtg_ao_device(ctx, cur.hits, n, &ap, dd, K, dc, nullptr), "rtg_ao_device");
-      if (aoHistory.on)
+      if (aoAccum)
         accumulate_frame(ctx, aoHistory, W, H, zoom, dc, k ? &st[(k - 1) & 1] : nullptr, cur);
     }
     const HistoryState& last = st[(frames - 1) & 1];
@@ -697,9 +766,10 @@ int main(int argc, char** argv) {
         hipSuccess)
       check(RTG_ERR_HIP, "readback");
     if (aoFilter || aoHistory.on) {  // the frame never leaves the device on its way to the filter
-      void* df = aoFilter ? filter_frame(ctx, last.hits, W, H, aoFilterParams,
-                                         aoHistory.on ? (const void*)last.acc : dc)
-                          : last.acc;
+      void* df = aoVariance.on ? svgf_frame(ctx, last, W, H, aoFilterParams, aoVariance)
+                 : aoFilter    ? filter_frame(ctx, last.hits, W, H, aoFilterParams,
+                                              aoHistory.on ? (const void*)last.acc : dc)
+                               : last.acc;
       smooth.resize(n);
       if (hipMemcpy(smooth.data(), df, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
         check(RTG_ERR_HIP, "readback");
@@ -712,6 +782,7 @@ int main(int argc, char** argv) {
       (void)hipFree(s.hits);
       (void)hipFree(s.acc);
       (void)hipFree(s.len);
+      (void)hipFree(s.m2);
     }
     rtg_context_destroy(ctx);
     std::vector<unsigned char> grey(n);
@@ -798,8 +869,9 @@ int main(int argc, char** argv) {
     HistoryState st[2] = {};
     for (size_t k = 0; k < (frames > 1 ? 2u : 1u); ++k)
       if (hipMalloc(&st[k].hits, n * sizeof(rtg_hit)) != hipSuccess ||
-          (gatherHistory.on && (hipMalloc(&st[k].acc, n * sizeof(rtg_vec)) != hipSuccess ||
-                                hipMalloc(&st[k].len, n * sizeof(unsigned short)) != hipSuccess)))
+          (gatherAccum && (hipMalloc(&st[k].acc, n * sizeof(rtg_vec)) != hipSuccess ||
+                           hipMalloc(&st[k].len, n * sizeof(unsigned short)) != hipSuccess)) ||
+          (gatherVariance.on && hipMalloc(&st[k].m2, n * sizeof(rtg_vec)) != hipSuccess))
         check(RTG_ERR_NOMEM, "hipMalloc");
     if (hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
         hipMalloc(&dd, K * sizeof(rtg_vec)) != hipSuccess ||
@@ -821,15 +893,18 @@ int main(int argc, char** argv) {
       check(rtg_gather_device(ctx, cur.hits, n, &gp, dd, dw, K, (int)depth + 1, dl, nullptr,
                               nullptr),
             "rtg_gather_device");
-      if (gatherHistory.on)
+      if (gatherAccum)
         accumulate_frame(ctx, gatherHistory, W, H, zoom, dl, k ? &st[(k - 1) & 1] : nullptr, cur);
     }
     const HistoryState& last = st[(frames - 1) & 1];
-    if (gatherHistory.on &&  // the accumulated frame takes the gathered one's place
+    if (gatherAccum &&  // the accumulated frame takes the gathered one's place
         hipMemcpy(dl, last.acc, n * sizeof(rtg_vec), hipMemcpyDeviceToDevice) != hipSuccess)
       check(RTG_ERR_HIP, "copy");
     if (gatherFilter) {
-      rtg_vec* smooth = (rtg_vec*)filter_frame(ctx, last.hits, W, H, gatherFilterParams, dl);
+      rtg_vec* smooth =
+          (rtg_vec*)(gatherVariance.on
+                         ? svgf_frame(ctx, last, W, H, gatherFilterParams, gatherVariance)
+                         : filter_frame(ctx, last.hits, W, H, gatherFilterParams, dl));
       (void)hipFree(dl);
       dl = smooth;
     }
@@ -845,6 +920,7 @@ int main(int argc, char** argv) {
       (void)hipFree(s.hits);
       (void)hipFree(s.acc);
       (void)hipFree(s.len);
+      (void)hipFree(s.m2);
     }
     (void)hipFree(dd);
     (void)hipFree(dw);

@@ -84,6 +84,15 @@ ACCUM_PARAMS_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("normalLog2",
                                ("planeScale", "<f4"), ("maxHistory", "<u4")])
 assert ACCUM_PARAMS_DTYPE.itemsize == 20
 ACCUM_SAME_ID, ACCUM_NORMAL, ACCUM_PLANE, ACCUM_SKIP_NONFINITE = 1, 2, 4, 8  # RTG_ACCUM_*
+# rtg_variance_params and rtg_svgf_params (include/rtg.h): the variance-guided filter
+VARIANCE_PARAMS_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("normalLog2", "<u4"),
+                                  ("planeScale", "<f4"), ("minHistory", "<u4")])
+assert VARIANCE_PARAMS_DTYPE.itemsize == 20
+SVGF_PARAMS_DTYPE = np.dtype([("passes", "<u4"), ("normalLog2", "<u4"), ("planeScale", "<f4"),
+                              ("kind", "<u4"), ("flags", "<u4"), ("sigmaL", "<f4"),
+                              ("epsL", "<f4")])
+assert SVGF_PARAMS_DTYPE.itemsize == 28
+SVGF_LUMA = 16  # RTG_SVGF_LUMA, next to the FILTER_* bits
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -123,6 +132,8 @@ EXPORTED = [
     "rtg_gather_host",
     "rtg_filter_scratch", "rtg_filter_host", "rtg_filter_device", "rtg_filter",
     "rtg_accumulate_host", "rtg_accumulate_device", "rtg_accumulate",
+    "rtg_variance_host", "rtg_variance_device", "rtg_variance",
+    "rtg_svgf_scratch", "rtg_svgf_host", "rtg_svgf_device", "rtg_svgf",
     "rtg_contains_device", "rtg_contains", "rtg_contains_host",
 ]
 
@@ -295,6 +306,21 @@ def lib() -> ctypes.CDLL:
                 ("rtg_accumulate_device",
                  [vp, vp, u, u, vp, vp, vp, f, vp, vp, vp, vp, vp, vp, vp, vp]),
                 ("rtg_accumulate", [i, vp, u, u, vp, vp, vp, f, vp, vp, vp, vp, vp, vp, vp])):
+            try:
+                getattr(L, name).argtypes = at
+            except AttributeError:
+                if not os.environ.get("RTG_LIB"):
+                    raise
+        # the variance-guided filter; an RTG_LIB build of the commit before it
+        # (tools/ab_bench.sh against the parent) loads without it
+        for name, at in (
+                ("rtg_variance_host", [vp, u, u, vp, vp, vp, vp, vp, i]),
+                ("rtg_variance_device", [vp, vp, u, u, vp, vp, vp, vp, vp, vp]),
+                ("rtg_variance", [i, vp, u, u, vp, vp, vp, vp, vp]),
+                ("rtg_svgf_scratch", [u, u, vp, vp]),
+                ("rtg_svgf_host", [vp, u, u, vp, vp, vp, vp, vp, i]),
+                ("rtg_svgf_device", [vp, vp, u, u, vp, vp, vp, vp, vp, vp, sz, vp]),
+                ("rtg_svgf", [i, vp, u, u, vp, vp, vp, vp, vp])):
             try:
                 getattr(L, name).argtypes = at
             except AttributeError:
@@ -1150,6 +1176,104 @@ def accumulate(hits, width: int, height: int, params, src, prev=None, zoom: floa
     return (acc, ln, o2) if m2 else (acc, ln)
 
 
+def variance_params(kind: int = FILTER_RGB, flags: int = 0, plane_scale: float = 0.0,
+                    normal_log2: int = 0, min_history: int = 4) -> np.ndarray:
+    """One rtg_variance_params record (kind: FILTER_RGB / GRAY; flags:
+    FILTER_SAME_ID | NORMAL | PLANE | SKIP_NONFINITE, the spatial window's tap
+    rule; a hit pixel with len < min_history takes the spatial estimate)."""
+    p = np.zeros(1, VARIANCE_PARAMS_DTYPE)
+    p[0] = (kind, flags, normal_log2, plane_scale, min_history)
+    return p
+
+
+def _variance_args(hits, width: int, height: int, params, acc, m2, length):
+    """The records, params and the accumulated state as contiguous arrays, and
+    the destination: (H, W) float32."""
+    p = np.ascontiguousarray(params, VARIANCE_PARAMS_DTYPE).reshape(1)
+    C = 3 if int(p["kind"][0]) == FILTER_RGB else 1
+    n = width * height
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    a = np.ascontiguousarray(acc, np.float32).reshape(-1)
+    m = np.ascontiguousarray(m2, np.float32).reshape(-1)
+    ln = np.ascontiguousarray(length, np.uint16).reshape(-1)
+    if len(h) != n or len(a) != n * C or len(m) != n * C or len(ln) != n:
+        raise ValueError(f"variance: {len(h)} hit records, {len(a)} and {len(m)} moment words and "
+                         f"{len(ln)} lengths for a {width} x {height} frame of {C} channels")
+    return h, p, a, m, ln, np.empty((height, width), np.float32)
+
+
+def variance_host(hits, width: int, height: int, params, acc, m2, length,
+                  threads: int = 1) -> np.ndarray:
+    """One variance per pixel from accumulate's moments on the host
+    (rtg_variance_host; no GPU needed): acc, m2 and length are accumulate's
+    (acc, len, m2) of the frame, params from variance_params(); (H, W) float32
+    out."""
+    h, p, a, m, ln, out = _variance_args(hits, width, height, params, acc, m2, length)
+    _check(lib().rtg_variance_host(_ptr(h), width, height, _ptr(p), _ptr(a), _ptr(m), _ptr(ln),
+                                   _ptr(out), threads), "rtg_variance_host")
+    return out
+
+
+def variance(hits, width: int, height: int, params, acc, m2, length, device: int = 0) -> np.ndarray:
+    """The same on the GPU, one-shot (rtg_variance)."""
+    h, p, a, m, ln, out = _variance_args(hits, width, height, params, acc, m2, length)
+    _check(lib().rtg_variance(device, _ptr(h), width, height, _ptr(p), _ptr(a), _ptr(m), _ptr(ln),
+                              _ptr(out)), "rtg_variance")
+    return out
+
+
+def svgf_params(passes: int, kind: int = FILTER_RGB, flags: int = 0, plane_scale: float = 0.0,
+                normal_log2: int = 0, sigma_l: float = 4.0, eps_l: float = 1e-6) -> np.ndarray:
+    """One rtg_svgf_params record (kind: FILTER_RGB / GRAY; flags: the FILTER_*
+    bits | SVGF_LUMA, the luminance term scaled by sigma_l and eps_l)."""
+    p = np.zeros(1, SVGF_PARAMS_DTYPE)
+    p[0] = (passes, normal_log2, plane_scale, kind, flags, sigma_l, eps_l)
+    return p
+
+
+def svgf_scratch(width: int, height: int, params) -> int:
+    """Bytes of device scratch Context.svgf_device needs for such a frame
+    (rtg_svgf_scratch): caller-owned, 16-byte aligned; 0 for one pass."""
+    p = np.ascontiguousarray(params, SVGF_PARAMS_DTYPE).reshape(1)
+    out = ctypes.c_size_t(0)
+    _check(lib().rtg_svgf_scratch(width, height, _ptr(p), ctypes.byref(out)), "rtg_svgf_scratch")
+    return out.value
+
+
+def _svgf_args(hits, width: int, height: int, params, src, var):
+    """The records, params, source and its variance as contiguous arrays, and
+    the destinations: (H, W, 3) or (H, W) float32, and (H, W) float32."""
+    p = np.ascontiguousarray(params, SVGF_PARAMS_DTYPE).reshape(1)
+    C = 3 if int(p["kind"][0]) == FILTER_RGB else 1
+    n = width * height
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    s = np.ascontiguousarray(src, np.float32).reshape(-1)
+    v = np.ascontiguousarray(var, np.float32).reshape(-1)
+    if len(h) != n or len(s) != n * C or len(v) != n:
+        raise ValueError(f"svgf: {len(h)} hit records, {len(s)} source words and {len(v)} "
+                         f"variances for a {width} x {height} frame of {C} channels")
+    out = np.empty((height, width, 3) if C == 3 else (height, width), np.float32)
+    return h, p, s, v, out, np.empty((height, width), np.float32)
+
+
+def svgf_host(hits, width: int, height: int, params, src, var, threads: int = 1):
+    """The variance-guided a-trous passes on the host (rtg_svgf_host; no GPU
+    needed): src the frame's float32 signal, var its per-pixel variance
+    (variance_host's), params from svgf_params().  Returns (dst, dst_var)."""
+    h, p, s, v, out, vout = _svgf_args(hits, width, height, params, src, var)
+    _check(lib().rtg_svgf_host(_ptr(h), width, height, _ptr(p), _ptr(s), _ptr(v), _ptr(out),
+                               _ptr(vout), threads), "rtg_svgf_host")
+    return out, vout
+
+
+def svgf(hits, width: int, height: int, params, src, var, device: int = 0):
+    """The same on the GPU, one-shot (rtg_svgf)."""
+    h, p, s, v, out, vout = _svgf_args(hits, width, height, params, src, var)
+    _check(lib().rtg_svgf(device, _ptr(h), width, height, _ptr(p), _ptr(s), _ptr(v), _ptr(out),
+                          _ptr(vout)), "rtg_svgf")
+    return out, vout
+
+
 def _project_args(camera, points):
     c = np.ascontiguousarray(camera, CAMERA_DTYPE).reshape(1)
     p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
@@ -1577,6 +1701,34 @@ class Context:
                                            v(pv[2]), v(pv[3]), v(out_acc_ptr), v(out_len_ptr),
                                            v(out_m2_ptr), v(stream)),
                "rtg_accumulate_device")
+
+    def variance_device(self, hits_ptr: int, width: int, height: int, params, acc_ptr: int,
+                        m2_ptr: int, len_ptr: int, var_ptr: int, stream: int = 0):
+        """One variance per pixel of a width x height frame from the accumulated
+        state at acc_ptr, m2_ptr (float32 per channel) and len_ptr (uint16),
+        accumulate_device's outputs, into var_ptr (device, float32 per pixel),
+        asynchronously on `stream` (rtg_variance_device; params from
+        variance_params(); the context needs no scene)."""
+        p = np.ascontiguousarray(params, VARIANCE_PARAMS_DTYPE).reshape(1)
+        v = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        _check(lib().rtg_variance_device(self._h, v(hits_ptr), width, height, _ptr(p), v(acc_ptr),
+                                         v(m2_ptr), v(len_ptr), v(var_ptr), v(stream)),
+               "rtg_variance_device")
+
+    def svgf_device(self, hits_ptr: int, width: int, height: int, params, src_ptr: int,
+                    var_ptr: int, dst_ptr: int, dst_var_ptr: int, scratch_ptr: int = 0,
+                    scratch_bytes: int = 0, stream: int = 0):
+        """The variance-guided a-trous passes of a width x height frame: the signal
+        at src_ptr (float32 per channel) and its variance at var_ptr (float32 per
+        pixel) into dst_ptr and dst_var_ptr, asynchronously on `stream`
+        (rtg_svgf_device; params from svgf_params(), the scratch svgf_scratch()
+        bytes, 16-byte aligned; the context needs no scene)."""
+        p = np.ascontiguousarray(params, SVGF_PARAMS_DTYPE).reshape(1)
+        v = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        _check(lib().rtg_svgf_device(self._h, v(hits_ptr), width, height, _ptr(p), v(src_ptr),
+                                     v(var_ptr), v(dst_ptr), v(dst_var_ptr), v(scratch_ptr),
+                                     scratch_bytes, v(stream)),
+               "rtg_svgf_device")
 
     def camera_project_device(self, camera, width: int, height: int, points_ptr: int, n: int,
                               dst_ptr: int, zoom: float = -4.0, stream: int = 0):

@@ -2,7 +2,7 @@
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
                        [--only-order] [--only-ao] [--only-matte] [--only-views]
                        [--only-fold] [--only-gather] [--only-filter] [--only-accumulate]
-                       [--order-alt-json FILE ...]
+                       [--only-svgf] [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
 with the scene and the rays resident, on three batches of bench.py's frames:
@@ -97,6 +97,13 @@ rows under "accumulate" (accumulate_rows below): one frame blended onto the
 previous one under a small pan and under a roll, both wave shapes of the kernel
 side by side, a torch chain of the same arithmetic and the streaming floor.
 --only-accumulate runs these alone and keeps FILE's other sections.
+
+The variance estimate and the variance-guided passes (rtg_variance_device,
+rtg_svgf_device, csrc/rtg_svgf.hip) get rows under "svgf" (svgf_rows below): the
+filter's four frames fed through one accumulation with M2, the variance with
+every history long and short against its streaming floor, five passes against
+rtg_filter_device in the same rounds, per pass and form, and a torch chain.
+--only-svgf runs these alone and keeps FILE's other sections.
 GPU only.
 """
 import argparse
@@ -640,6 +647,236 @@ def filter_rows(args, stream):
     return out, ok
 
 
+def torch_svgf(ids, P, N, img, var, passes, flags, normal_log2, scale, sigma, eps):
+    """rtg_svgf*'s arithmetic with RTG_SVGF_LUMA as a torch chain, in the manner
+    of torch_filter: img a list of C (H, W) planes, var an (H, W) plane; the
+    filtered planes and the carried variance."""
+    import torch.nn.functional as TF
+    H, W = ids.shape
+    hw, kw = (0.0625, 0.25, 0.375, 0.25, 0.0625), (0.25, 0.5, 0.25)
+    zero = torch.zeros((), dtype=torch.float32, device=ids.device)
+
+    def lum(v):
+        return v[0] if len(v) == 1 else (0.2126 * v[0] + 0.7152 * v[1]) + 0.0722 * v[2]
+
+    def admits(idq, vals):
+        keep = idq >= 0
+        if flags & R.FILTER_SAME_ID:
+            keep &= idq == ids
+        if flags & R.FILTER_SKIP_NONFINITE:
+            for a in vals:
+                keep &= torch.isfinite(a)
+        return keep
+
+    for i in range(passes):
+        s = 1 << i
+        b = 2 * s
+        pad = lambda a, v: TF.pad(a, (b, b, b, b), value=v)  # noqa: E731
+        idp, varp = pad(ids, -1), pad(var, 0.0)
+        Pp, Np, vp = [pad(a, 0.0) for a in P], [pad(a, 0.0) for a in N], [pad(a, 0.0) for a in img]
+        gs, gw = torch.zeros_like(var), torch.zeros_like(var)
+        for dy in range(-1, 2):
+            for dx in range(-1, 2):
+                ys, xs = slice(b + dy, b + dy + H), slice(b + dx, b + dx + W)
+                keep = admits(idp[ys, xs], [varp[ys, xs]])
+                k = kw[dy + 1] * kw[dx + 1]
+                gs += torch.where(keep, k * varp[ys, xs], zero)
+                gw += torch.where(keep, torch.full_like(gw, k), zero)
+        g = torch.where(gw > 0, gs / gw, var)
+        ls = 1.0 / (sigma * torch.sqrt(g) + eps)
+        lp = lum(img)
+        acc = [torch.zeros_like(a) for a in img]
+        sv, sw = torch.zeros_like(var), torch.zeros_like(var)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                ys, xs = slice(b + dy * s, b + dy * s + H), slice(b + dx * s, b + dx * s + W)
+                vq = [a[ys, xs] for a in vp]
+                keep = admits(idp[ys, xs], vq + [varp[ys, xs]])
+                w = torch.full_like(sw, hw[dy + 2] * hw[dx + 2])
+                if flags & R.FILTER_NORMAL:
+                    c = (N[0] * Np[0][ys, xs] + N[1] * Np[1][ys, xs]) + N[2] * Np[2][ys, xs]
+                    c = torch.where(c > 0, c, zero)
+                    for _ in range(normal_log2):
+                        c = c * c
+                    w = w * c
+                if flags & R.FILTER_PLANE:
+                    e = [Pp[q][ys, xs] - P[q] for q in range(3)]
+                    d = ((N[0] * e[0] + N[1] * e[1]) + N[2] * e[2]).abs()
+                    z = 1.0 - d * scale
+                    w = w * torch.where(z > 0, z, zero)
+                z = 1.0 - (lum(vq) - lp).abs() * ls
+                w = w * torch.where(z > 0, z, zero)
+                keep &= w > 0
+                w = torch.where(keep, w, zero)
+                for q in range(len(img)):
+                    acc[q] += torch.where(keep, w * vq[q], zero)
+                sv += torch.where(keep, (w * w) * varp[ys, xs], zero)
+                sw += w
+        done = (sw > 0) & (ids >= 0)
+        img = [torch.where(done, acc[q] / sw, img[q]) for q in range(len(img))]
+        var = torch.where(done, sv / (sw * sw), var)
+    return img, var
+
+
+def svgf_rows(args, stream):
+    """The variance estimate and the variance-guided passes (csrc/rtg_svgf.hip)
+    on filter_rows' four frames, each fed through one rtg_accumulate_device
+    (a reset frame, with M2), floats from there on.  Round by round in one
+    process: rtg_variance_device with every history long (minHistory 0: the
+    stream) and with every history short (minHistory 65535: every tile with a
+    hit stages its window), against the streaming floor (the id, acc, m2 and len
+    in, one word out per pixel at 6 TB/s); rtg_filter_device at five passes on
+    the accumulated frame, the yardstick; rtg_svgf_device at five passes with
+    SAME_ID | NORMAL | PLANE | RTG_SVGF_LUMA, sigmaL 4, epsL 1e-6, as it chooses
+    its forms and with each form forced (RTG_SVGF_FORM) at passes 1 to 5, whose
+    differences are the passes on their own (floor per pass: 32 guide bytes,
+    value and variance in and out); and a torch chain of the same arithmetic.
+    Reported, not gated: every time.  Gated: the call and the torch chain agree
+    to 1e-4 relative on finite pixels, value and variance."""
+    K, passes, nlog, sigma, eps = 16, 5, 3, 4.0, 1e-6
+    FORMS = ("tiled", "direct")
+    flags = R.FILTER_SAME_ID | R.FILTER_NORMAL | R.FILTER_PLANE
+    table = torch.from_numpy(R.ao_directions(K)).cuda()
+    wt = torch.full((K,), 1.0 / K, dtype=torch.float32, device="cuda")
+    out, ok = {"passes": passes, "flags": flags | R.SVGF_LUMA, "normalLog2": nlog, "samples": K,
+               "sigmaL": sigma, "epsL": eps, "floor_bandwidth_TBps": 6.0}, True
+    for name, cfg, (W, H), kind in (("c3_count", "c3", CONFIGS["c3"][:2], R.FILTER_COUNT),
+                                    ("c5_count", "c5", CONFIGS["c5"][:2], R.FILTER_COUNT),
+                                    ("c3_rgb", "c3", CONFIGS["c3"][:2], R.FILTER_RGB),
+                                    ("c5_rgb_1080p", "c5", (1920, 1080), R.FILTER_RGB)):
+        n, S, C = W * H, CONFIGS[cfg][4] + 1, 3 if kind == R.FILTER_RGB else 1
+        fkind = R.FILTER_RGB if C == 3 else R.FILTER_GRAY
+        sph, lg = R.generate_scene(CONFIGS[cfg][2], CONFIGS[cfg][3], 42)
+        scale = float(F(1) / np.abs(sph["radius"]).max())
+        rays0 = torch.from_numpy(primary_rays(W, H)).cuda()
+        hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        ctx.intersect_device(rays0.data_ptr(), n, hits.data_ptr(), stream)
+        if kind == R.FILTER_COUNT:
+            src = torch.empty((n,), dtype=torch.int16, device="cuda")
+            radius = float(F(2.5) * np.abs(sph["radius"]).max())
+            ctx.ao_device(hits.data_ptr(), n, R.ao_params(K, radius, 1e-3, 42, R.AO_JITTER),
+                          table.data_ptr(), K, src.data_ptr(), stream)
+        else:
+            src = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+            gp = R.gather_params(K, 1e-3, 42, R.GATHER_JITTER | R.GATHER_SKIP_NONFINITE)
+            ctx.gather_device(hits.data_ptr(), n, gp, table.data_ptr(), wt.data_ptr(), K,
+                              src.data_ptr(), stack_size=S, stream=stream)
+        acc = torch.empty((n, C), dtype=torch.float32, device="cuda")
+        m2 = torch.empty((n, C), dtype=torch.float32, device="cuda")
+        ln = torch.empty((n,), dtype=torch.int16, device="cuda")
+        ctx.accumulate_device(hits.data_ptr(), W, H,
+                              R.accumulate_params(kind, flags | R.ACCUM_SKIP_NONFINITE, scale, nlog),
+                              src.data_ptr(), acc.data_ptr(), ln.data_ptr(), None,
+                              out_m2_ptr=m2.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        del rays0, src
+        var, dvar = (torch.empty((n,), dtype=torch.float32, device="cuda") for _ in range(2))
+        dst = torch.empty((n, C), dtype=torch.float32, device="cuda")
+        fdst = torch.empty((n, C), dtype=torch.float32, device="cuda")
+        ps = [R.svgf_params(k, fkind, flags | R.SVGF_LUMA, scale, nlog, sigma, eps)
+              for k in range(1, passes + 1)]
+        fp = R.filter_params(passes, fkind, flags, scale, nlog)
+        nbytes, fbytes = R.svgf_scratch(W, H, ps[-1]), R.filter_scratch(W, H, fp)
+        scratch = torch.empty((max(nbytes, 16) // 4,), dtype=torch.int32, device="cuda")
+
+        def variance(min_history):
+            ctx.variance_device(hits.data_ptr(), W, H,
+                                R.variance_params(fkind, flags, scale, nlog, min_history),
+                                acc.data_ptr(), m2.data_ptr(), ln.data_ptr(), var.data_ptr(), stream)
+
+        def plain():
+            ctx.filter_device(hits.data_ptr(), W, H, fp, acc.data_ptr(), fdst.data_ptr(),
+                              scratch.data_ptr(), fbytes, stream)
+
+        def call(form, p):
+            if form:
+                os.environ["RTG_SVGF_FORM"] = form
+            else:
+                os.environ.pop("RTG_SVGF_FORM", None)
+            ctx.svgf_device(hits.data_ptr(), W, H, p, acc.data_ptr(), var.data_ptr(), dst.data_ptr(),
+                            dvar.data_ptr(), scratch.data_ptr(), nbytes, stream)
+
+        variance(65535)  # what the passes are timed on: the spatial estimate of the one frame
+        fns = [lambda: variance(0), lambda: variance(65535), plain, lambda: call("", ps[-1])]
+        fns += [(lambda f=f, p=p: call(f, p)) for f in FORMS for p in ps]
+        head = 4
+        raw = []
+        m = measure(fns, args.rounds, window_ms=100.0, raw=raw,
+                    names=[f"svgf {name} variance long", f"svgf {name} variance short",
+                           f"svgf {name} filter", f"svgf {name} default"] +
+                          [f"svgf {name} {f} passes {k}" for f in FORMS for k in range(1, passes + 1)])
+        os.environ.pop("RTG_SVGF_FORM", None)
+        vfloor = n * (4 + 8 * C + 2 + 4) / 6.0e12 * 1e3
+        floor = n * (40 + 8 * C) / 6.0e12 * 1e3
+        forms = {}
+        for fi, f in enumerate(FORMS):
+            cum = raw[head + fi * passes:head + (fi + 1) * passes]
+            per = [cum[0]] + [[b - a for a, b in zip(cum[k - 1], cum[k])] for k in range(1, passes)]
+            forms[f] = {"cumulative": m[head + fi * passes:head + (fi + 1) * passes],
+                        "pass_ms_median": [round(float(np.median(v)), 5) for v in per],
+                        "pass_ms_min": [round(min(v), 5) for v in per],
+                        "pass_ms_max": [round(max(v), 5) for v in per],
+                        "pass_over_floor": [round(float(np.median(v)) / floor, 2) for v in per]}
+        # the call's own answer, then the torch chain of the same arithmetic
+        variance(65535)
+        call("", ps[-1])
+        torch.cuda.synchronize()
+        got, gvar = dst.clone(), dvar.clone()
+        h = hits.view(torch.float32)
+        ids = hits[:, 0].reshape(H, W).contiguous()
+        P = [h[:, 2 + q].reshape(H, W).contiguous() for q in range(3)]
+        N = [h[:, 5 + q].reshape(H, W).contiguous() for q in range(3)]
+        img = [acc[:, q].reshape(H, W).contiguous() for q in range(C)]
+        v0 = var.reshape(H, W)
+        torch.cuda.synchronize()
+        chain = lambda: torch_svgf(ids, P, N, img, v0, passes, flags, nlog, scale, sigma, eps)  # noqa: E731
+        rimg, rvar = chain()
+        ref, rvar = torch.stack(rimg, -1).reshape(n, C), rvar.reshape(n)
+        torch.cuda.synchronize()
+        tm = measure([chain], args.rounds, window_ms=100.0, min_reps=1,
+                     names=[f"svgf {name} torch chain"])[0]
+
+        def compare(a, b):
+            fin = torch.isfinite(a) & torch.isfinite(b)
+            rel = ((a - b).abs() / b.abs().clamp_min(1e-30))[fin]
+            worst = float(rel.max()) if rel.numel() else 0.0
+            words = int((a.view(torch.int32)[fin] != b.view(torch.int32)[fin]).sum())
+            return bool((torch.isfinite(a) == torch.isfinite(b)).all()) and worst <= 1e-4, worst, words
+
+        agree_v, worst_v, words_v = compare(got, ref)
+        agree_s, worst_s, words_s = compare(gvar, rvar)
+        ok = ok and agree_v and agree_s
+        real = hits[:, 0] >= 0
+        out[name] = {
+            "W": W, "H": H, "kind": int(fkind), "hit_points": int(real.sum()), "plane_scale": scale,
+            "variance_long": m[0], "variance_short": m[1],
+            "variance_floor_ms": round(vfloor, 5),
+            "variance_long_over_floor": round(m[0]["ms_median"] / vfloor, 2),
+            "variance_short_over_floor": round(m[1]["ms_median"] / vfloor, 2),
+            "filter": m[2], "default": m[3],
+            "svgf_over_filter": round(m[3]["ms_median"] / m[2]["ms_median"], 2),
+            "floor_ms_per_pass": round(floor, 5),
+            "default_forms": "tiled up to step 4, direct beyond", "forms": forms,
+            "svgf_scratch_bytes": nbytes, "torch_chain": tm,
+            "torch_over_svgf": round(tm["ms_median"] / m[3]["ms_median"], 2),
+            "changed_share_of_hit_pixels_against_filter": round(float(
+                ((got != fdst).any(1) & real).sum() / real.sum()), 4),
+            "largest_relative_difference": worst_v, "words_that_differ": words_v,
+            "variance_largest_relative_difference": worst_s, "variance_words_that_differ": words_s,
+            "agree_to_1e-4": agree_v and agree_s}
+        print(f"svgf {name}: {m[3]['ms_median']} ms against the filter's {m[2]['ms_median']} ms, "
+              f"variance {m[0]['ms_median']} / {m[1]['ms_median']} ms (floor {vfloor:.4f}), torch "
+              f"{tm['ms_median']} ms, largest relative difference {worst_v:.3g} / {worst_s:.3g}",
+              file=sys.stderr, flush=True)
+        ctx.close()
+        del hits, acc, m2, ln, var, dvar, dst, fdst, scratch, got, gvar, ref, rvar, rimg, ids, P, N
+        del img, h, v0, real
+        torch.cuda.empty_cache()
+    return out, ok
+
+
 def torch_accumulate(cur, prev, pose, W, H, zoom, flags, nlog, scale, max_history):
     """rtg_accumulate* (include/rtg.h) as a chain of torch operations in the
     definition's operand order: the projection, index gathers for the four taps,
@@ -1166,8 +1403,12 @@ def main():
                     help="the filter's rows alone, put into FILE next to what it holds")
     ap.add_argument("--only-accumulate", action="store_true",
                     help="the temporal accumulation's rows alone, put into FILE next to what it holds")
+    ap.add_argument("--only-svgf", action="store_true",
+                    help="the variance estimate's and the variance-guided passes' rows alone, put into "
+                         "FILE next to what it holds")
     ap.add_argument("--parent-commit", default="",
-                    help="recorded with --only-fold, --only-gather, --only-filter or --only-accumulate as the parent "
+                    help="recorded with --only-fold, --only-gather, --only-filter, --only-accumulate or "
+                         "--only-svgf as the parent "
                          "of --commit")
     ap.add_argument("--order-label", default="origin-major b=10 c=10",
                     help="recorded as the library's key layout and bit counts")
@@ -1223,6 +1464,15 @@ def main():
         res["accumulate_commit"], res["accumulate_parent_commit"] = args.commit, args.parent_commit
         res["accumulate"], ok = accumulate_rows(args, torch.cuda.current_stream().cuda_stream)
         res["accumulate"]["rounds"] = args.rounds
+        finish(args, res, ok)
+    if args.only_svgf:  # (the same: it makes the accumulated frames of its own)
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["svgf_commit"], res["svgf_parent_commit"] = args.commit, args.parent_commit
+        res["svgf"], ok = svgf_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["svgf"]["rounds"] = args.rounds
         finish(args, res, ok)
     W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
     assert (W, H) == CONFIGS["c5"][:2]
