@@ -190,7 +190,9 @@ unsigned rtg_shard_global_row(unsigned localRow, unsigned rowBlock, unsigned sha
 /* Asynchronous render of shard `shard` of a W x H frame into device memory
  * dstDevice (rtg_shard_rows(...) * W rtg_vec) on `stream` (a hipStream_t, or
  * NULL for the null stream).  The camera uses global row indices, so the
- * shard's pixels are bit-identical to the same pixels of a 1-shard render. */
+ * shard's pixels are bit-identical to the same pixels of a 1-shard render.
+ * Exercised, with rtg_render_rows_device, up to a frame of 32771 x 21845 (8.59
+ * GB, past byte offset 2^32 and float index 2^31), whole and in 3 shards (tests/test_gpu_large.py). */
 int rtg_render_device(rtg_context* ctx, unsigned width, unsigned height, float zoom,
                       float aliasFactor, int stackSize, unsigned rowBlock, unsigned shard,
                       unsigned nShards, rtg_vec* dstDevice, void* stream);
@@ -254,7 +256,8 @@ typedef struct rtg_gbuf_px { /* 32 bytes */
  * scene into device memory dstDevice (rtg_shard_rows(...) * W records, 16-byte
  * aligned) on `stream`; shard rows packed as rtg_render_device packs them.
  * Uses none of the context's render scratch: it may be mixed freely with
- * rtg_render_device calls on the same context. */
+ * rtg_render_device calls on the same context.  Exercised up to 32771 x 4097
+ * records (4.30 GB), whole and in 3 shards (tests/test_gpu_large.py). */
 int rtg_gbuffer_device(rtg_context* ctx, unsigned width, unsigned height, float zoom,
                        float aliasFactor, unsigned rowBlock, unsigned shard, unsigned nShards,
                        rtg_gbuf_px* dstDevice, void* stream);
@@ -305,7 +308,8 @@ int rtg_gbuffer_host(const rtg_sphere* spheres, unsigned sphNum, unsigned width,
  * rtg_gbuffer_device on one context.  n == 0 is RTG_OK with no launch.
  * RTG_ERR_INVALID with a message, before any GPU call, for a null buffer,
  * hits not 16-byte aligned, a context without a scene, or a batch of more
- * than 2^31-1 workgroups (64 rays each). */
+ * than 2^31-1 workgroups (64 rays each).  Exercised up to n = 357 924 864 (8.6
+ * GB of rays, 11.5 GB of hits), the _indexed forms too (tests/test_gpu_large.py). */
 typedef struct rtg_ray     { rtg_vec origin, dir; } rtg_ray;      /* 24 B */
 typedef struct rtg_segment { rtg_vec a, b; }        rtg_segment;  /* 24 B */
 typedef struct rtg_hit {                                           /* 32 B */
@@ -374,7 +378,8 @@ int rtg_visible_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_segme
  * n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID with a message, before
  * any GPU call, for a null buffer, a context without a scene, stackSize
  * outside 1..RTG_MAX_STACK, an unknown walk or semantics, or a batch of more
- * than 2^31-1 workgroups (64 rays each).
+ * than 2^31-1 workgroups (64 rays each).  Exercised up to n = 357 924 864 (4.3
+ * GB of colours), the _indexed form too (tests/test_gpu_large.py).
  *
  * Out of scope: a per-ray intensity, a caller-chosen refractive material for
  * the ray's medium, and multi-GPU batches.  (Ordering a batch for coherence:
@@ -443,7 +448,8 @@ int rtg_raytrace_host(const rtg_sphere* spheres, unsigned sphNum,
  * is RTG_OK with no launch.  RTG_ERR_INVALID
  * with a message, before any GPU call, for a null ray, order or scratch
  * buffer, an unknown kind, n > 2^32 - 1, a scratch that is too small or not
- * 16-byte aligned, or a context without a scene.
+ * 16-byte aligned, or a context without a scene.  Exercised up to n =
+ * 178 957 056 rays (4.29 GB) (tests/test_gpu_large.py).
  *
  * The _indexed launches: lane k of the launch takes ray order[k] and writes
  * its result at order[k], so the outputs are in the caller's order and, for
@@ -511,7 +517,9 @@ int rtg_raytrace_indexed_device(rtg_context* ctx, const rtg_ray* raysDevice,
  * RTG_ERR_INVALID with a message, before any GPU call, for a null pointer, an
  * empty frame, an aliasFactor above 256 or NaN, stackSize outside
  * 1..RTG_MAX_STACK, an unknown walk or semantics, a context without a scene
- * (the render only) or a frame of more than 2^31-1 workgroups.
+ * (the render only) or a frame of more than 2^31-1 workgroups.  Exercised up
+ * to 32771 x 10923 pixels (the render, 4.30 GB) and 16384 x 21846 rays (8.6 GB)
+ * (tests/test_gpu_large.py).
  *
  * Out of scope: row shards and multi-GPU for posed frames, a posed G-buffer
  * call (rtg_camera_rays_device plus rtg_intersect_device gives it), a camera
@@ -562,6 +570,7 @@ int rtg_camera_rays_device(rtg_context* ctx, const rtg_camera* cam, unsigned wid
  * n == 0 writes nothing and is RTG_OK.  RTG_ERR_INVALID with a message, before
  * any GPU call, for a null pointer, an empty frame, W or H above 2^24 (their
  * floats are then exact) or a batch of more than 2^31-1 workgroups (device).
+ * Exercised up to n = 357 924 864 points (4.3 GB) (tests/test_gpu_large.py).
  * The device form is asynchronous on `stream`, takes points in device memory
  * and needs no scene; the pose is host memory, read before return. */
 int rtg_camera_project_host(const rtg_camera* cam, unsigned width, unsigned height, float zoom,
@@ -621,7 +630,8 @@ int rtg_render_camera_host(const rtg_sphere* spheres, unsigned sphNum, const rtg
  * everything rtg_render_camera* rejects, a null pose table with nViews > 0, a
  * pose table off 4-byte alignment (device form), nViews * tilesX * tilesY
  * above 2^31-1 workgroups (tiles of 8 x 8 pixels, rounded up per view) and
- * nViews * width * height * 12 not representable in size_t.
+ * nViews * width * height * 12 not representable in size_t.  Exercised up to
+ * 7 views of 8192 x 8192 (5.6 GB of frames) (tests/test_gpu_large.py).
  *
  * Out of scope: per-view sizes or zooms, a G-buffer or ray generator over
  * views, row shards and multi-GPU for views, filtering or SH projection of
@@ -724,7 +734,9 @@ int rtg_camera_cube(const rtg_vec* eye, rtg_camera out[6]);
  * null params, weight table, output or (nViews > 0) scratch, G == 0, nViews
  * not a multiple of G, K outside 1..RTG_FOLD_MAX_WEIGHTS, an unknown flag, a
  * scratch that is too small or off 16-byte alignment, and G * W * H * K floats
- * or the scratch size not representable in size_t.
+ * or the scratch size not representable in size_t.  rtg_views_fold_device is
+ * exercised up to 7 frames of 8192 x 8192 (5.6 GB) and a weight table as large
+ * (tests/test_gpu_large.py).
  *
  * Out of scope: per-group weight tables, per-view sizes, a tree-shaped group
  * sum (the sequential one is the definition; it is slow only for very large
@@ -831,6 +843,8 @@ int rtg_cube_sh_weights(unsigned res, unsigned bands, float aliasFactor, float* 
  * nDirs outside samples..RTG_AO_MAX_DIRS, an unknown flag, n > 2^32 - 1, an
  * n * K that overflows size_t (the segments), more than 2^31-1 workgroups (64
  * lanes each) or, for the fused call only, a context without a scene.
+ * Exercised up to n = 134 217 792 records (4.29 GB) and, the segments, n * K =
+ * 268 439 552 (6.4 GB) (tests/test_gpu_large.py).
  *
  * Out of scope: an _indexed form, bent normals, distance falloff, a
  * G-buffer-record input, multi-GPU batches. */
@@ -920,7 +934,7 @@ int rtg_ao_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_hit* hits,
  * n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID with a message, before
  * any GPU call, for a null hit or output buffer, a context without a scene,
  * n > 2^32 - 1, more than 2^31-1 workgroups (64 lanes each) or an unknown
- * walk.
+ * walk.  Exercised up to n = 134 217 792 records (4.29 GB) (tests/test_gpu_large.py).
  *
  * Out of scope: lights other than the context's, an _indexed form, a
  * per-light colour breakdown beyond the mask, gloss or specular terms, a
@@ -999,7 +1013,8 @@ int rtg_matte_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* 
  * unknown flag, a stackSize outside 1..RTG_MAX_STACK, an unknown walk or
  * semantics, n > 2^32 - 1, an n * K that overflows size_t (the rays), more than
  * 2^31-1 workgroups (64 lanes each) or, for the fused call only, a context
- * without a scene.
+ * without a scene.  Exercised up to n = 134 217 792 records (4.29 GB) and, the
+ * rays, n * K = 268 439 552 (6.4 GB) (tests/test_gpu_large.py).
  *
  * Out of scope: per-point direction tables, hit distances or bent normals as
  * outputs, an _indexed form, re-sorting the rays between bounces, multi-GPU
@@ -1112,7 +1127,8 @@ int rtg_gather_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light*
  * normalLog2 or kind out of range, an unknown flag, hits off 16-byte alignment
  * (device), a scratch that is too small or misaligned, and dst's byte range
  * overlapping src's or the scratch's (addresses compared as numbers, on the
- * host and on the device alike).
+ * host and on the device alike).  Exercised up to 16387 x 21846 pixels (11.5
+ * GB of records, 4.30 GB of colours) (tests/test_gpu_large.py).
  *
  * A value- and variance-driven term is rtg_svgf*'s, below, with parameter
  * records of its own.  Out of scope: rtg_gbuf_px records as guides, per-pass
@@ -1341,7 +1357,8 @@ int rtg_accumulate(int device, const rtg_hit* hits, unsigned width, unsigned hei
  * kind out of range, COUNT as the kind, an unknown flag, hits off 16-byte
  * alignment (device), a scratch that is too small or misaligned, and any
  * written byte range (var; dst, dstVar, the scratch) overlapping another of
- * the call's value buffers (addresses compared as numbers).
+ * the call's value buffers (addresses compared as numbers).  Both exercised
+ * up to 16387 x 8192 pixels (4.30 GB of records) (tests/test_gpu_large.py).
  *
  * Out of scope: fusing the variance estimate into pass 0, feeding the first
  * pass back as history, per-pass parameters, moving spheres, views and

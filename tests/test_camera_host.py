@@ -59,10 +59,11 @@ def restate_look_at(eye, target, up=(0.0, 1.0, 0.0)):
     return np.array([e, right, _cross(back, right), back], F)
 
 
-def restate_rays(cam, W, H, aa, zoom):
+def restate_rays(cam, W, H, aa, zoom, rows=None):
     """v.q = (rx * right.q + ry * up.q) + zoom * back.q, dir = vnorm(v), origin
     = eye, with (rx, ry) as test_raytrace_host.sample_rays forms them; pixel
-    order, samples i outer, j inner.  (H*W*nAA*nAA, 6) float32 and nAA*nAA."""
+    order, samples i outer, j inner.  (H*W*nAA*nAA, 6) float32 and nAA*nAA.
+    rows: only those rows of the frame, in the order given."""
     cam = np.asarray(cam, F).reshape(4, 3)
     aa, zoom = F(aa), F(zoom)
     xs, ys, asp = F(16) / F(W), F(12) / F(H), F(16) / F(12)
@@ -72,8 +73,8 @@ def restate_rays(cam, W, H, aa, zoom):
     nAA = 0
     while F(nAA) < aa:
         nAA += 1
-    y, x, i, j = np.meshgrid(np.arange(H), np.arange(W), np.arange(nAA), np.arange(nAA),
-                             indexing="ij")
+    y, x, i, j = np.meshgrid(np.arange(H) if rows is None else np.asarray(rows, np.int64),
+                             np.arange(W), np.arange(nAA), np.arange(nAA), indexing="ij")
     with np.errstate(all="ignore"):
         rx = ((x.astype(F) - halfW) * xs + j.astype(F) * st) * asp
         ry = (halfH - y.astype(F)) * ys + i.astype(F) * st

@@ -24,8 +24,9 @@ def _dot(a, b):
     return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
 
 
-def restate(rtg, sph, W, H, zoom, aa):
-    """(H, W) GBUF_DTYPE records from the definition, all samples at once."""
+def restate(rtg, sph, W, H, zoom, aa, rows=None):
+    """(H, W) GBUF_DTYPE records from the definition, all samples at once.
+    rows: only those rows of the frame, (len(rows), W) records."""
     aa, zoom = F(aa), F(zoom)
     xs, ys, asp = F(16) / F(W), F(12) / F(H), F(16) / F(12)
     st = xs / aa
@@ -33,13 +34,14 @@ def restate(rtg, sph, W, H, zoom, aa):
     nAA = 0
     while F(nAA) < aa:  # `for (int i = 0; i < aliasFactor; ++i)`
         nAA += 1
-    out = np.zeros((H, W), rtg.GBUF_DTYPE)
+    ys_ = np.arange(H) if rows is None else np.asarray(rows, np.int64)
+    out = np.zeros((len(ys_), W), rtg.GBUF_DTYPE)
     out["id"] = -1
     out["t"] = F(1000)
     if nAA == 0:
         return out
     S = nAA * nAA
-    y, x, s = np.meshgrid(np.arange(H), np.arange(W), np.arange(S), indexing="ij")
+    y, x, s = np.meshgrid(ys_, np.arange(W), np.arange(S), indexing="ij")
     i, j = (s // nAA).astype(F), (s % nAA).astype(F)
     pxX = (x.astype(F) - halfW) * xs
     pxY = (halfH - y.astype(F)) * ys
@@ -79,7 +81,7 @@ def restate(rtg, sph, W, H, zoom, aa):
         out["t"] = np.where(any_hit, pick(minT), F(1000))
         out["sample"] = np.where(any_hit, win, 0)
         idc = np.maximum(out["id"], 0)
-        N = np.zeros((H, W, 3), F)
+        N = np.zeros((len(ys_), W, 3), F)
         if len(sph):
             t = out["t"]
             e = [(F(0) + t * pick(d[q])) - sph["pos"][idc, q] for q in range(3)]
