@@ -17,7 +17,7 @@ import pytest
 import raygen
 from conftest import GOLDEN, PKG, ROOT, bits_equal, first_mismatch, load_f32, load_scene
 from raygen import scene
-from test_order_host import check_order, host_mix
+from test_order_host import check_order, host_mix, key_scenes, ladder_batch, restate_keys
 from test_raytrace_host import THREADS, mixed_rays, scene_with_lights
 
 pytestmark = pytest.mark.gpu
@@ -170,6 +170,31 @@ def test_device_order_special_batches(R, torch_cuda):
         desc = mix[o[::-1]]
         order, keys = _same_as_host(R, torch_cuda, ctx, sph, desc)
         assert (np.diff(keys.astype(np.int64)) <= 0).all() and keys[0] > keys[-1]
+    finally:
+        ctx.close()
+
+
+# ---- 1b. the key against its restatement ----
+
+@pytest.mark.parametrize("name", list(key_scenes()))
+def test_device_keys_equal_the_restatement(R, torch_cuda, name):
+    """The ladder-and-edges batch of test_order_host.py (origins and directions
+    x 2^k for every k a float32 holds, zero, -0, 3e38, 1e-45, NaN and infinite
+    components): the device's keys against the numpy restatement of rtg.h's
+    text, not by way of the host form, and its order against the stable sort of
+    those keys; rays and segments."""
+    sph = key_scenes()[name]
+    rays = ladder_batch(sph)
+    ctx = R.Context(0)
+    ctx.set_scene(sph, np.zeros(0, R.LIGHT_DTYPE))
+    try:
+        for kind in (R.ORDER_RAYS, R.ORDER_SEGMENTS):
+            order, keys = _order(R, torch_cuda, ctx, rays, kind)
+            want = restate_keys(sph, rays, kind)
+            bad = np.flatnonzero(keys != want)
+            assert not len(bad), (kind, len(bad), rays[bad[0]], hex(int(keys[bad[0]])),
+                                  hex(int(want[bad[0]])))
+            assert (order == np.argsort(want, kind="stable")).all(), kind
     finally:
         ctx.close()
 

@@ -125,6 +125,211 @@ def test_segments_are_rays_to_b_minus_a(rtg, name):
     assert (rtg.ray_order_host(sph, rec, kind=rtg.ORDER_SEGMENTS) == o_s).all()
 
 
+# ---- 5b. the key, restated from the text of include/rtg.h ----
+
+F = np.float32
+LADDER = range(-149, 128)  # every power of two a float32 holds
+
+
+def restate_key_box(sph):
+    """(lo, hi, scale), three float32 each: lo = min(c - |r|), hi = max(c + |r|)
+    over the spheres whose centre and radius are finite, [-1, 1]^3 when none is
+    left; scale = 1024 / (hi - lo), or 0 when hi <= lo or the width or the
+    quotient is not finite."""
+    c, r = sph["pos"].astype(F).reshape(-1, 3), np.abs(sph["radius"].astype(F)).reshape(-1)
+    keep = np.isfinite(c).all(1) & np.isfinite(r)
+    c, r = c[keep], r[keep]
+    if not len(c):
+        lo, hi = np.full(3, -1, F), np.full(3, 1, F)
+    else:
+        with np.errstate(over="ignore"):
+            lo, hi = (c - r[:, None]).min(0), (c + r[:, None]).max(0)
+    with np.errstate(all="ignore"):
+        w = hi - lo
+        q = F(1024) / w
+    ok = (hi > lo) & np.isfinite(w) & np.isfinite(q)
+    assert lo.dtype == F and q.dtype == F
+    return lo, hi, np.where(ok, q, F(0)).astype(F)
+
+
+def _clamp_int(x):
+    """(int)clamp(x, 0, 1023), the clamp in float with NaN going to 0."""
+    x = np.where(np.isnan(x), F(0), x)
+    x = np.minimum(np.maximum(x, F(0)), F(1023))
+    return x.astype(np.int64).astype(np.uint64)
+
+
+def _spread(v, stride, at):
+    out = np.zeros(v.shape, np.uint64)
+    for i in range(10):
+        out |= ((v >> np.uint64(i)) & np.uint64(1)) << np.uint64(at + stride * i)
+    return out
+
+
+def restate_bins(d):
+    """(u, v) octahedral bins of float32 directions (n, 3)."""
+    dx, dy, dz = (d[:, q].astype(F) for q in range(3))
+    one = F(1)
+    with np.errstate(all="ignore"):
+        s = (np.abs(dx) + np.abs(dy)) + np.abs(dz)
+        px, py = dx / s, dy / s
+        sx = np.where(dx < 0, -one, one)  # sign(0) = +1, and -0 is a zero
+        sy = np.where(dy < 0, -one, one)
+        fx = (one - np.abs(py)) * sx
+        fy = (one - np.abs(px)) * sy
+        low = dz < 0
+        px, py = np.where(low, fx, px), np.where(low, fy, py)
+        u = _clamp_int((px + one) * F(512))
+        v = _clamp_int((py + one) * F(512))
+    none = (s == 0) | ~np.isfinite(s)
+    assert s.dtype == F and px.dtype == F
+    return np.where(none, np.uint64(0), u), np.where(none, np.uint64(0), v)
+
+
+def restate_keys(sph, rays, kind=0):
+    """uint64 keys of (n, 6) float32 rays, or of segments (a, b) as the rays
+    (a, b - a) with the difference taken in float."""
+    r = np.ascontiguousarray(rays, F).reshape(-1, 6)
+    o, d = r[:, :3], r[:, 3:]
+    if kind:
+        with np.errstate(all="ignore"):
+            d = (d - o).astype(F)
+    lo, _, scale = restate_key_box(sph)
+    key = np.zeros(len(r), np.uint64)
+    with np.errstate(all="ignore"):
+        for q in range(3):
+            cell = _clamp_int((o[:, q] - lo[q]) * scale[q])
+            key |= _spread(cell, 3, 20 + q)
+    u, v = restate_bins(d)
+    return key | _spread(u, 2, 0) | _spread(v, 2, 1)
+
+
+def key_scenes():
+    """name -> spheres: reference, 200, c5, no sphere; 200 with a NaN centre, an
+    infinite centre component and an infinite and a NaN radius added (all four
+    skipped); one point sphere (every axis degenerate); two point spheres apart
+    in x only (y and z degenerate); two spheres whose box is wider than FLT_MAX."""
+    out = {name: scene(name) for name in ("reference", 200, "c5", 0)}
+    odd = np.concatenate([scene(200), scene(12)[:4]])
+    odd[200]["pos"][1] = np.nan
+    odd[201]["pos"][2] = -np.inf
+    odd[202]["radius"] = np.inf
+    odd[203]["radius"] = np.nan
+    out["skipped"] = odd
+    point = scene(12)[:1].copy()
+    point["radius"] = 0
+    out["point"] = point
+    line = scene(12)[:2].copy()
+    line["radius"] = 0
+    line["pos"][1] = line["pos"][0]
+    line["pos"][1][0] += F(3)
+    out["line"] = line
+    wide = scene(12)[:2].copy()
+    wide["pos"][0] = (-3e38, 0, -1)
+    wide["pos"][1] = (3e38, 1, -2)
+    out["wide"] = wide
+    return out
+
+
+def ladder_batch(sph, seed=77):
+    """64 rays of raygen.inside per k of LADDER with origins and directions
+    x 2^k, then 3840 rays with edges planted: zero directions, -0 components,
+    components of 3e38 (the sum overflows) and 1e-45, NaN and +-inf origin
+    components, the six axis directions, and every 3rd of the whole batch with
+    dz < 0 by construction of raygen.inside.  (21 568, 6) float32."""
+    rng = np.random.default_rng(seed)
+    geo = sph if len(sph) and np.isfinite(sph["pos"]).all() and np.isfinite(sph["radius"]).all() \
+        else scene(200)
+    base = raygen.inside(rng, geo, 64 * len(LADDER)).astype(np.float64)
+    k = np.repeat(np.asarray(LADDER), 64)
+    with np.errstate(over="ignore", under="ignore"):
+        lad = (base * np.ldexp(1.0, k)[:, None]).astype(F)
+    e = raygen.inside(rng, geo, 3840)
+    i = np.arange(len(e))
+    e[i % 16 == 0, 3:] = 0
+    e[i % 16 == 1, 3 + (i[i % 16 == 1] // 16) % 3] = -0.0
+    e[i % 16 == 2, 3 + (i[i % 16 == 2] // 16) % 3] = 3e38
+    e[i % 16 == 3, 3:] = (3e38, -3e38, 3e38)
+    e[i % 16 == 4, 3 + (i[i % 16 == 4] // 16) % 3] = 1e-45
+    e[i % 16 == 5, 3:] = (1e-45, 0, -1e-45)
+    vals = np.asarray([np.nan, np.inf, -np.inf], F)
+    at = np.flatnonzero(i % 16 == 6)
+    e[at, (at // 16) % 3] = vals[(at // 48) % 3]
+    at = np.flatnonzero(i % 16 == 7)
+    e[at, 3:] = 0
+    e[at, 3 + (at // 16) % 3] = np.where((at // 48) % 2 == 0, 1, -1)
+    at = np.flatnonzero(i % 16 == 8)  # -0 in x or y under dz < 0: the fold's sign(0)
+    e[at, 3 + (at // 16) % 2] = -0.0
+    e[at, 5] = -np.abs(e[at, 5])
+    at = np.flatnonzero(i % 16 == 9)  # on the fold line: dz = -0 and +0
+    e[at, 5] = np.where((at // 16) % 2 == 0, -0.0, 0.0)
+    out = np.concatenate([lad, e]).astype(F)
+    assert (out[:, 5] < 0).mean() > 0.3 and np.signbit(out[:, 3:5][out[:, 3:5] == 0]).any()
+    return out
+
+
+@pytest.mark.parametrize("name", list(key_scenes()))
+def test_keys_equal_the_restatement(rtg, name):
+    sph = key_scenes()[name]
+    rays = ladder_batch(sph)
+    lo, hi, scale = restate_key_box(sph)
+    if name in ("point", "line", "wide"):
+        assert (scale == 0).any()
+    if name == 0:
+        assert (lo == -1).all() and (hi == 1).all() and (scale == 512).all()
+    if name == "skipped":
+        assert all((a == b).all() for a, b in zip((lo, hi, scale), restate_key_box(scene(200))))
+    for kind in (0, 1):
+        order, keys = rtg.ray_order_host(sph, rays, kind=kind, threads=4, keys=True)
+        want = restate_keys(sph, rays, kind)
+        bad = np.flatnonzero(keys != want)
+        assert not len(bad), (kind, len(bad), rays[bad[0]], hex(int(keys[bad[0]])), hex(int(want[bad[0]])))
+        assert (order == np.argsort(want, kind="stable")).all()
+    if name in ("reference", 200, "c5"):
+        assert len(np.unique(want >> np.uint64(20))) > 500 and len(np.unique(want & np.uint64(0xFFFFF))) > 5000
+
+
+def _unspread(key, stride, at):
+    out = np.zeros(key.shape, np.int64)
+    for i in range(10):
+        out |= (((key >> np.uint64(at + stride * i)) & np.uint64(1)) << np.uint64(i)).astype(np.int64)
+    return out
+
+
+def test_bin_centre_lies_within_a_bin_of_the_direction(rtg):
+    """In float64: the centre of a ray's bin, taken back through the inverse
+    octahedral map, is within one bin of the ray's direction.  A bin is 2^-9
+    wide in p, so the centre is at most 2^-10 from p in each coordinate; on the
+    octahedron |x| + |y| + |z| = 1 the point then moves by at most (du, dv, |du|
+    + |dv|), a length of sqrt(6) 2^-10, on either side of the fold (the fold
+    swaps and reflects the coordinates and is continuous across its edges).
+    The octahedron's points are at least 1 / sqrt(3) from the centre, so the
+    angle is at most asin(sqrt(18) 2^-10); the float32 rounding of s, dx / s
+    and (p + 1) 512 moves p by a few 2^-24, far less than the 1e-5 allowed here."""
+    sph = scene(200)
+    rays = ladder_batch(sph)
+    keys = rtg.ray_order_host(sph, rays, keys=True)[1]
+    d32 = rays[:, 3:]
+    with np.errstate(all="ignore"):
+        s32 = (np.abs(d32[:, 0]) + np.abs(d32[:, 1])) + np.abs(d32[:, 2])
+    ok = np.isfinite(s32) & (s32 > 0)
+    assert ok.mean() > 0.9
+    d = d32[ok].astype(np.float64)
+    d /= np.abs(d).max(1, keepdims=True)  # (keeps the squares in range)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    u, v = _unspread(keys[ok], 2, 0), _unspread(keys[ok], 2, 1)
+    pu, pv = (u + 0.5) / 512 - 1, (v + 0.5) / 512 - 1
+    z = 1 - np.abs(pu) - np.abs(pv)
+    x = np.where(z < 0, (1 - np.abs(pv)) * np.where(pu < 0, -1.0, 1.0), pu)
+    y = np.where(z < 0, (1 - np.abs(pu)) * np.where(pv < 0, -1.0, 1.0), pv)
+    c = np.stack([x, y, z], 1)
+    c /= np.linalg.norm(c, axis=1, keepdims=True)
+    angle = np.arccos(np.clip((c * d).sum(1), -1, 1))
+    bound = np.arcsin(np.sqrt(18.0) * 2.0 ** -10) + 1e-5
+    assert angle.max() <= bound, (angle.max(), bound, rays[ok][np.argmax(angle)])
+    assert angle.max() > bound / 8  # and the bound is not slack by an order of magnitude
+
+
 # ---- 6. thread independence ----
 
 def test_thread_independence(rtg):
