@@ -34,6 +34,8 @@
  *     loop over hasClearLineOfSight in the reference)    rtg_ao_segments[_device|_host]
  *   calculateMatte for a caller's own hit points       rtg_matte[_device|_host]
  *     raytracer.h:313-367
+ *   (the light of a grid of baked SH probes at a hit    rtg_irradiance[_device|_host],
+ *     point: the consumer of the folded views)            rtg_probe_grid_points, rtg_probe_grid_poses
  *   (one-bounce indirect light of a hit point: the      rtg_gather[_device|_host],
  *     caller's loop over rayTrace in the reference)       rtg_gather_rays[_device|_host]
  *   (a frame of those per-pixel signals smoothed along   rtg_filter[_device|_host],
@@ -957,6 +959,146 @@ int rtg_matte(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_
 int rtg_matte_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_light* lights,
                    unsigned lgtNum, const rtg_hit* hits, size_t n, rtg_vec* outHost,
                    unsigned long long* litHost, int walk, int nthreads);
+
+/* ---- irradiance: a grid of SH probes per hit point ----
+ * Hit points go in, the light that a lattice of baked probes holds for each
+ * point comes out, with the interpolation weight that was left: the consumer
+ * of rtg_render_views_fold*'s coefficients, and the table-driven alternative
+ * to rtg_gather* for indirect light.  A plain trilinear fetch is not usable:
+ * probes inside a sphere and probes behind a wall leak their light, so the
+ * lookup leaves out invalid probes, probes behind the point's tangent plane
+ * and probes the point cannot see, which makes it a scene query (rtg_visible's
+ * rule for eight segments per point that share their origin), fused: no n x 8
+ * segment buffer on the caller's side.  The call takes n rtg_hit records
+ * exactly as rtg_intersect* writes them and pairs with rtg_ao*, rtg_matte* and
+ * rtg_gather* on the same records.
+ *
+ * THE GRID.  Probe (ix, iy, iz) of an nx x ny x nz lattice has index
+ * p = (iz * ny + iy) * nx + ix and position X_p.q = origin.q + (float)i_q *
+ * step.q.  Its K = bands * bands coefficients (rtg_vec) are coeffs[p * K + k],
+ * k = l * (l + 1) + m: exactly what rtg_render_views_fold* writes with G = 6,
+ * one group per probe in index order, and rtg_cube_sh_weights' table, so a
+ * bake feeds the lookup with no reshuffle.  valid[p] (RTG_IRR_VALID only) is
+ * one byte per probe, 0: leave the probe out.  The validity bytes are the
+ * caller's: rtg_contains*(rtg_probe_grid_points) < 0 gives them (a probe
+ * inside a sphere sees only that sphere's inside).
+ *
+ * ARITHMETIC, all in float with no contraction and in this order.  A record
+ * with id < 0 gets (0, 0, 0) and weight +0.f and makes no query.  For a record
+ * with id >= 0 (`id` is read for its sign only, `t` is not read, N = normal is
+ * used as given: not normalised, a flipped or scaled normal is legal):
+ *   start    A.q = P.q + bias * N.q                        (rtg_ao*'s start point)
+ *   cell     per axis q:  g = (A.q - origin.q) / step.q
+ *              if !(g >= 0.f) g = 0.f                       (NaN goes to 0)
+ *              if g > (float)(n_q - 1) g = (float)(n_q - 1)
+ *              i0 = (unsigned)g, lowered to n_q - 2 when above it and n_q >= 2
+ *              f = g - (float)i0
+ *              i1 = i0 + 1 if that is < n_q, else i0
+ *   basis    once per point, c0 .. c4 the constants of the orthonormal real
+ *            basis (rtg_cube_sh_weights' Y_k) rounded from double to float,
+ *            c0 = 0.28209479177387814, c1 = 0.4886025119029199, c2 =
+ *            1.0925484305920792, c3 = 0.31539156525252005, c4 =
+ *            0.5462742152960396:
+ *              b0 = lobe[0] * c0
+ *              b1 = lobe[1] * (c1 * N.y)    b2 = lobe[1] * (c1 * N.z)
+ *              b3 = lobe[1] * (c1 * N.x)
+ *              b4 = lobe[2] * (c2 * (N.x * N.y))
+ *              b5 = lobe[2] * (c2 * (N.y * N.z))
+ *              b6 = lobe[2] * (c3 * (3.f * (N.z * N.z) - 1.f))
+ *              b7 = lobe[2] * (c2 * (N.x * N.z))
+ *              b8 = lobe[2] * (c4 * (N.x * N.x - N.y * N.y))
+ *   corners  W = +0.f, acc = (0, 0, 0); for c = 0 .. 7 in order: bits cx = c &
+ *            1, cy = (c >> 1) & 1, cz = c >> 2 pick i1 (set) or i0 per axis,
+ *            and t_q = f_q (set) or 1.f - f_q;  w = (t_x * t_y) * t_z.  The
+ *            corner's probe p is LEFT OUT if any of these holds:
+ *              !(w > 0.f)                                   (zero or NaN)
+ *              RTG_IRR_VALID and valid[p] == 0
+ *              RTG_IRR_FACING and !(s > 0.f), with d = X_p - A and
+ *                s = (N.x * d.x + N.y * d.y) + N.z * d.z
+ *              RTG_IRR_VISIBLE and the segment (A, X_p) is blocked under
+ *                rtg_visible's rule, word for word
+ *            (the query has no side effect: it is made only for corners that
+ *            passed the other tests).  A kept corner does
+ *              e = (+0.f, +0.f, +0.f)
+ *              for k = 0 .. K-1:  e.q = e.q + b_k * coeffs[p * K + k].q
+ *              W = W + w;  acc.q = acc.q + w * e.q
+ *   result   out[i].q = acc.q / W if W > 0.f, else (0, 0, 0); NaN words are
+ *            stored as 0xFFC00000, as every record's.  weight[i] = W (`weight`
+ *            may be NULL): where it is 0 no probe reached the point and the
+ *            caller falls back to its ambient term.
+ * So an axis with n_q == 1 has f = 0: its second corner has weight 0 and is
+ * never fetched (a flat floor-plan grid), and a point outside the lattice
+ * takes the boundary cell's edge.  Coefficients are used as given, so a NaN
+ * or infinite coefficient follows the arithmetic: bake with
+ * RTG_FOLD_SKIP_NONFINITE.  The result does not depend on lights, stackSize
+ * or rtg_context_set_semantics.
+ *
+ * lobe[l] scales band l: RTG_IRR_LOBE_RADIANCE reconstructs the baked radiance
+ * along N, RTG_IRR_LOBE_COSINE is the clamped-cosine convolution (irradiance /
+ * pi, the radiance a white matte surface leaves with).
+ *
+ * rtg_irradiance_device is the FUSED call, asynchronous on `stream`: it
+ * allocates nothing, takes none of the context's render scratch and may be
+ * mixed with every other call on the context.  `grid` and `params` are host
+ * memory in every call, read before the call returns.  The context needs a
+ * scene only with RTG_IRR_VISIBLE; without that flag a context with no scene
+ * is legal, as with rtg_views_fold_device.
+ *
+ * n == 0 is RTG_OK with no launch.  RTG_ERR_INVALID with a message, before
+ * any GPU call, for a null hit, coefficient, params, grid or output pointer,
+ * a null `valid` with RTG_IRR_VALID, a step that is not finite or not > 0, a
+ * non-finite origin, a dimension outside 1..2^20, nx * ny * nz * K > 2^31 - 1,
+ * bands outside 1..3, an unknown flag, an unknown walk, n > 2^32 - 1, more
+ * than 2^31-1 workgroups (64 lanes each), or RTG_IRR_VISIBLE on a context
+ * without a scene.
+ *
+ * Out of scope: smooth backface wraps, Chebyshev or depth-moment visibility
+ * (DDGI), bands above 3, per-probe offsets, probes off a lattice, an _indexed
+ * form, a device-side pose generator, multi-GPU batches. */
+typedef struct rtg_probe_grid {
+  rtg_vec origin;        /* position of probe (0,0,0) */
+  rtg_vec step;          /* spacing per axis; finite and > 0 */
+  unsigned nx, ny, nz;   /* >= 1 each, <= 2^20 each; nx*ny*nz*K <= 2^31 - 1 */
+  unsigned bands;        /* 1..3; K = bands*bands coefficients (rtg_vec) per probe */
+} rtg_probe_grid;
+
+#define RTG_IRR_VALID    1  /* a corner whose valid[] byte is 0 is left out */
+#define RTG_IRR_FACING   2  /* a corner not in front of the point's tangent plane is left out */
+#define RTG_IRR_VISIBLE  4  /* a corner the point does not see is left out */
+typedef struct rtg_irradiance_params {
+  float bias;      /* start offset along the normal, used as given (rtg_ao's) */
+  float lobe[3];   /* per-band factor l = 0, 1, 2; used as given */
+  unsigned flags;  /* an unknown bit is RTG_ERR_INVALID */
+} rtg_irradiance_params;
+#define RTG_IRR_LOBE_RADIANCE {1.f, 1.f, 1.f}          /* reconstructs the baked radiance along N */
+#define RTG_IRR_LOBE_COSINE   {1.f, 2.f / 3.f, 0.25f}  /* clamped-cosine irradiance / pi */
+/* Host conveniences whose bits ARE part of the contract (one multiplication
+ * and one addition per word, and a copy): the nx * ny * nz probe positions in
+ * index order, and rtg_camera_cube of each, 6 per probe, probe-major: the pose
+ * table of a bake with G = 6.  RTG_ERR_INVALID for a null pointer or a grid
+ * the lookup rejects. */
+int rtg_probe_grid_points(const rtg_probe_grid* grid, rtg_vec* out);
+int rtg_probe_grid_poses(const rtg_probe_grid* grid, rtg_camera* out);
+/* The fused kernel: n colours into outDevice (12 B each) and, when
+ * weightDevice is not NULL, n weights.  validDevice may be NULL without
+ * RTG_IRR_VALID. */
+int rtg_irradiance_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
+                          const rtg_probe_grid* grid, const rtg_vec* coeffsDevice,
+                          const unsigned char* validDevice, const rtg_irradiance_params* params,
+                          rtg_vec* outDevice, float* weightDevice, void* stream);
+/* One-shot: uploads the scene, the hits and the tables, runs on `device`,
+ * downloads the colours and (weightHost not NULL) the weights. */
+int rtg_irradiance(int device, const rtg_sphere* spheres, unsigned sphNum, const rtg_hit* hits,
+                   size_t n, const rtg_probe_grid* grid, const rtg_vec* coeffs,
+                   const unsigned char* valid, const rtg_irradiance_params* params,
+                   rtg_vec* outHost, float* weightHost);
+/* The same on the host, no GPU call.  walk 0: plain loops over every corner
+ * and sphere (the yardstick).  walk 1: the kernel's own path over the packed
+ * tables, as rtg_visible_host.  nthreads <= 0: 1. */
+int rtg_irradiance_host(const rtg_sphere* spheres, unsigned sphNum, const rtg_hit* hits, size_t n,
+                        const rtg_probe_grid* grid, const rtg_vec* coeffs,
+                        const unsigned char* valid, const rtg_irradiance_params* params,
+                        rtg_vec* outHost, float* weightHost, int walk, int nthreads);
 
 /* ---- gather: a hemisphere of rayTrace colours per hit point ----
  * Hit points go in, one colour per point comes out: the weighted sum of

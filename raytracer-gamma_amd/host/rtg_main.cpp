@@ -94,6 +94,20 @@ static void usage() {
   printf("      --matte      FILE   Also write the frame's direct light (rtg_matte_device of every\n");
   printf("                           primary hit at aa 1, from --camera or the identity pose) as a\n");
   printf("                           P6 PPM, scaled by its own largest component like the render\n");
+  printf("      --probe-grid SPEC    Bake a grid of SH light probes over the scene's bounds:\n");
+  printf("                           nx,ny,nz[,res[,bands]] (probe (0,0,0) at the bounds' low corner,\n");
+  printf("                           the last at the high one; res x res cube faces per probe, 16\n");
+  printf("                           unless given, at aa 1; 1..3 SH bands, 3 unless given; the fused\n");
+  printf("                           rtg_render_views_fold_device with RTG_FOLD_SKIP_NONFINITE over\n");
+  printf("                           rtg_probe_grid_poses, validity from rtg_contains_device); needs\n");
+  printf("                           --irradiance\n");
+  printf("      --irradiance FILE    Also write the grid's light at every primary hit at aa 1, from\n");
+  printf("                           --camera or the identity pose (rtg_irradiance_device with\n");
+  printf("                           RTG_IRR_LOBE_COSINE) as a P6 PPM, scaled by its own largest\n");
+  printf("                           component like the render\n");
+  printf("      --irr-flags  LIST    Which probes a point leaves out: a comma list of valid, facing,\n");
+  printf("                           visible, or none (default valid,facing,visible)\n");
+  printf("      --irr-bias   B       The lookup's start offset along the normal (default 0.001)\n");
   printf("      --gather     SPEC    Also write the frame's one-bounce indirect light: K[,bias[,seed]]\n");
   printf("                           (rtg_gather_device of every primary hit at aa 1, from --camera\n");
   printf("                           or the identity pose: K probes of rtg_ao_directions(K), weights\n");
@@ -130,6 +144,47 @@ static bool parse_pose(const char* s, rtg_camera* out) {
   const rtg_vec eye = {v[0], v[1], v[2]}, target = {v[3], v[4], v[5]}, up = {v[6], v[7], v[8]};
   check(rtg_camera_look_at(&eye, &target, &up, out), "rtg_camera_look_at");
   return true;
+}
+
+// "valid,facing,visible" (any subset, or "none") as RTG_IRR_* bits; false when it is not that.
+static bool parse_irr_flags(const char* s, unsigned* flags) {
+  *flags = 0;
+  if (!strcmp(s, "none")) return true;
+  while (*s) {
+    const size_t k = strcspn(s, ",");
+    if (k == 5 && !strncmp(s, "valid", k)) *flags |= RTG_IRR_VALID;
+    else if (k == 6 && !strncmp(s, "facing", k)) *flags |= RTG_IRR_FACING;
+    else if (k == 7 && !strncmp(s, "visible", k)) *flags |= RTG_IRR_VISIBLE;
+    else return false;
+    s += k;
+    if (*s == ',' && !*++s) return false;
+  }
+  return *flags != 0;
+}
+
+// The grid of --probe-grid over the scene's bounds, in float: per axis lo = the
+// least pos - |radius| and hi = the greatest pos + |radius| (comparisons as
+// written: a NaN never wins), origin = lo and step = (hi - lo) / (float)(n - 1)
+// for n >= 2; 1.f for n == 1 or a step that is not > 0.  No sphere: [-1, 1]^3.
+static rtg_probe_grid grid_over(const std::vector<rtg_sphere>& spheres, const unsigned dims[3],
+                                unsigned bands) {
+  float lo[3] = {-1.f, -1.f, -1.f}, hi[3] = {1.f, 1.f, 1.f};
+  for (size_t i = 0; i < spheres.size(); ++i) {
+    const float c[3] = {spheres[i].pos.x, spheres[i].pos.y, spheres[i].pos.z};
+    const float r = fabsf(spheres[i].radius);
+    for (int q = 0; q < 3; ++q) {
+      const float a = c[q] - r, b = c[q] + r;
+      if (i == 0 || a < lo[q]) lo[q] = a;
+      if (i == 0 || b > hi[q]) hi[q] = b;
+    }
+  }
+  float st[3];
+  for (int q = 0; q < 3; ++q) {
+    st[q] = dims[q] >= 2 ? (hi[q] - lo[q]) / (float)(dims[q] - 1) : 1.f;
+    if (!(st[q] > 0.f)) st[q] = 1.f;
+  }
+  return rtg_probe_grid{{lo[0], lo[1], lo[2]}, {st[0], st[1], st[2]}, dims[0], dims[1], dims[2],
+                        bands};
 }
 
 // "PASSES[,planeScale[,normalLog2]]" of --ao-filter and --gather-filter; false when it is not that.
@@ -279,7 +334,11 @@ int main(int argc, char** argv) {
   unsigned long long seed = 42;
   float aa = 3.f, zoom = -4.f;
   std::string out = "testPPM.ppm", sceneIn, sceneOut, gbufOut, raysIn, hitsOut, radianceOut, aoOut;
-  std::string matteOut, gatherOut;
+  std::string matteOut, gatherOut, irrOut;
+  bool probeGrid = false;
+  unsigned gridDims[3] = {0, 0, 0}, gridRes = 16, gridBands = 3;
+  rtg_irradiance_params irrParams = {1.0e-3f, RTG_IRR_LOBE_COSINE,
+                                     RTG_IRR_VALID | RTG_IRR_FACING | RTG_IRR_VISIBLE};
   bool ao = false, matte = false, gather = false, gatherSkip = false;
   rtg_gather_params gatherParams = {0, 1.0e-3f, 0, 0};
   rtg_ao_params aoParams = {0, 0.f, 1.0e-3f, 0, 0};
@@ -426,6 +485,25 @@ int main(int argc, char** argv) {
     } else if (!strcmp(a, "--matte")) {
       matteOut = need(a);
       matte = true;
+    } else if (!strcmp(a, "--probe-grid")) {
+      char tail = 0;
+      const int k = sscanf(need(a), "%u,%u,%u,%u,%u%c", gridDims, gridDims + 1, gridDims + 2,
+                           &gridRes, &gridBands, &tail);
+      if (k < 3 || k > 5 || !gridDims[0] || !gridDims[1] || !gridDims[2] || !gridRes ||
+          gridBands < 1 || gridBands > 3) {
+        printf("Invalid probe grid (nx,ny,nz[,res[,bands]], each >= 1, bands in 1..3)\n");
+        return 1;
+      }
+      probeGrid = true;
+    } else if (!strcmp(a, "--irradiance")) {
+      irrOut = need(a);
+    } else if (!strcmp(a, "--irr-flags")) {
+      if (!parse_irr_flags(need(a), &irrParams.flags)) {
+        printf("Invalid irradiance flags (a comma list of valid, facing, visible, or none)\n");
+        return 1;
+      }
+    } else if (!strcmp(a, "--irr-bias")) {
+      irrParams.bias = strtof(need(a), nullptr);
     } else if (!strcmp(a, "--scene")) {
       sceneIn = need(a);
     } else if (!strcmp(a, "--save-scene")) {
@@ -464,6 +542,12 @@ int main(int argc, char** argv) {
 
   if (matte && (matteOut.empty() || matteOut == out || W == 0 || H == 0)) {
     printf("Invalid matte (a file other than --out, for a frame with pixels)\n");
+    return 1;
+  }
+
+  if (probeGrid == irrOut.empty() || (probeGrid && (irrOut == out || W == 0 || H == 0))) {
+    printf("--probe-grid and --irradiance go together (a file other than --out, for a frame with "
+           "pixels)\n");
     return 1;
   }
 
@@ -506,9 +590,9 @@ int main(int argc, char** argv) {
 
   const bool manyViews = cube || !viewsIn.empty();
   if (manyViews && (cube == !viewsIn.empty() || posed || gpus || ao || matte || gather ||
-                    !gbufOut.empty() || !raysIn.empty())) {
+                    probeGrid || !gbufOut.empty() || !raysIn.empty())) {
     printf("--views or --cube renders alone: one of them, on one device, without --camera,\n"
-           "--gbuffer, --rays, --ao, --matte or --gather\n");
+           "--gbuffer, --rays, --ao, --matte, --gather or --probe-grid\n");
     return 1;
   }
   if ((shBands != 0) != !shOut.empty() || (shBands && !cube)) {
@@ -845,6 +929,97 @@ int main(int argc, char** argv) {
     }
     printf("Wrote %s (%ux%u, direct light of %u lights per primary hit, max %.8g)\n",
            matteOut.c_str(), W, H, nLgt, (double)lightMax);
+  }
+
+  if (probeGrid) {  // the bake, then pose -> primary rays -> hits -> the grid's light -> bytes
+    const size_t n = (size_t)W * H;
+    if (!posed) rtg_camera_identity(&camera);
+    const rtg_probe_grid grid = grid_over(spheres, gridDims, gridBands);
+    const size_t probes = (size_t)grid.nx * grid.ny * grid.nz, nV = 6 * probes;
+    const unsigned K = gridBands * gridBands;
+    std::vector<rtg_vec> pts(probes);
+    check(rtg_probe_grid_points(&grid, pts.data()), "rtg_probe_grid_points");
+    std::vector<rtg_camera> poses(nV);
+    check(rtg_probe_grid_poses(&grid, poses.data()), "rtg_probe_grid_poses");
+    std::vector<float> wts((size_t)6 * gridRes * gridRes * K);
+    check(rtg_cube_sh_weights(gridRes, gridBands, 1.f, wts.data()), "rtg_cube_sh_weights");
+    const rtg_fold_params fp = {6, K, RTG_FOLD_SKIP_NONFINITE};
+    size_t scratchBytes = 0;
+    check(rtg_views_fold_scratch(nV, gridRes, gridRes, K, &scratchBytes), "rtg_views_fold_scratch");
+    rtg_context* ctx = nullptr;
+    check(rtg_context_create((int)device, &ctx), "rtg_context_create");
+    check(rtg_context_set_semantics(ctx, semantics), "rtg_context_set_semantics");
+    check(rtg_context_set_scene(ctx, spheres.data(), nSph, lights.data(), nLgt),
+          "rtg_context_set_scene");
+    rtg_camera* dPoses = nullptr;
+    float* dW = nullptr;
+    rtg_vec *dCoef = nullptr, *dPts = nullptr, *dl = nullptr;
+    void* dScratch = nullptr;
+    int* dIn = nullptr;
+    unsigned char *dValid = nullptr, *db = nullptr;
+    rtg_ray* dr = nullptr;
+    rtg_hit* dh = nullptr;
+    float* dmax = nullptr;
+    if (hipMalloc(&dPoses, nV * sizeof(rtg_camera)) != hipSuccess ||
+        hipMalloc(&dW, wts.size() * sizeof(float)) != hipSuccess ||
+        hipMalloc(&dCoef, probes * K * sizeof(rtg_vec)) != hipSuccess ||
+        hipMalloc(&dScratch, scratchBytes) != hipSuccess ||
+        hipMalloc(&dPts, probes * sizeof(rtg_vec)) != hipSuccess ||
+        hipMalloc(&dIn, probes * sizeof(int)) != hipSuccess ||
+        hipMalloc(&dValid, probes) != hipSuccess ||
+        hipMalloc(&dr, n * sizeof(rtg_ray)) != hipSuccess ||
+        hipMalloc(&dh, n * sizeof(rtg_hit)) != hipSuccess ||
+        hipMalloc(&dl, n * sizeof(rtg_vec)) != hipSuccess ||
+        hipMalloc(&dmax, sizeof(float)) != hipSuccess || hipMalloc(&db, n * 3) != hipSuccess)
+      check(RTG_ERR_NOMEM, "hipMalloc");
+    if (hipMemcpy(dPoses, poses.data(), nV * sizeof(rtg_camera), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMemcpy(dW, wts.data(), wts.size() * sizeof(float), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMemcpy(dPts, pts.data(), probes * sizeof(rtg_vec), hipMemcpyHostToDevice) != hipSuccess)
+      check(RTG_ERR_HIP, "upload");
+    check(rtg_render_views_fold_device(ctx, dPoses, nV, gridRes, gridRes, -1.f, 1.f,
+                                       (int)depth + 1, &fp, dW, dCoef, nullptr, dScratch,
+                                       scratchBytes, nullptr),
+          "rtg_render_views_fold_device");
+    // validity: a probe inside a sphere is left out (rtg_contains* < 0 is valid)
+    check(rtg_contains_device(ctx, dPts, probes, dIn, nullptr), "rtg_contains_device");
+    std::vector<int> in(probes);
+    if (hipMemcpy(in.data(), dIn, probes * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+      check(RTG_ERR_HIP, "readback");
+    std::vector<unsigned char> valid(probes);
+    size_t nValid = 0;
+    for (size_t p = 0; p < probes; ++p) nValid += valid[p] = in[p] < 0;
+    if (hipMemcpy(dValid, valid.data(), probes, hipMemcpyHostToDevice) != hipSuccess)
+      check(RTG_ERR_HIP, "upload");
+    check(rtg_camera_rays_device(ctx, &camera, W, H, zoom, 1.f, dr, nullptr),
+          "rtg_camera_rays_device");
+    check(rtg_intersect_device(ctx, dr, n, dh, nullptr), "rtg_intersect_device");
+    check(rtg_irradiance_device(ctx, dh, n, &grid, dCoef, dValid, &irrParams, dl, nullptr,
+                                nullptr),
+          "rtg_irradiance_device");
+    check(rtg_max_colour_device(ctx, dl, n, dmax, nullptr), "rtg_max_colour_device");
+    check(rtg_ppm_bytes_device(ctx, dl, n, dmax, db, nullptr), "rtg_ppm_bytes_device");
+    std::vector<unsigned char> bytes(n * 3);
+    float lightMax = 0.f;
+    if (hipMemcpy(bytes.data(), db, n * 3, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&lightMax, dmax, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      check(RTG_ERR_HIP, "readback");
+    for (void* d : {(void*)dPoses, (void*)dW, (void*)dCoef, dScratch, (void*)dPts, (void*)dIn,
+                    (void*)dValid, (void*)dr, (void*)dh, (void*)dl, (void*)dmax, (void*)db})
+      (void)hipFree(d);
+    rtg_context_destroy(ctx);
+    FILE* f = fopen(irrOut.c_str(), "wb");
+    if (!f || fprintf(f, "P6\n%u %u\n255\n", W, H) < 0 ||
+        fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f) != 0) {
+      fprintf(stderr, "Error: can't write %s\n", irrOut.c_str());
+      exit(EXIT_FAILURE);
+    }
+    printf("Wrote %s (%ux%u, light of a %ux%ux%u grid of SH%u probes from %.9g,%.9g,%.9g by "
+           "%.9g,%.9g,%.9g, %zu valid, %ux%u faces, flags %u, max %.8g)\n",
+           irrOut.c_str(), W, H, grid.nx, grid.ny, grid.nz, K, (double)grid.origin.x,
+           (double)grid.origin.y, (double)grid.origin.z, (double)grid.step.x, (double)grid.step.y,
+           (double)grid.step.z, nValid, gridRes, gridRes, irrParams.flags, (double)lightMax);
   }
 
   if (gather) {  // pose -> primary rays -> hits -> gathered light -> bytes, all on the device

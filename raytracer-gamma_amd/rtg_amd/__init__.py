@@ -93,6 +93,15 @@ SVGF_PARAMS_DTYPE = np.dtype([("passes", "<u4"), ("normalLog2", "<u4"), ("planeS
                               ("epsL", "<f4")])
 assert SVGF_PARAMS_DTYPE.itemsize == 28
 SVGF_LUMA = 16  # RTG_SVGF_LUMA, next to the FILTER_* bits
+# rtg_probe_grid and rtg_irradiance_params (include/rtg.h): the SH probe grid's lookup
+PROBE_GRID_DTYPE = np.dtype([("origin", "<f4", 3), ("step", "<f4", 3), ("nx", "<u4"),
+                             ("ny", "<u4"), ("nz", "<u4"), ("bands", "<u4")])
+assert PROBE_GRID_DTYPE.itemsize == 40
+IRR_PARAMS_DTYPE = np.dtype([("bias", "<f4"), ("lobe", "<f4", 3), ("flags", "<u4")])
+assert IRR_PARAMS_DTYPE.itemsize == 20
+IRR_VALID, IRR_FACING, IRR_VISIBLE = 1, 2, 4  # RTG_IRR_*
+IRR_LOBE_RADIANCE = (1.0, 1.0, 1.0)
+IRR_LOBE_COSINE = (1.0, float(np.float32(2.0) / np.float32(3.0)), 0.25)
 
 RTG_OK = 0
 ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "out of memory",
@@ -128,6 +137,8 @@ EXPORTED = [
     "rtg_ao_directions", "rtg_ao_segments_host", "rtg_ao_segments_device", "rtg_ao_device",
     "rtg_ao", "rtg_ao_host",
     "rtg_matte_device", "rtg_matte", "rtg_matte_host",
+    "rtg_probe_grid_points", "rtg_probe_grid_poses",
+    "rtg_irradiance_device", "rtg_irradiance", "rtg_irradiance_host",
     "rtg_gather_rays_host", "rtg_gather_rays_device", "rtg_gather_device", "rtg_gather",
     "rtg_gather_host",
     "rtg_filter_scratch", "rtg_filter_host", "rtg_filter_device", "rtg_filter",
@@ -271,6 +282,19 @@ def lib() -> ctypes.CDLL:
         L.rtg_matte_device.argtypes = [vp, vp, sz, vp, vp, vp]
         L.rtg_matte.argtypes = [i, vp, u, vp, u, vp, sz, vp, vp]
         L.rtg_matte_host.argtypes = [vp, u, vp, u, vp, sz, vp, vp, i, i]
+        # the probe grid's lookup; an RTG_LIB build of the commit before it
+        # (tools/ab_bench.sh against the parent) loads without it
+        for name, at in (
+                ("rtg_probe_grid_points", [vp, vp]),
+                ("rtg_probe_grid_poses", [vp, vp]),
+                ("rtg_irradiance_device", [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+                ("rtg_irradiance", [i, vp, u, vp, sz, vp, vp, vp, vp, vp, vp]),
+                ("rtg_irradiance_host", [vp, u, vp, sz, vp, vp, vp, vp, vp, vp, i, i])):
+            try:
+                getattr(L, name).argtypes = at
+            except AttributeError:
+                if not os.environ.get("RTG_LIB"):
+                    raise
         # the gather; an RTG_LIB build of the commit before it (tools/ab_bench.sh
         # against the parent) loads without it
         for name, at in (
@@ -977,6 +1001,106 @@ def matte(spheres, lights, hits, device: int = 0, mask: bool = False):
     _check(lib().rtg_matte(device, _ptr(sph), len(sph), _ptr(lgt), len(lgt), _ptr(src), n,
                            _ptr(dst), lp), "rtg_matte")
     return (out, lit) if mask else out
+
+
+def probe_grid(origin, step, dims, bands: int = 3) -> np.ndarray:
+    """One rtg_probe_grid record: probe (ix, iy, iz) of the dims = (nx, ny, nz)
+    lattice sits at origin + (ix, iy, iz) * step and holds bands * bands
+    coefficients."""
+    g = np.zeros(1, PROBE_GRID_DTYPE)
+    g[0] = (tuple(origin), tuple(step), dims[0], dims[1], dims[2], bands)
+    return g
+
+
+def irradiance_params(bias: float = 1e-3, lobe=IRR_LOBE_RADIANCE, flags: int = 0) -> np.ndarray:
+    """One rtg_irradiance_params record (flags: IRR_VALID | IRR_FACING |
+    IRR_VISIBLE; lobe: IRR_LOBE_RADIANCE, IRR_LOBE_COSINE or three factors)."""
+    p = np.zeros(1, IRR_PARAMS_DTYPE)
+    p[0] = (bias, tuple(lobe), flags)
+    return p
+
+
+def _grid(grid) -> np.ndarray:
+    return np.ascontiguousarray(grid, PROBE_GRID_DTYPE).reshape(1)
+
+
+def _grid_probes(g) -> int:
+    return int(g["nx"][0]) * int(g["ny"][0]) * int(g["nz"][0])
+
+
+def _grid_rows(g) -> int:
+    """Rows to allocate for a per-probe result: the probes of a grid the library
+    accepts, one for a grid it rejects before it writes."""
+    n = _grid_probes(g)
+    return n if 1 <= n * int(g["bands"][0]) ** 2 < 1 << 31 else 1
+
+
+def probe_grid_points(grid) -> np.ndarray:
+    """The probe positions in index order (rtg_probe_grid_points): (nx * ny * nz, 3)
+    float32.  contains*(...) < 0 of them gives the lookup's validity bytes."""
+    g = _grid(grid)
+    out = np.zeros((_grid_rows(g), 3), np.float32)
+    _check(lib().rtg_probe_grid_points(_ptr(g), _ptr(out)), "rtg_probe_grid_points")
+    return out
+
+
+def probe_grid_poses(grid) -> np.ndarray:
+    """camera_cube of every probe position, 6 per probe, probe-major
+    (rtg_probe_grid_poses): the pose table of a bake with fold_params(6, K)."""
+    g = _grid(grid)
+    out = np.zeros(6 * _grid_rows(g), CAMERA_DTYPE)
+    _check(lib().rtg_probe_grid_poses(_ptr(g), _ptr(out)), "rtg_probe_grid_poses")
+    return out
+
+
+def _irradiance_args(spheres, hits, grid, coeffs, valid, params, weight: bool):
+    """Scene, records, tables and the two results, with pointers that are never
+    null for an empty batch (legal: RTG_OK, nothing written); the validity
+    table's pointer is null when there is none."""
+    spheres = np.ascontiguousarray(spheres, SPHERE_DTYPE)
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    n = len(h)
+    g = _grid(grid)
+    p = np.ascontiguousarray(params, IRR_PARAMS_DTYPE).reshape(1)
+    c = np.ascontiguousarray(coeffs, np.float32).reshape(-1, 3)
+    k = int(g["bands"][0]) ** 2
+    assert len(c) == _grid_probes(g) * k, "coeffs are (nx * ny * nz * bands^2, 3)"
+    v = None
+    if valid is not None:
+        v = np.ascontiguousarray(valid, np.uint8).reshape(-1)
+        assert len(v) == _grid_probes(g), "valid is one byte per probe"
+    out = np.empty((n, 3), np.float32)
+    w = np.empty(n, np.float32) if weight else None
+    src = h if n else np.zeros(1, HIT_DTYPE)
+    dst = out if n else np.zeros((1, 3), np.float32)
+    wp = None if w is None else ctypes.c_void_p((w if n else np.zeros(1, np.float32)).ctypes.data)
+    return spheres, src, n, g, p, c, v, out, dst, w, wp
+
+
+def irradiance_host(spheres, hits, grid, coeffs, params, valid=None, walk: int = 0,
+                    threads: int = 1, weight: bool = False):
+    """The light of a grid of SH probes at every hit point on the host
+    (rtg_irradiance_host; no GPU needed): (n, 3) float32; weight=True: returns
+    (colours, weights), a weight of 0 where no probe was left.  grid from
+    probe_grid(), coeffs as render_views_fold* returns them for
+    probe_grid_poses(grid), params from irradiance_params().  walk 0: plain
+    loops; walk 1: the kernel's own path over the packed tables."""
+    sph, src, n, g, p, c, v, out, dst, w, wp = _irradiance_args(spheres, hits, grid, coeffs, valid,
+                                                                params, weight)
+    _check(lib().rtg_irradiance_host(_ptr(sph), len(sph), _ptr(src), n, _ptr(g), _ptr(c), _ptr(v),
+                                     _ptr(p), _ptr(dst), wp, walk, threads), "rtg_irradiance_host")
+    return (out, w) if weight else out
+
+
+def irradiance(spheres, hits, grid, coeffs, params, valid=None, device: int = 0,
+               weight: bool = False):
+    """The same on the GPU, one-shot (rtg_irradiance): HIT_DTYPE records as
+    intersect() returns them in."""
+    sph, src, n, g, p, c, v, out, dst, w, wp = _irradiance_args(spheres, hits, grid, coeffs, valid,
+                                                                params, weight)
+    _check(lib().rtg_irradiance(device, _ptr(sph), len(sph), _ptr(src), n, _ptr(g), _ptr(c),
+                                _ptr(v), _ptr(p), _ptr(dst), wp), "rtg_irradiance")
+    return (out, w) if weight else out
 
 
 def gather_params(samples: int, bias: float = 1e-3, seed: int = 0, flags: int = 0) -> np.ndarray:
@@ -1755,6 +1879,27 @@ class Context:
                                       ctypes.c_void_p(lit_ptr) if lit_ptr else None,
                                       ctypes.c_void_p(stream) if stream else None),
                "rtg_matte_device")
+
+    def irradiance_device(self, hits_ptr: int, n: int, grid, coeffs_ptr: int, params,
+                          dst_ptr: int, valid_ptr: int = 0, weight_ptr: int = 0, stream: int = 0):
+        """The light of the probe grid `grid` (probe_grid()) at n hit points at
+        hits_ptr (device, 32-byte HIT_DTYPE records as intersect_device writes
+        them), with the coefficients at coeffs_ptr (device, (nx * ny * nz * K, 3)
+        float32 as render_views_fold writes them) and, with IRR_VALID, the
+        validity bytes at valid_ptr (device, one uint8 per probe), into dst_ptr
+        (device, an (N, 3) float32 tensor) and, when weight_ptr is given, the
+        weights (device, n float32), asynchronously on `stream`
+        (rtg_irradiance_device; params from irradiance_params()).  The context
+        needs a scene only with IRR_VISIBLE."""
+        g = _grid(grid)
+        p = np.ascontiguousarray(params, IRR_PARAMS_DTYPE).reshape(1)
+        _check(lib().rtg_irradiance_device(self._h, ctypes.c_void_p(hits_ptr), n, _ptr(g),
+                                           ctypes.c_void_p(coeffs_ptr),
+                                           ctypes.c_void_p(valid_ptr) if valid_ptr else None,
+                                           _ptr(p), ctypes.c_void_p(dst_ptr),
+                                           ctypes.c_void_p(weight_ptr) if weight_ptr else None,
+                                           ctypes.c_void_p(stream) if stream else None),
+               "rtg_irradiance_device")
 
     def gather_device(self, hits_ptr: int, n: int, params, dirs_ptr: int, weights_ptr: int,
                       n_dirs: int, dst_ptr: int, skipped_ptr: int = 0, stack_size: int = 6,

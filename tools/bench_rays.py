@@ -104,6 +104,14 @@ filter's four frames fed through one accumulation with M2, the variance with
 every history long and short against its streaming floor, five passes against
 rtg_filter_device in the same rounds, per pass and form, and a torch chain.
 --only-svgf runs these alone and keeps FILE's other sections.
+
+The probe grid's lookup (rtg_irradiance_device, csrc/rtg_irradiance.hip) gets
+rows under "irradiance" (irradiance_rows below): an 8 x 8 x 4 grid of SH9 probes
+baked as fold_rows bakes, looked up at the primary hits of a frame with no flag,
+with VALID | FACING and with all three, next to the unfused chain (torch cells
+and segments, rtg_visible_device, a torch gather and fold of the same
+arithmetic) and the streaming floor.  --only-irradiance runs these alone and
+keeps FILE's other sections.
 GPU only.
 """
 import argparse
@@ -1370,6 +1378,184 @@ def fold_rows(args, stream):
     return out, ok
 
 
+def irradiance_rows(args, stream):
+    """The probe grid's lookup (csrc/rtg_irradiance.hip) at the aa = 1 primary
+    hits of C3 at 3840 x 2160 and of C5 at 1920 x 1080.  The grid: 8 x 8 x 4 SH9
+    probes over the box of the scene's spheres, baked as fold_rows bakes (32 x 32
+    faces at aa 1, rtg_cube_sh_weights, RTG_FOLD_SKIP_NONFINITE, the config's
+    stack size), validity from rtg_contains_device; bias 1e-3, RTG_IRR_LOBE_COSINE.
+    Per flag set (none, VALID | FACING, all three), round by round in one process:
+      fused          rtg_irradiance_device with the weight buffer;
+      fused_no_weight the same without it;
+      cells_torch    torch forming A, the cell, the eight weights, probe indices
+                     and positions and the n x 8 segments (A, X_p) (192 bytes
+                     per point), op by op as rtg.h orders them;
+      visible        rtg_visible_device over the n x 8 segments (with VISIBLE);
+      fold_torch     a torch gather and fold of the same arithmetic.
+    The unfused row is the per-round sum of its pieces.  Reported, not gated:
+    the times, the ratio to the floor at 6 TB/s (32 B in, 12 B out and 4 B of
+    weight per point) and whether the fused call is faster than the chain by
+    more than the chain's own min-max spread.  Gated: the fused call with and
+    without the weight buffer and the torch chain give the same words (NaN
+    canonicalised), colours and weights."""
+    bands, K, res_, bias = 3, 9, 32, 1e-3
+    dims = (8, 8, 4)
+    nP = dims[0] * dims[1] * dims[2]
+    lobe = R.IRR_LOBE_COSINE
+    c0, c1, c2, c3, c4 = (float(F(v)) for v in (0.28209479177387814, 0.4886025119029199,
+                                                  1.0925484305920792, 0.31539156525252005,
+                                                  0.5462742152960396))
+    l0, l1, l2 = (float(F(v)) for v in lobe)
+    table = torch.from_numpy(R.cube_sh_weights(res_, bands, 1.0)).cuda()
+    fp = R.fold_params(6, K, R.FOLD_SKIP_NONFINITE)
+    nbytes = R.views_fold_scratch(6 * nP, res_, res_, K)
+    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device="cuda")
+    out, ok = {"grid": list(dims), "bands": bands, "face": res_, "bias": bias,
+               "lobe": [l0, l1, l2]}, True
+    for name, (W, H) in (("c3", (3840, 2160)), ("c5", (1920, 1080))):
+        n = W * H
+        S = CONFIGS[name][4] + 1
+        sph, lg = R.generate_scene(CONFIGS[name][2], CONFIGS[name][3], 42)
+        c = sph["pos"].astype(F)
+        r = np.abs(sph["radius"].astype(F))[:, None]
+        lo, hi = (c - r).min(0), (c + r).max(0)
+        step = np.array([(hi[q] - lo[q]) / F(dims[q] - 1) for q in range(3)], F)
+        g = R.probe_grid(lo, step, dims, bands)
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        rays = torch.from_numpy(primary_rays(W, H)).cuda()
+        hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream)
+        d_cams = torch.from_numpy(R.probe_grid_poses(g).view(F).reshape(6 * nP, 12)).cuda()
+        d_pts = torch.from_numpy(R.probe_grid_points(g)).cuda()
+        coef = torch.zeros((nP * K, 3), dtype=torch.float32, device="cuda")
+        inside = torch.zeros((nP,), dtype=torch.int32, device="cuda")
+        ctx.render_views_fold(d_cams.data_ptr(), 6 * nP, res_, res_, fp, table.data_ptr(),
+                              coef.data_ptr(), scratch.data_ptr(), nbytes, zoom=-1.0,
+                              alias_factor=1.0, stack_size=S, stream=stream)
+        ctx.contains_device(d_pts.data_ptr(), nP, inside.data_ptr(), stream)
+        valid = (inside < 0).to(torch.uint8)
+        real = hits[:, 0] >= 0
+        P = hits[:, 2:5].view(torch.float32)
+        N = hits[:, 5:8].view(torch.float32)
+        o_t = torch.from_numpy(np.ascontiguousarray(g["origin"][0])).cuda()
+        s_t = torch.from_numpy(np.ascontiguousarray(g["step"][0])).cuda()
+        top = torch.tensor([d - 1 for d in dims], dtype=torch.float32, device="cuda")
+        nm2 = torch.tensor([max(d - 2, 0) for d in dims], dtype=torch.int32, device="cuda")
+        nm1 = torch.tensor([d - 1 for d in dims], dtype=torch.int32, device="cuda")
+        zero = torch.zeros((), dtype=torch.float32, device="cuda")
+        segs = torch.empty((n, 8, 6), dtype=torch.float32, device="cuda")
+        vis = torch.empty((n * 8,), dtype=torch.uint8, device="cuda")
+        state = {}
+
+        def cells():
+            A = P + bias * N
+            gq = (A - o_t) / s_t  # (tensor / tensor: a true division, not a reciprocal)
+            gq = torch.where(gq >= 0, gq, zero)
+            gq = torch.where(gq > top, top, gq)
+            i0 = torch.minimum(gq.to(torch.int32), nm2)
+            f = gq - i0.to(torch.float32)
+            i1 = torch.minimum(i0 + 1, nm1)
+            g1 = 1.0 - f
+            w = torch.empty((n, 8), dtype=torch.float32, device="cuda")
+            p = torch.empty((n, 8), dtype=torch.int64, device="cuda")
+            for cnr in range(8):
+                bit = (cnr & 1, (cnr >> 1) & 1, cnr >> 2)
+                i = [(i1 if bit[q] else i0)[:, q] for q in range(3)]
+                t = [(f if bit[q] else g1)[:, q] for q in range(3)]
+                w[:, cnr] = (t[0] * t[1]) * t[2]
+                p[:, cnr] = ((i[2] * dims[1] + i[1]) * dims[0] + i[0]).to(torch.int64)
+                segs[:, cnr, :3] = A
+                for q in range(3):
+                    along = i[q].to(torch.float32) * s_t[q]
+                    segs[:, cnr, 3 + q] = o_t[q] + along
+            state["w"], state["p"] = w, p
+
+        def fold(flags):
+            w, p = state["w"], state["p"]
+            x, y, z = N[:, 0], N[:, 1], N[:, 2]
+            b = [torch.full((n,), float(F(l0) * F(c0)), dtype=torch.float32, device="cuda"),
+                 l1 * (c1 * y), l1 * (c1 * z), l1 * (c1 * x),
+                 l2 * (c2 * (x * y)), l2 * (c2 * (y * z)), l2 * (c3 * ((3.0 * (z * z)) - 1.0)),
+                 l2 * (c2 * (x * z)), l2 * (c4 * ((x * x) - (y * y)))]
+            acc = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+            Wt = torch.zeros((n,), dtype=torch.float32, device="cuda")
+            for cnr in range(8):
+                keep = real & (w[:, cnr] > 0)
+                if flags & R.IRR_VALID:
+                    keep &= valid[p[:, cnr]] != 0
+                if flags & R.IRR_FACING:
+                    d = segs[:, cnr, 3:] - segs[:, cnr, :3]
+                    sx = N[:, 0] * d[:, 0]
+                    sy = N[:, 1] * d[:, 1]
+                    sz = N[:, 2] * d[:, 2]
+                    keep &= ((sx + sy) + sz) > 0
+                if flags & R.IRR_VISIBLE:
+                    keep &= vis.view(n, 8)[:, cnr] != 0
+                e = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+                for k in range(K):
+                    e = e + b[k][:, None] * coef[p[:, cnr] * K + k]
+                Wt = torch.where(keep, Wt + w[:, cnr], Wt)
+                acc = torch.where(keep[:, None], acc + w[:, cnr, None] * e, acc)
+            res = torch.where((Wt > 0)[:, None], acc / Wt[:, None], zero)
+            return res, Wt
+
+        def words(t):
+            bits = t.contiguous().view(torch.int32)  # NaN as 0xFFC00000, the records' form
+            return torch.where(torch.isnan(t), torch.full_like(bits, -0x400000), bits)
+
+        oa = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        ob = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        wa = torch.empty((n,), dtype=torch.float32, device="cuda")
+        floor_ms = n * 48 / 6.0e12 * 1e3
+        out[name] = {"W": W, "H": H, "points": n, "hit_points": int(real.sum()), "stack_size": S,
+                     "valid_probes": int(valid.sum()), "segment_bytes": n * 8 * 24,
+                     "floor_ms_at_6TBps_48B_per_point": round(floor_ms, 5)}
+        for label, flags in (("none", 0), ("valid_facing", 3), ("all", 7)):
+            pr = R.irradiance_params(bias, lobe, flags)
+            fns = [lambda: ctx.irradiance_device(hits.data_ptr(), n, g, coef.data_ptr(), pr,
+                                                 oa.data_ptr(), valid_ptr=valid.data_ptr(),
+                                                 weight_ptr=wa.data_ptr(), stream=stream),
+                   lambda: ctx.irradiance_device(hits.data_ptr(), n, g, coef.data_ptr(), pr,
+                                                 ob.data_ptr(), valid_ptr=valid.data_ptr(),
+                                                 stream=stream),
+                   cells, lambda: fold(flags)]
+            names = ["fused", "fused_no_weight", "cells_torch", "fold_torch"]
+            if flags & R.IRR_VISIBLE:
+                fns.append(lambda: ctx.visible_device(segs.data_ptr(), n * 8, vis.data_ptr(), stream))
+                names.append("visible")
+            cells()  # (fold and visible read its state in their warm-up launches)
+            ctx.visible_device(segs.data_ptr(), n * 8, vis.data_ptr(), stream)
+            raw = []
+            rows = measure(fns, args.rounds, raw=raw, min_reps=2,
+                           names=[f"irradiance {name} {label} {k}" for k in names])
+            tw, tW = fold(flags)
+            torch.cuda.synchronize()
+            same = bool((words(oa) == words(ob)).all())
+            chain = bool((words(oa) == words(tw)).all() and (words(wa) == words(tW)).all())
+            ok = ok and same and chain
+            sums = _spread_rows({"unfused": [sum(v) for v in zip(*raw[2:])]})
+            spread = sums["unfused"]["ms_max"] - sums["unfused"]["ms_min"]
+            fu = rows[0]
+            out[name][label] = dict(
+                zip(names, rows), **sums, flags=flags,
+                unfused_over_fused=round(sums["unfused"]["ms_median"] / fu["ms_median"], 3),
+                fused_faster_than_unfused_by_more_than_its_spread=bool(
+                    sums["unfused"]["ms_median"] - fu["ms_median"] > spread),
+                fused_over_floor=round(fu["ms_median"] / floor_ms, 2),
+                Mpoints_per_s=round(n / (fu["ms_median"] * 1e-3) / 1e6, 1),
+                zero_weight_share_of_hit_points=round(
+                    float((wa[real] == 0).to(torch.float64).mean()), 4),
+                fused_equals_fused_no_weight=same, fused_equals_torch_chain=chain,
+                torch_chain_differing_points=int((words(oa) != words(tw)).any(1).sum()))
+            print(f"irradiance {name} {label}: fused {fu['ms_median']} ms, unfused "
+                  f"{sums['unfused']['ms_median']} ms, floor {floor_ms:.4f} ms", file=sys.stderr,
+                  flush=True)
+        ctx.close()
+        del segs, vis, state
+    return out, ok
+
+
 def finish(args, res, ok):
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
@@ -1406,6 +1592,8 @@ def main():
     ap.add_argument("--only-svgf", action="store_true",
                     help="the variance estimate's and the variance-guided passes' rows alone, put into "
                          "FILE next to what it holds")
+    ap.add_argument("--only-irradiance", action="store_true",
+                    help="the probe grid's lookup rows alone, put into FILE next to what it holds")
     ap.add_argument("--parent-commit", default="",
                     help="recorded with --only-fold, --only-gather, --only-filter, --only-accumulate or "
                          "--only-svgf as the parent "
@@ -1473,6 +1661,15 @@ def main():
         res["svgf_commit"], res["svgf_parent_commit"] = args.commit, args.parent_commit
         res["svgf"], ok = svgf_rows(args, torch.cuda.current_stream().cuda_stream)
         res["svgf"]["rounds"] = args.rounds
+        finish(args, res, ok)
+    if args.only_irradiance:  # (the same: it makes the hits and the grid of its own frames)
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["irradiance_commit"], res["irradiance_parent_commit"] = args.commit, args.parent_commit
+        res["irradiance"], ok = irradiance_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["irradiance"]["rounds"] = args.rounds
         finish(args, res, ok)
     W, H = CONFIGS["c3"][0], CONFIGS["c3"][1]
     assert (W, H) == CONFIGS["c5"][:2]
