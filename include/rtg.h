@@ -44,6 +44,9 @@
  *     the camera moves: reprojection by the hit points)   rtg_camera_project[_device|_host]
  *   (a variance per pixel from the carried moments, and  rtg_variance[_device|_host],
  *     the filter guided by it: edges inside a surface)    rtg_svgf[_device|_host], rtg_svgf_scratch
+ *   (such a signal traced on a coarser frame, brought up  rtg_upsample[_device|_host], rtg_upsample_scratch,
+ *     by the full frame's records; the pixels it cannot    rtg_hits_pick[_device|_host],
+ *     reach listed, traced alone and placed)               rtg_values_place[_device|_host]
  *   primaryContainer for a caller's own points         rtg_contains[_device|_host]
  *     raytracer.h:245-270
  *   checkError -> exit(EXIT_FAILURE)  err_code.h:143   negative return + rtg_last_error
@@ -1551,6 +1554,146 @@ int rtg_svgf_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned width,
 int rtg_svgf(int device, const rtg_hit* hits, unsigned width, unsigned height,
              const rtg_svgf_params* params, const float* src, const float* varSrc, float* dstHost,
              float* dstVarHost);
+
+/* ---- upsample: a low-resolution signal brought up by full-resolution guides ----
+ * The per-pixel signals above cost what their probes cost; everything after
+ * them is cheap.  These calls let a caller trace the signal on a coarser frame
+ * of the same pose and zoom, bring it up to the full frame with the full
+ * frame's own records as guides, and learn which pixels no coarse tap agrees
+ * with: the HOLE LIST, on which the signal is then run at full resolution
+ * (rtg_hits_pick*, the signal's own call, rtg_values_place*, below).  Float
+ * arithmetic that is defined here: the same words on the host and on every GPU.
+ *
+ * THE TWO FRAMES.  scaleLog2 = L in 1..3, f = 1 << L.  The full frame is W x H,
+ * the low frame Wl x Hl with W == Wl << L and H == Hl << L.  The aa-1 sample of
+ * pixel x of a W-wide frame leaves the eye at (x - W/2) * (16/W) (main.cpp:
+ * 411-413 with sample (0, 0) of :432-433, camera_dir): no half-pixel offset.
+ * (X - Wl/2) is (f X - W/2) / f and 16/Wl is f * (16/W), both exactly, so low
+ * pixel (X, Y) is the ray of full pixel (f X, f Y), bit for bit, and its record
+ * is that pixel's record.  A full pixel x lies between low columns x >> L and
+ * (x >> L) + 1 at the fraction (x mod f) / f, which is exact in float, as is
+ * every product of two such fractions.
+ *
+ * INPUTS.  `hits`: W * H full-resolution rtg_hit records, `lowHits`: Wl * Hl
+ * records of the low frame, both read as rtg_filter* reads them (id for its
+ * sign and for equality, point and normal as given, t not read).  `lowSrc`:
+ * Wl * Hl values of one of rtg_filter*'s kinds (RTG_FILTER_RGB rtg_vec,
+ * RTG_FILTER_GRAY float, RTG_FILTER_COUNT unsigned short with value (float)c);
+ * C = 3 channels for RGB, else 1.  `dst`: W * H * C floats.  The call needs no
+ * scene.
+ *
+ * PER FULL PIXEL p = (x, y), all in float with no contraction and in this
+ * operand order, dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z, q over the
+ * channels:
+ *   id_p < 0:  dst[p].q = +0.f; the pixel is no hole and nothing else is read.
+ *   otherwise  x0 = x >> L, tx = (float)(x & (f - 1)) * (1.f / f); y0 = y >> L,
+ *     ty = (float)(y & (f - 1)) * (1.f / f); sum.q = sw = +0.f;
+ *     taps dy = 0, 1 (outer), dx = 0, 1 (inner): q = (x0 + dx, y0 + dy),
+ *     wx = dx ? tx : 1.f - tx, wy = dy ? ty : 1.f - ty, w = wy * wx.  The tap
+ *     is left out when q is outside the low frame, or lowId_q < 0, or
+ *     RTG_UPSAMPLE_SAME_ID is set and lowId_q != id_p, or
+ *     RTG_UPSAMPLE_SKIP_NONFINITE is set and any word of lowSrc[q] has an
+ *     all-ones exponent field.  Then rtg_filter*'s two terms, verbatim:
+ *       RTG_UPSAMPLE_NORMAL:  c = dot(N_p, lowN_q);  c = c > 0.f ? c : 0.f;
+ *                             normalLog2 times c = c * c;  w = w * c
+ *       RTG_UPSAMPLE_PLANE:   e = lowP_q - P_p per component;
+ *                             d = fabsf(dot(N_p, e));  z = 1.f - d * planeScale;
+ *                             z = z > 0.f ? z : 0.f;  w = w * z
+ *     and the tap is left out when !(w > 0.f), which also drops the taps whose
+ *     bilinear weight is zero (tx == 0.f or ty == 0.f).  An accepted tap gives
+ *       sum.q = sum.q + w * lowSrc[q].q;  sw = sw + w
+ *   sw > 0.f:  dst[p].q = sum.q / sw, the correctly rounded quotient.
+ *   otherwise  the pixel is a HOLE: dst[p].q = +0.f, and the pixel is listed.
+ * NaN words are stored as 0xFFC00000.  NaN points, normals and values follow
+ * the comparisons as written.
+ *
+ * THE HOLE LIST is optional: `holes` (unsigned, capacity holeCap) and
+ * `holeCount` (one unsigned) are both null or both non-null.  holeCount
+ * receives the number of holes of the frame, also when it exceeds holeCap;
+ * holes[0 .. min(count, holeCap)) receive the holes' pixel indices y * W + x in
+ * ascending order, and no entry past that is written.  The order is part of
+ * the contract: two runs and the host form give the same words.
+ *
+ * rtg_upsample_host restates this in plain loops: the yardstick.
+ * rtg_upsample_device is asynchronous on `stream`, allocates nothing, needs no
+ * scene, takes none of the context's render scratch and may be mixed with
+ * every other call on the context; `params` is host memory, read before
+ * return.  Without a hole list it is one launch and needs no scratch
+ * (rtg_upsample_scratch gives 0, and the scratch may be null).  With one it
+ * is three launches (the pixels, a scan over the workgroups' hole counts, the
+ * list's entries) and needs a caller-owned scratch of rtg_upsample_scratch's
+ * bytes, 16-byte aligned, the call's until it has finished on the stream.  No
+ * kernel waits for another workgroup of its own launch.
+ *
+ * RTG_ERR_INVALID with a message, before any GPU call, for a null pointer (a
+ * null scratch is legal only when 0 bytes are needed), W, H, Wl or Hl equal to
+ * 0, W != Wl << L or H != Hl << L, L outside 1..3, W or H above 2^24, W * H
+ * above 2^32 - 1 (which also keeps the grid below 2^31 workgroups),
+ * normalLog2 above 8, an unknown kind or flag, holes without holeCount or the
+ * reverse, hits or lowHits off 16-byte alignment (device), a scratch that is
+ * too small or misaligned, and any output's byte range (dst, holes, holeCount,
+ * the scratch) overlapping an input's or another output's (addresses compared
+ * as numbers, on the host and on the device alike).
+ *
+ * rtg_hits_pick*: out[i] = hits[idx[i]] for i < m, the 32 bytes as they are;
+ * an index >= n gives a miss record (id -1, every other word 0) and reads
+ * nothing.  rtg_values_place*: dst[idx[i]] = vals[i] for i < m, `vals` m values
+ * of `kind` and `dst` n * C floats, converted as rtg_filter* converts (COUNT to
+ * float, float words as they are); an index >= n is skipped.  The indices are
+ * taken as DISTINCT, as a hole list's are: with a repeated index any one of
+ * its values lands.  `m` is a host value: the caller reads holeCount back, one
+ * 4-byte copy.  m == 0 is legal and does nothing.  RTG_ERR_INVALID for a null
+ * pointer, n == 0, an unknown kind, hits or out off 16-byte alignment
+ * (device), more than 2^31 - 1 workgroups (device), and an output's byte range
+ * overlapping an input's.
+ *
+ * Out of scope: factors that are no power of two and frames not divisible by
+ * f, upsampling moments or history lengths (accumulate at full resolution
+ * after the upsample), checkerboard or adaptive sample placement, rtg_gbuf_px
+ * guides, views and multi-GPU. */
+#define RTG_UPSAMPLE_MAX_SCALE_LOG2 3
+#define RTG_UPSAMPLE_SAME_ID 1         /* a tap of another id is left out */
+#define RTG_UPSAMPLE_NORMAL 2          /* the normal term */
+#define RTG_UPSAMPLE_PLANE 4           /* the plane-distance term */
+#define RTG_UPSAMPLE_SKIP_NONFINITE 8  /* a tap whose value has a NaN or infinite word is left out */
+typedef struct rtg_upsample_params { /* 20 B */
+  unsigned kind;        /* RTG_FILTER_RGB / GRAY / COUNT */
+  unsigned flags;       /* RTG_UPSAMPLE_* bits; an unknown bit is RTG_ERR_INVALID */
+  unsigned normalLog2;  /* 0..8 */
+  float planeScale;     /* used as given */
+  unsigned scaleLog2;   /* 1..RTG_UPSAMPLE_MAX_SCALE_LOG2 */
+} rtg_upsample_params;
+/* Bytes of scratch rtg_upsample_device needs for such a full frame: 0 when
+ * withHoles is 0. */
+int rtg_upsample_scratch(unsigned width, unsigned height, int withHoles, size_t* bytes);
+/* Plain loops; the result does not depend on nthreads (threads take bands of
+ * rows; the list is written in order afterwards).  nthreads <= 0: 1. */
+int rtg_upsample_host(const rtg_hit* hits, unsigned width, unsigned height,
+                      const rtg_upsample_params* params, const rtg_hit* lowHits,
+                      unsigned lowWidth, unsigned lowHeight, const void* lowSrc, float* dst,
+                      unsigned* holes, unsigned holeCap, unsigned* holeCount, int nthreads);
+int rtg_upsample_device(rtg_context* ctx, const rtg_hit* hitsDevice, unsigned width,
+                        unsigned height, const rtg_upsample_params* params,
+                        const rtg_hit* lowHitsDevice, unsigned lowWidth, unsigned lowHeight,
+                        const void* lowSrcDevice, float* dstDevice, unsigned* holesDevice,
+                        unsigned holeCap, unsigned* holeCountDevice, void* scratchDevice,
+                        size_t scratchBytes, void* stream);
+/* One-shot: uploads the inputs (host memory), allocates its own scratch, runs
+ * on `device`, downloads dst and, with a list, holeCount and holeCap entries
+ * (the entries past min(count, holeCap) are the caller's own words). */
+int rtg_upsample(int device, const rtg_hit* hits, unsigned width, unsigned height,
+                 const rtg_upsample_params* params, const rtg_hit* lowHits, unsigned lowWidth,
+                 unsigned lowHeight, const void* lowSrc, float* dstHost, unsigned* holesHost,
+                 unsigned holeCap, unsigned* holeCountHost);
+int rtg_hits_pick_host(const rtg_hit* hits, size_t n, const unsigned* idx, size_t m,
+                       rtg_hit* outHost, int nthreads);
+int rtg_hits_pick_device(rtg_context* ctx, const rtg_hit* hitsDevice, size_t n,
+                         const unsigned* idxDevice, size_t m, rtg_hit* outDevice, void* stream);
+int rtg_values_place_host(unsigned kind, const void* vals, const unsigned* idx, size_t m, size_t n,
+                          float* dstHost, int nthreads);
+int rtg_values_place_device(rtg_context* ctx, unsigned kind, const void* valsDevice,
+                            const unsigned* idxDevice, size_t m, size_t n, float* dstDevice,
+                            void* stream);
 
 /* ---- containment: primaryContainer per point ----
  * "Which medium is this point in": out[i] is the lowest sphere index s for

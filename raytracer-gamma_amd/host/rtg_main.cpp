@@ -74,6 +74,14 @@ static void usage() {
   printf("                           RTG_FILTER_SAME_ID | NORMAL | PLANE; planeScale defaults to 1,\n");
   printf("                           normalLog2 to 3); the PGM is then 255 * value / K, clamped to\n");
   printf("                           0..255; needs --ao\n");
+  printf("      --ao-scale   L[,planeScale[,normalLog2]]\n");
+  printf("                           Trace the probes on the frame of width >> L and height >> L of\n");
+  printf("                           the same pose (L in 1..3; both must divide by 1 << L), bring\n");
+  printf("                           the counts up with rtg_upsample_device (RTG_UPSAMPLE_SAME_ID |\n");
+  printf("                           NORMAL | PLANE; planeScale 1, normalLog2 3 unless given) and\n");
+  printf("                           trace at full resolution only the pixels no low tap agrees with\n");
+  printf("                           (rtg_hits_pick_device, rtg_values_place_device); the frame is\n");
+  printf("                           then floats for --ao-history and --ao-filter; needs --ao\n");
   printf("      --ao-history FILE[,MAXHISTORY]\n");
   printf("                           Accumulate the counts over a camera path before they are written:\n");
   printf("                           one frame per line of FILE (poses in --camera's syntax, oldest\n");
@@ -118,6 +126,9 @@ static void usage() {
   printf("      --gather-filter SPEC Smooth the gathered light before it is scaled and written: the\n");
   printf("                           spec and the filter of --ao-filter, with\n");
   printf("                           RTG_FILTER_SKIP_NONFINITE under --gather-skip; needs --gather\n");
+  printf("      --gather-scale L[,planeScale[,normalLog2]]\n");
+  printf("                           Gather on the low frame and upsample, as --ao-scale does (with\n");
+  printf("                           RTG_UPSAMPLE_SKIP_NONFINITE under --gather-skip); needs --gather\n");
   printf("      --gather-history FILE[,MAXHISTORY]\n");
   printf("                           Accumulate the gathered light the same way (with\n");
   printf("                           RTG_ACCUM_SKIP_NONFINITE under --gather-skip) before it is\n");
@@ -321,6 +332,88 @@ static void* svgf_frame(rtg_context* ctx, const HistoryState& s, unsigned W, uns
   return dst;
 }
 
+// "L[,planeScale[,normalLog2]]" of --ao-scale and --gather-scale; false when it is not that.
+struct Scale {
+  unsigned L = 0;  // 0: the signal is traced at full resolution
+  float planeScale = 1.f;
+  unsigned normalLog2 = 3;
+};
+static bool parse_scale(const char* s, Scale* sc) {
+  char tail = 0;
+  const int k = sscanf(s, "%u,%f,%u%c", &sc->L, &sc->planeScale, &sc->normalLog2, &tail);
+  return k >= 1 && k <= 3 && sc->L >= 1 && sc->L <= RTG_UPSAMPLE_MAX_SCALE_LOG2 &&
+         sc->normalLog2 <= 8;
+}
+
+// The device buffers of a mixed-resolution frame: the low frame's rays, records
+// and values, the hole list with its scratch, and the holes' records and values.
+struct Mixed {
+  unsigned Wl, Hl;
+  rtg_ray* lowRays;
+  rtg_hit* lowHits;
+  void* lowSig;
+  rtg_hit* picked;
+  void* pickedSig;
+  unsigned* holes;
+  unsigned* count;
+  void* scratch;
+  size_t scratchBytes;
+};
+static Mixed mixed_alloc(const Scale& sc, unsigned W, unsigned H, size_t valueBytes) {
+  Mixed m = {};
+  m.Wl = W >> sc.L;
+  m.Hl = H >> sc.L;
+  const size_t n = (size_t)W * H, nl = (size_t)m.Wl * m.Hl;
+  check(rtg_upsample_scratch(W, H, 1, &m.scratchBytes), "rtg_upsample_scratch");
+  if (hipMalloc(&m.lowRays, nl * sizeof(rtg_ray)) != hipSuccess ||
+      hipMalloc(&m.lowHits, nl * sizeof(rtg_hit)) != hipSuccess ||
+      hipMalloc(&m.lowSig, nl * valueBytes) != hipSuccess ||
+      hipMalloc(&m.picked, n * sizeof(rtg_hit)) != hipSuccess ||
+      hipMalloc(&m.pickedSig, n * valueBytes) != hipSuccess ||
+      hipMalloc(&m.holes, n * sizeof(unsigned)) != hipSuccess ||
+      hipMalloc(&m.count, sizeof(unsigned)) != hipSuccess ||
+      hipMalloc(&m.scratch, m.scratchBytes) != hipSuccess)
+    check(RTG_ERR_NOMEM, "hipMalloc");
+  return m;
+}
+static void mixed_free(Mixed& m) {
+  (void)hipFree(m.lowRays);
+  (void)hipFree(m.lowHits);
+  (void)hipFree(m.lowSig);
+  (void)hipFree(m.picked);
+  (void)hipFree(m.pickedSig);
+  (void)hipFree(m.holes);
+  (void)hipFree(m.count);
+  (void)hipFree(m.scratch);
+  m = Mixed{};
+}
+// The low frame's records of a pose, on the default stream.
+static void mixed_low_hits(rtg_context* ctx, const Mixed& m, const rtg_camera& pose, float zoom) {
+  check(rtg_camera_rays_device(ctx, &pose, m.Wl, m.Hl, zoom, 1.f, m.lowRays, nullptr),
+        "rtg_camera_rays_device");
+  check(rtg_intersect_device(ctx, m.lowRays, (size_t)m.Wl * m.Hl, m.lowHits, nullptr),
+        "rtg_intersect_device");
+}
+// m.lowSig brought up to `dst` by the full records `hits`; the holes' records
+// go to m.picked.  Returns the number of holes (one 4-byte copy back).
+static size_t mixed_upsample(rtg_context* ctx, const Mixed& m, const Scale& sc, unsigned kind,
+                             unsigned moreFlags, unsigned W, unsigned H, const rtg_hit* hits,
+                             float* dst) {
+  const size_t n = (size_t)W * H;
+  const rtg_upsample_params up = {
+      kind, RTG_UPSAMPLE_SAME_ID | RTG_UPSAMPLE_NORMAL | RTG_UPSAMPLE_PLANE | moreFlags,
+      sc.normalLog2, sc.planeScale, sc.L};
+  check(rtg_upsample_device(ctx, hits, W, H, &up, m.lowHits, m.Wl, m.Hl, m.lowSig, dst, m.holes,
+                            (unsigned)n, m.count, m.scratch, m.scratchBytes, nullptr),
+        "rtg_upsample_device");
+  unsigned count = 0;
+  if (hipMemcpy(&count, m.count, sizeof count, hipMemcpyDeviceToHost) != hipSuccess)
+    check(RTG_ERR_HIP, "readback");
+  check(rtg_hits_pick_device(ctx, hits, n, m.holes, count, m.picked, nullptr),
+        "rtg_hits_pick_device");
+  return count;
+}
+
 static bool parse_uint(const char* s, unsigned* out) {
   char* end;
   unsigned long v = strtoul(s, &end, 10);
@@ -346,6 +439,7 @@ int main(int argc, char** argv) {
   rtg_filter_params aoFilterParams = {}, gatherFilterParams = {};
   History aoHistory, gatherHistory;
   Variance aoVariance, gatherVariance;
+  Scale aoScale, gatherScale;
   unsigned gpus = 0;
   int semantics = RTG_SEMANTICS_CPU;
   bool posed = false;
@@ -482,6 +576,12 @@ int main(int argc, char** argv) {
         printf("Invalid variance (SIGMA[,minHistory], minHistory in 0..65535)\n");
         return 1;
       }
+    } else if (!strcmp(a, "--ao-scale") || !strcmp(a, "--gather-scale")) {
+      if (!parse_scale(need(a), a[2] == 'a' ? &aoScale : &gatherScale)) {
+        printf("Invalid scale (L[,planeScale[,normalLog2]], L in 1..%d, normalLog2 in 0..8)\n",
+               RTG_UPSAMPLE_MAX_SCALE_LOG2);
+        return 1;
+      }
     } else if (!strcmp(a, "--matte")) {
       matteOut = need(a);
       matte = true;
@@ -570,14 +670,23 @@ int main(int argc, char** argv) {
     printf("--ao-variance needs --ao-filter, --gather-variance needs --gather-filter\n");
     return 1;
   }
+  if ((aoScale.L && !ao) || (gatherScale.L && !gather)) {
+    printf("--ao-scale needs --ao, --gather-scale needs --gather\n");
+    return 1;
+  }
+  for (const Scale* sc : {&aoScale, &gatherScale})
+    if (sc->L && (W == 0 || H == 0 || W % (1u << sc->L) || H % (1u << sc->L))) {
+      printf("A frame of %ux%u does not divide by the scale's factor %u\n", W, H, 1u << sc->L);
+      return 1;
+    }
   // the variance needs the accumulated moments: without a history, of one reset frame
   const bool aoAccum = aoHistory.on || aoVariance.on;
   const bool gatherAccum = gatherHistory.on || gatherVariance.on;
-  // (an accumulated frame is floats: the filter then takes it as GRAY)
-  aoFilterParams.kind = aoAccum ? RTG_FILTER_GRAY : RTG_FILTER_COUNT;
+  // (an accumulated frame is floats, and so is an upsampled one: the filter then takes it as GRAY)
+  aoFilterParams.kind = aoAccum || aoScale.L ? RTG_FILTER_GRAY : RTG_FILTER_COUNT;
   gatherFilterParams.kind = RTG_FILTER_RGB;
   if (gatherSkip) gatherFilterParams.flags |= RTG_FILTER_SKIP_NONFINITE;
-  aoHistory.params.kind = RTG_FILTER_COUNT;
+  aoHistory.params.kind = aoScale.L ? RTG_FILTER_GRAY : RTG_FILTER_COUNT;
   gatherHistory.params.kind = RTG_FILTER_RGB;
   if (gatherSkip) gatherHistory.params.flags |= RTG_ACCUM_SKIP_NONFINITE;
   if (aoHistory.on) aoHistory.poses = read_poses(aoHistory.file);
@@ -815,6 +924,12 @@ int main(int argc, char** argv) {
     rtg_ray* dr = nullptr;
     rtg_vec* dd = nullptr;
     unsigned short* dc = nullptr;
+    float* dsig = nullptr;  // --ao-scale: the upsampled counts with the holes' own placed in
+    Mixed mixed = {};
+    if (aoScale.L) {
+      mixed = mixed_alloc(aoScale, W, H, sizeof(unsigned short));
+      if (hipMalloc(&dsig, n * sizeof(float)) != hipSuccess) check(RTG_ERR_NOMEM, "hipMalloc");
+    }
     // the frames of --ao-history ping-pong between two states; without it
     // there is one frame and only its records
     const size_t frames = aoHistory.on ? aoHistory.poses.size() + 1 : 1;
@@ -831,6 +946,7 @@ int main(int argc, char** argv) {
         check(RTG_ERR_NOMEM, "hipMalloc");
     if (hipMemcpy(dd, table.data(), K * sizeof(rtg_vec), hipMemcpyHostToDevice) != hipSuccess)
       check(RTG_ERR_HIP, "upload");
+    size_t holesSeen = 0;
     for (size_t k = 0; k < frames; ++k) {
       HistoryState& cur = st[k & 1];
       cur.pose = k + 1 < frames ? aoHistory.poses[k] : camera;
@@ -839,21 +955,43 @@ int main(int argc, char** argv) {
       check(rtg_camera_rays_device(ctx, &cur.pose, W, H, zoom, 1.f, dr, nullptr),
             "rtg_camera_rays_device");
       check(rtg_intersect_device(ctx, dr, n, cur.hits, nullptr), "rtg_intersect_device");
-      check(rtg_ao_device(ctx, cur.hits, n, &ap, dd, K, dc, nullptr), "rtg_ao_device");
+      if (aoScale.L) {  // the probes on the low frame, then on the holes alone
+        mixed_low_hits(ctx, mixed, cur.pose, zoom);
+        check(rtg_ao_device(ctx, mixed.lowHits, (size_t)mixed.Wl * mixed.Hl, &ap, dd, K,
+                            (unsigned short*)mixed.lowSig, nullptr),
+              "rtg_ao_device");
+        const size_t m =
+            mixed_upsample(ctx, mixed, aoScale, RTG_FILTER_COUNT, 0, W, H, cur.hits, dsig);
+        if (m) {
+          check(rtg_ao_device(ctx, mixed.picked, m, &ap, dd, K, (unsigned short*)mixed.pickedSig,
+                              nullptr),
+                "rtg_ao_device");
+          check(rtg_values_place_device(ctx, RTG_FILTER_COUNT, mixed.pickedSig, mixed.holes, m, n,
+                                        dsig, nullptr),
+                "rtg_values_place_device");
+        }
+        holesSeen += m;
+      } else {
+        check(rtg_ao_device(ctx, cur.hits, n, &ap, dd, K, dc, nullptr), "rtg_ao_device");
+      }
       if (aoAccum)
-        accumulate_frame(ctx, aoHistory, W, H, zoom, dc, k ? &st[(k - 1) & 1] : nullptr, cur);
+        accumulate_frame(ctx, aoHistory, W, H, zoom, aoScale.L ? (const void*)dsig : dc,
+                         k ? &st[(k - 1) & 1] : nullptr, cur);
     }
     const HistoryState& last = st[(frames - 1) & 1];
     std::vector<unsigned short> counts(n);
     std::vector<float> smooth;
-    if (hipMemcpy(counts.data(), dc, n * sizeof(unsigned short), hipMemcpyDeviceToHost) !=
-        hipSuccess)
+    if (!aoScale.L &&
+        hipMemcpy(counts.data(), dc, n * sizeof(unsigned short), hipMemcpyDeviceToHost) !=
+            hipSuccess)
       check(RTG_ERR_HIP, "readback");
-    if (aoFilter || aoHistory.on) {  // the frame never leaves the device on its way to the filter
+    if (aoFilter || aoHistory.on || aoScale.L) {  // the frame never leaves the device on its way to the filter
+      const void* sig = aoScale.L ? (const void*)dsig : dc;
       void* df = aoVariance.on ? svgf_frame(ctx, last, W, H, aoFilterParams, aoVariance)
                  : aoFilter    ? filter_frame(ctx, last.hits, W, H, aoFilterParams,
-                                              aoHistory.on ? (const void*)last.acc : dc)
-                               : last.acc;
+                                              aoHistory.on ? (const void*)last.acc : sig)
+                 : aoHistory.on ? (void*)last.acc
+                                : (void*)dsig;
       smooth.resize(n);
       if (hipMemcpy(smooth.data(), df, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
         check(RTG_ERR_HIP, "readback");
@@ -862,6 +1000,8 @@ int main(int argc, char** argv) {
     (void)hipFree(dr);
     (void)hipFree(dd);
     (void)hipFree(dc);
+    (void)hipFree(dsig);
+    mixed_free(mixed);
     for (HistoryState& s : st) {
       (void)hipFree(s.hits);
       (void)hipFree(s.acc);
@@ -884,6 +1024,8 @@ int main(int argc, char** argv) {
     printf("Wrote %s (%ux%u, %u probes of length %.8g per primary hit", aoOut.c_str(), W, H, K,
            (double)aoParams.radius);
     if (aoHistory.on) printf(", accumulated over %zu frames", frames);
+    if (aoScale.L)
+      printf(", traced at %ux%u and on %zu holes", W >> aoScale.L, H >> aoScale.L, holesSeen);
     printf(")\n");
   }
 
@@ -1042,6 +1184,9 @@ int main(int argc, char** argv) {
     unsigned char* db = nullptr;
     const size_t frames = gatherHistory.on ? gatherHistory.poses.size() + 1 : 1;  // as for --ao
     HistoryState st[2] = {};
+    Mixed mixed = {};
+    if (gatherScale.L) mixed = mixed_alloc(gatherScale, W, H, sizeof(rtg_vec));
+    size_t holesSeen = 0;
     for (size_t k = 0; k < (frames > 1 ? 2u : 1u); ++k)
       if (hipMalloc(&st[k].hits, n * sizeof(rtg_hit)) != hipSuccess ||
           (gatherAccum && (hipMalloc(&st[k].acc, n * sizeof(rtg_vec)) != hipSuccess ||
@@ -1065,9 +1210,28 @@ int main(int argc, char** argv) {
       check(rtg_camera_rays_device(ctx, &cur.pose, W, H, zoom, 1.f, dr, nullptr),
             "rtg_camera_rays_device");
       check(rtg_intersect_device(ctx, dr, n, cur.hits, nullptr), "rtg_intersect_device");
-      check(rtg_gather_device(ctx, cur.hits, n, &gp, dd, dw, K, (int)depth + 1, dl, nullptr,
-                              nullptr),
-            "rtg_gather_device");
+      if (gatherScale.L) {  // the gather on the low frame, then on the holes alone
+        mixed_low_hits(ctx, mixed, cur.pose, zoom);
+        check(rtg_gather_device(ctx, mixed.lowHits, (size_t)mixed.Wl * mixed.Hl, &gp, dd, dw, K,
+                                (int)depth + 1, (rtg_vec*)mixed.lowSig, nullptr, nullptr),
+              "rtg_gather_device");
+        const size_t m = mixed_upsample(ctx, mixed, gatherScale, RTG_FILTER_RGB,
+                                        gatherSkip ? RTG_UPSAMPLE_SKIP_NONFINITE : 0, W, H,
+                                        cur.hits, (float*)dl);
+        if (m) {
+          check(rtg_gather_device(ctx, mixed.picked, m, &gp, dd, dw, K, (int)depth + 1,
+                                  (rtg_vec*)mixed.pickedSig, nullptr, nullptr),
+                "rtg_gather_device");
+          check(rtg_values_place_device(ctx, RTG_FILTER_RGB, mixed.pickedSig, mixed.holes, m, n,
+                                        (float*)dl, nullptr),
+                "rtg_values_place_device");
+        }
+        holesSeen += m;
+      } else {
+        check(rtg_gather_device(ctx, cur.hits, n, &gp, dd, dw, K, (int)depth + 1, dl, nullptr,
+                                nullptr),
+              "rtg_gather_device");
+      }
       if (gatherAccum)
         accumulate_frame(ctx, gatherHistory, W, H, zoom, dl, k ? &st[(k - 1) & 1] : nullptr, cur);
     }
@@ -1091,6 +1255,7 @@ int main(int argc, char** argv) {
         hipMemcpy(&lightMax, dmax, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
       check(RTG_ERR_HIP, "readback");
     (void)hipFree(dr);
+    mixed_free(mixed);
     for (HistoryState& s : st) {
       (void)hipFree(s.hits);
       (void)hipFree(s.acc);
@@ -1112,6 +1277,9 @@ int main(int argc, char** argv) {
     printf("Wrote %s (%ux%u, %u probes per primary hit, depth %u, max %.8g",
            gatherOut.c_str(), W, H, K, depth, (double)lightMax);
     if (gatherHistory.on) printf(", accumulated over %zu frames", frames);
+    if (gatherScale.L)
+      printf(", gathered at %ux%u and on %zu holes", W >> gatherScale.L, H >> gatherScale.L,
+             holesSeen);
     printf(")\n");
   }
 

@@ -84,6 +84,12 @@ ACCUM_PARAMS_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("normalLog2",
                                ("planeScale", "<f4"), ("maxHistory", "<u4")])
 assert ACCUM_PARAMS_DTYPE.itemsize == 20
 ACCUM_SAME_ID, ACCUM_NORMAL, ACCUM_PLANE, ACCUM_SKIP_NONFINITE = 1, 2, 4, 8  # RTG_ACCUM_*
+# rtg_upsample_params (include/rtg.h): guided upsampling of a low-resolution signal
+UPSAMPLE_PARAMS_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("normalLog2", "<u4"),
+                                  ("planeScale", "<f4"), ("scaleLog2", "<u4")])
+assert UPSAMPLE_PARAMS_DTYPE.itemsize == 20
+UPSAMPLE_MAX_SCALE_LOG2 = 3  # RTG_UPSAMPLE_*
+UPSAMPLE_SAME_ID, UPSAMPLE_NORMAL, UPSAMPLE_PLANE, UPSAMPLE_SKIP_NONFINITE = 1, 2, 4, 8
 # rtg_variance_params and rtg_svgf_params (include/rtg.h): the variance-guided filter
 VARIANCE_PARAMS_DTYPE = np.dtype([("kind", "<u4"), ("flags", "<u4"), ("normalLog2", "<u4"),
                                   ("planeScale", "<f4"), ("minHistory", "<u4")])
@@ -145,6 +151,9 @@ EXPORTED = [
     "rtg_accumulate_host", "rtg_accumulate_device", "rtg_accumulate",
     "rtg_variance_host", "rtg_variance_device", "rtg_variance",
     "rtg_svgf_scratch", "rtg_svgf_host", "rtg_svgf_device", "rtg_svgf",
+    "rtg_upsample_scratch", "rtg_upsample_host", "rtg_upsample_device", "rtg_upsample",
+    "rtg_hits_pick_host", "rtg_hits_pick_device",
+    "rtg_values_place_host", "rtg_values_place_device",
     "rtg_contains_device", "rtg_contains", "rtg_contains_host",
 ]
 
@@ -345,6 +354,23 @@ def lib() -> ctypes.CDLL:
                 ("rtg_svgf_host", [vp, u, u, vp, vp, vp, vp, vp, i]),
                 ("rtg_svgf_device", [vp, vp, u, u, vp, vp, vp, vp, vp, vp, sz, vp]),
                 ("rtg_svgf", [i, vp, u, u, vp, vp, vp, vp, vp])):
+            try:
+                getattr(L, name).argtypes = at
+            except AttributeError:
+                if not os.environ.get("RTG_LIB"):
+                    raise
+        # the guided upsampling and the index calls; an RTG_LIB build of the commit
+        # before them (tools/ab_bench.sh against the parent) loads without them
+        for name, at in (
+                ("rtg_upsample_scratch", [u, u, i, vp]),
+                ("rtg_upsample_host", [vp, u, u, vp, vp, u, u, vp, vp, vp, u, vp, i]),
+                ("rtg_upsample_device",
+                 [vp, vp, u, u, vp, vp, u, u, vp, vp, vp, u, vp, vp, sz, vp]),
+                ("rtg_upsample", [i, vp, u, u, vp, vp, u, u, vp, vp, vp, u, vp]),
+                ("rtg_hits_pick_host", [vp, sz, vp, sz, vp, i]),
+                ("rtg_hits_pick_device", [vp, vp, sz, vp, sz, vp, vp]),
+                ("rtg_values_place_host", [u, vp, vp, sz, sz, vp, i]),
+                ("rtg_values_place_device", [vp, u, vp, vp, sz, sz, vp, vp])):
             try:
                 getattr(L, name).argtypes = at
             except AttributeError:
@@ -1300,6 +1326,125 @@ def accumulate(hits, width: int, height: int, params, src, prev=None, zoom: floa
     return (acc, ln, o2) if m2 else (acc, ln)
 
 
+def upsample_params(scale_log2: int, kind: int = FILTER_RGB, flags: int = 0,
+                    plane_scale: float = 0.0, normal_log2: int = 0) -> np.ndarray:
+    """One rtg_upsample_params record (scale_log2 1..3; kind: FILTER_RGB / GRAY /
+    COUNT; flags: UPSAMPLE_SAME_ID | NORMAL | PLANE | SKIP_NONFINITE)."""
+    p = np.zeros(1, UPSAMPLE_PARAMS_DTYPE)
+    p[0] = (kind, flags, normal_log2, plane_scale, scale_log2)
+    return p
+
+
+def upsample_scratch(width: int, height: int, with_holes: bool = True) -> int:
+    """Bytes of device scratch Context.upsample_device needs for such a full
+    frame (rtg_upsample_scratch): caller-owned, 16-byte aligned; 0 without a
+    hole list."""
+    out = ctypes.c_size_t(0)
+    _check(lib().rtg_upsample_scratch(width, height, int(with_holes), ctypes.byref(out)),
+           "rtg_upsample_scratch")
+    return out.value
+
+
+def _upsample_args(hits, width: int, height: int, params, low_hits, low_width: int,
+                   low_height: int, low_src, holes):
+    """The records, params and the low signal as contiguous arrays of the kind's
+    type, the destination ((H, W, 3) float32 for RGB, (H, W) otherwise), and
+    the list: `holes` None (no list), a capacity (a new array) or the caller's
+    own uint32 array, written in place."""
+    p = np.ascontiguousarray(params, UPSAMPLE_PARAMS_DTYPE).reshape(1)
+    kind = int(p["kind"][0])
+    C = 3 if kind == FILTER_RGB else 1
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    lh = np.ascontiguousarray(low_hits, HIT_DTYPE).reshape(-1)
+    s = np.ascontiguousarray(low_src, np.uint16 if kind == FILTER_COUNT else np.float32).reshape(-1)
+    nl = low_width * low_height
+    if len(h) != width * height or len(lh) != nl or len(s) != nl * C:
+        raise ValueError(f"upsample: {len(h)} records, {len(lh)} low records and {len(s)} low "
+                         f"source words for a {width} x {height} frame over a "
+                         f"{low_width} x {low_height} one of kind {kind}")
+    out = np.empty((height, width, 3) if C == 3 else (height, width), np.float32)
+    if holes is None:
+        return h, p, lh, s, out, None, 0, None
+    if isinstance(holes, np.ndarray):
+        if holes.dtype != np.uint32 or not holes.flags.c_contiguous or not holes.flags.writeable:
+            raise ValueError("upsample: holes is a writable contiguous uint32 array or a capacity")
+        lst = holes.reshape(-1)
+    else:
+        lst = np.zeros(int(holes), np.uint32)
+    return h, p, lh, s, out, lst, len(lst), np.zeros(1, np.uint32)
+
+
+def _list_ptr(lst):
+    """The list's address; a list of capacity 0 still has one."""
+    if lst is None:
+        return None, None
+    keep = lst if lst.size else np.zeros(1, np.uint32)
+    return keep, ctypes.c_void_p(keep.ctypes.data)
+
+
+def upsample_host(hits, width: int, height: int, params, low_hits, low_width: int,
+                  low_height: int, low_src, holes=None, threads: int = 1):
+    """Guided upsampling on the host (rtg_upsample_host; no GPU needed): the full
+    frame's HIT_DTYPE records, the low frame's records and signal (float32
+    (Hl, Wl, 3) or (Hl, Wl), or uint16 counts), params from upsample_params().
+    Returns the full frame, float32; with `holes` (a capacity, or a uint32
+    array that is written in place) returns (frame, list, count): the list
+    holds min(count, capacity) pixel indices in ascending order."""
+    h, p, lh, s, out, lst, cap, cnt = _upsample_args(hits, width, height, params, low_hits,
+                                                     low_width, low_height, low_src, holes)
+    keep, lp = _list_ptr(lst)
+    _check(lib().rtg_upsample_host(_ptr(h), width, height, _ptr(p), _ptr(lh), low_width,
+                                   low_height, _ptr(s), _ptr(out), lp, cap,
+                                   _ptr(cnt) if cnt is not None else None, threads),
+           "rtg_upsample_host")
+    return out if lst is None else (out, lst, int(cnt[0]))
+
+
+def upsample(hits, width: int, height: int, params, low_hits, low_width: int, low_height: int,
+             low_src, holes=None, device: int = 0):
+    """The same on the GPU, one-shot (rtg_upsample)."""
+    h, p, lh, s, out, lst, cap, cnt = _upsample_args(hits, width, height, params, low_hits,
+                                                     low_width, low_height, low_src, holes)
+    keep, lp = _list_ptr(lst)
+    _check(lib().rtg_upsample(device, _ptr(h), width, height, _ptr(p), _ptr(lh), low_width,
+                              low_height, _ptr(s), _ptr(out), lp, cap,
+                              _ptr(cnt) if cnt is not None else None),
+           "rtg_upsample")
+    return out if lst is None else (out, lst, int(cnt[0]))
+
+
+def hits_pick_host(hits, idx, threads: int = 1) -> np.ndarray:
+    """out[i] = hits[idx[i]] on the host (rtg_hits_pick_host): HIT_DTYPE records
+    and uint32 indices; an index >= len(hits) gives a miss record."""
+    h = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+    out = np.zeros(max(len(ix), 1), HIT_DTYPE)
+    keep = ix if ix.size else np.zeros(1, np.uint32)
+    _check(lib().rtg_hits_pick_host(_ptr(h), len(h), ctypes.c_void_p(keep.ctypes.data), len(ix),
+                                    ctypes.c_void_p(out.ctypes.data), threads),
+           "rtg_hits_pick_host")
+    return out[:len(ix)]
+
+
+def values_place_host(kind: int, vals, idx, dst, threads: int = 1) -> None:
+    """dst[idx[i]] = vals[i] on the host, in place (rtg_values_place_host): vals of
+    `kind` (float32 x 3, float32 or uint16 counts), dst a contiguous float32
+    array of n values; an index >= n is skipped; the indices are distinct."""
+    C = 3 if kind == FILTER_RGB else 1
+    v = np.ascontiguousarray(vals, np.uint16 if kind == FILTER_COUNT else np.float32).reshape(-1)
+    ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+    if not (isinstance(dst, np.ndarray) and dst.dtype == np.float32 and dst.flags.c_contiguous
+            and dst.flags.writeable) or dst.size % C or len(v) != len(ix) * C:
+        raise ValueError("values_place: dst is a writable contiguous float32 array of n values "
+                         "and vals holds one value per index")
+    keep = ix if ix.size else np.zeros(1, np.uint32)
+    kv = v if v.size else np.zeros(C, v.dtype)
+    _check(lib().rtg_values_place_host(kind, ctypes.c_void_p(kv.ctypes.data),
+                                       ctypes.c_void_p(keep.ctypes.data), len(ix), dst.size // C,
+                                       ctypes.c_void_p(dst.ctypes.data), threads),
+           "rtg_values_place_host")
+
+
 def variance_params(kind: int = FILTER_RGB, flags: int = 0, plane_scale: float = 0.0,
                     normal_log2: int = 0, min_history: int = 4) -> np.ndarray:
     """One rtg_variance_params record (kind: FILTER_RGB / GRAY; flags:
@@ -1825,6 +1970,48 @@ class Context:
                                            v(pv[2]), v(pv[3]), v(out_acc_ptr), v(out_len_ptr),
                                            v(out_m2_ptr), v(stream)),
                "rtg_accumulate_device")
+
+    def upsample_device(self, hits_ptr: int, width: int, height: int, params, low_hits_ptr: int,
+                        low_width: int, low_height: int, low_src_ptr: int, dst_ptr: int,
+                        holes_ptr: int = 0, hole_cap: int = 0, hole_count_ptr: int = 0,
+                        scratch_ptr: int = 0, scratch_bytes: int = 0, stream: int = 0):
+        """Guided upsampling of a low_width x low_height signal at low_src_ptr to
+        the width x height frame at dst_ptr (float32 per channel): the full
+        records at hits_ptr and the low ones at low_hits_ptr (device, as
+        filter_device takes them); with holes_ptr (uint32 x hole_cap) and
+        hole_count_ptr (one uint32) also the hole list, which needs the scratch
+        of upsample_scratch() bytes, 16-byte aligned; asynchronously on `stream`
+        (rtg_upsample_device; params from upsample_params(); the context needs
+        no scene)."""
+        p = np.ascontiguousarray(params, UPSAMPLE_PARAMS_DTYPE).reshape(1)
+        v = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        _check(lib().rtg_upsample_device(self._h, v(hits_ptr), width, height, _ptr(p),
+                                         v(low_hits_ptr), low_width, low_height, v(low_src_ptr),
+                                         v(dst_ptr), v(holes_ptr), hole_cap, v(hole_count_ptr),
+                                         v(scratch_ptr), scratch_bytes, v(stream)),
+               "rtg_upsample_device")
+
+    def hits_pick_device(self, hits_ptr: int, n: int, idx_ptr: int, m: int, out_ptr: int,
+                         stream: int = 0):
+        """out[i] = hits[idx[i]] for i < m: n HIT_DTYPE records at hits_ptr, m
+        uint32 indices at idx_ptr, m records into out_ptr (device, 16-byte
+        aligned), asynchronously on `stream` (rtg_hits_pick_device; an index >= n
+        gives a miss record)."""
+        v = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        _check(lib().rtg_hits_pick_device(self._h, v(hits_ptr), n, v(idx_ptr), m, v(out_ptr),
+                                          v(stream)),
+               "rtg_hits_pick_device")
+
+    def values_place_device(self, kind: int, vals_ptr: int, idx_ptr: int, m: int, n: int,
+                            dst_ptr: int, stream: int = 0):
+        """dst[idx[i]] = vals[i] for i < m: m values of `kind` at vals_ptr into the
+        n float32 values (x 3 for RGB) at dst_ptr, asynchronously on `stream`
+        (rtg_values_place_device; an index >= n is skipped, the indices are
+        distinct)."""
+        v = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        _check(lib().rtg_values_place_device(self._h, kind, v(vals_ptr), v(idx_ptr), m, n,
+                                             v(dst_ptr), v(stream)),
+               "rtg_values_place_device")
 
     def variance_device(self, hits_ptr: int, width: int, height: int, params, acc_ptr: int,
                         m2_ptr: int, len_ptr: int, var_ptr: int, stream: int = 0):

@@ -2,7 +2,8 @@
 """tools/bench_rays.py [--rounds N] [--out FILE] [--parent-json FILE] [--only-camera]
                        [--only-order] [--only-ao] [--only-matte] [--only-views]
                        [--only-fold] [--only-gather] [--only-filter] [--only-accumulate]
-                       [--only-svgf] [--order-alt-json FILE ...]
+                       [--only-svgf] [--only-irradiance] [--only-upsample]
+                       [--order-alt-json FILE ...]
 
 Times rtg_intersect_device (the batch closest-hit query, csrc/rtg_rays.hip)
 with the scene and the rays resident, on three batches of bench.py's frames:
@@ -112,6 +113,15 @@ with VALID | FACING and with all three, next to the unfused chain (torch cells
 and segments, rtg_visible_device, a torch gather and fold of the same
 arithmetic) and the streaming floor.  --only-irradiance runs these alone and
 keeps FILE's other sections.
+
+The guided upsampling (rtg_upsample_device, rtg_hits_pick_device,
+rtg_values_place_device, csrc/rtg_upsample.hip) gets rows under "upsample"
+(upsample_rows below): the call alone on C3 and C5 frames at L = 1 and 2 with
+and without the hole list, against its streaming floor and a torch chain of
+the same arithmetic plus nonzero (gated: equal words and list), and the
+mixed-resolution route of the gather and of the AO against the full-resolution
+call in the same rounds.  --only-upsample runs these alone and keeps FILE's
+other sections.
 GPU only.
 """
 import argparse
@@ -1070,6 +1080,284 @@ def accumulate_rows(args, stream):
     return out, ok
 
 
+def torch_upsample(full, low, L, W, H, flags, nlog, scale):
+    """rtg_upsample* (include/rtg.h) as a chain of torch operations in the
+    definition's operand order: index gathers for the four taps, `where` for the
+    rules, the quotient, and `nonzero` for the list.  full = (ids, P, N), low =
+    (ids, P, N, value planes), planes of (H, W) and (Hl, Wl); returns (planes,
+    the holes' pixel indices)."""
+    ids, P, N = full
+    lid, lP, lN, val = low
+    f, Wl, Hl = 1 << L, W >> L, H >> L
+    dot = lambda a, b: (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]  # noqa: E731
+    zero = torch.zeros((), dtype=torch.float32, device="cuda")
+    y, x = torch.meshgrid(torch.arange(H, device="cuda"), torch.arange(W, device="cuda"), indexing="ij")
+    x0, y0 = x >> L, y >> L
+    tx = (x & (f - 1)).to(torch.float32) * (1.0 / f)
+    ty = (y & (f - 1)).to(torch.float32) * (1.0 / f)
+    acc = [torch.zeros((H, W), dtype=torch.float32, device="cuda") for _ in val]
+    sw = torch.zeros((H, W), dtype=torch.float32, device="cuda")
+    for dy in (0, 1):
+        for dx in (0, 1):
+            xq, yq = x0 + dx, y0 + dy
+            keep = (xq < Wl) & (yq < Hl) & (ids >= 0)
+            xs, ys = xq.clamp(max=Wl - 1), yq.clamp(max=Hl - 1)
+            w = (ty if dy else 1.0 - ty) * (tx if dx else 1.0 - tx)
+            idq = lid[ys, xs]
+            keep &= idq >= 0
+            if flags & R.UPSAMPLE_SAME_ID:
+                keep &= idq == ids
+            if flags & R.UPSAMPLE_NORMAL:
+                c = dot(N, [lN[q][ys, xs] for q in range(3)])
+                c = torch.where(c > 0, c, zero)
+                for _ in range(nlog):
+                    c = c * c
+                w = w * c
+            if flags & R.UPSAMPLE_PLANE:
+                d = dot(N, [lP[q][ys, xs] - P[q] for q in range(3)]).abs()
+                z = 1.0 - d * scale
+                w = w * torch.where(z > 0, z, zero)
+            keep &= w > 0
+            for q in range(len(val)):
+                acc[q] = torch.where(keep, acc[q] + w * val[q][ys, xs], acc[q])
+            sw = torch.where(keep, sw + w, sw)
+    found = sw > 0
+    out = [torch.where(found, a / sw, zero) for a in acc]
+    holes = torch.nonzero(((ids >= 0) & ~found).reshape(-1)).reshape(-1)
+    return out, holes
+
+
+def upsample_rows(args, stream):
+    """The guided upsampling (csrc/rtg_upsample.hip) with SAME_ID | NORMAL |
+    PLANE, planeScale 4 / (the scene's largest |radius|) and normalLog2 3, from
+    the identity pose.  THE CALL ALONE: the K = 16 AO counts (COUNT) and the
+    direct light (RGB) of the low frame's aa = 1 primary hits brought up to
+    3840 x 2160 on C3 and to 1920 x 1080 on C5, L = 1 and 2, with and without the
+    hole list, against the streaming floor (32 B of record in and 4 C B out per
+    full pixel, the low records and values once, at 6 TB/s) and against a torch
+    chain of the same arithmetic plus `nonzero`.  Gated: the call's words and
+    list are the chain's.  THE ROUTE: the gather at K = 16 on C5 at 1920 x 1080
+    and the AO at K = 16 on C5 at 3840 x 2160, jitter off, at full resolution
+    against the sum of low records + low signal + upsample with the list + pick
+    + the signal on the holes + place, L = 1 and 2; the gather's low frame and
+    its holes both through the fused call and through gather_rays + raytrace +
+    a torch fold (mixed: both fused; mixed_low_unfused; mixed_unfused: both).
+    Reported, not gated: every time, the hole share, and the mean and largest
+    absolute difference of the mixed-resolution frame from the full one."""
+    K, nlog = 16, 3
+    flags = R.UPSAMPLE_SAME_ID | R.UPSAMPLE_NORMAL | R.UPSAMPLE_PLANE
+    table = torch.from_numpy(R.ao_directions(K)).cuda()
+    wt = torch.full((K,), 1.0 / K, dtype=torch.float32, device="cuda")
+    cam = R.camera_identity()
+    out, ok = {"flags": flags, "normalLog2": nlog, "plane_scale": "4 / largest |radius|",
+               "samples": K, "floor_bandwidth_TBps": 6.0, "call": {}, "route": {}}, True
+
+    def records(ctx, W, H):
+        n = W * H
+        rays = torch.empty((n, 6), dtype=torch.float32, device="cuda")
+        hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        ctx.camera_rays(cam, W, H, rays.data_ptr(), alias_factor=1.0, stream=stream)
+        ctx.intersect_device(rays.data_ptr(), n, hits.data_ptr(), stream)
+        torch.cuda.synchronize()
+        return rays, hits
+
+    def planes(hits, W, H):
+        h = hits.view(torch.float32)
+        return (hits[:, 0].reshape(H, W).contiguous(),
+                [h[:, 2 + q].reshape(H, W).contiguous() for q in range(3)],
+                [h[:, 5 + q].reshape(H, W).contiguous() for q in range(3)])
+
+    # ---- the call alone ----
+    for cfg, (W, H) in (("c3", CONFIGS["c3"][:2]), ("c5", (1920, 1080))):
+        n = W * H
+        sph, lg = R.generate_scene(CONFIGS[cfg][2], CONFIGS[cfg][3], 42)
+        scale = float(F(4) / np.abs(sph["radius"]).max())
+        radius = float(F(2.5) * np.abs(sph["radius"]).max())
+        ctx = R.Context(0)
+        ctx.set_scene(sph, lg)
+        _, hits = records(ctx, W, H)
+        full = planes(hits, W, H)
+        n_hit = int((hits[:, 0] >= 0).sum())
+        nbytes = R.upsample_scratch(W, H, True)
+        scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device="cuda")
+        lst = torch.empty((n,), dtype=torch.int32, device="cuda")
+        cnt = torch.zeros((1,), dtype=torch.int32, device="cuda")
+        for L in (1, 2):
+            Wl, Hl = W >> L, H >> L
+            nl = Wl * Hl
+            _, low = records(ctx, Wl, Hl)
+            lowp = planes(low, Wl, Hl)
+            for kname, kind, C in (("count", R.FILTER_COUNT, 1), ("rgb", R.FILTER_RGB, 3)):
+                if kind == R.FILTER_COUNT:
+                    src = torch.empty((nl,), dtype=torch.int16, device="cuda")
+                    ctx.ao_device(low.data_ptr(), nl, R.ao_params(K, radius, 1e-3, 42, 0),
+                                  table.data_ptr(), K, src.data_ptr(), stream)
+                    val = [(src.to(torch.int32) & 0xFFFF).to(torch.float32).reshape(Hl, Wl)]
+                else:
+                    src = torch.empty((nl, 3), dtype=torch.float32, device="cuda")
+                    ctx.matte_device(low.data_ptr(), nl, src.data_ptr(), stream=stream)
+                    torch.cuda.synchronize()
+                    val = [src[:, q].reshape(Hl, Wl).contiguous() for q in range(3)]
+                p = R.upsample_params(L, kind, flags, scale, nlog)
+                dst = torch.empty((n, C), dtype=torch.float32, device="cuda")
+                args_ = (hits.data_ptr(), W, H, p, low.data_ptr(), Wl, Hl, src.data_ptr(), dst.data_ptr())
+                plain = lambda: ctx.upsample_device(*args_, stream=stream)  # noqa: E731
+                listed = lambda: ctx.upsample_device(*args_, lst.data_ptr(), n, cnt.data_ptr(),  # noqa: E731
+                                                     scratch.data_ptr(), nbytes, stream=stream)
+                chain = lambda: torch_upsample(full, lowp + (val,), L, W, H, flags, nlog, scale)  # noqa: E731
+                row_name = f"{cfg}_{kname}_L{L}"
+                m = measure([plain, listed], args.rounds, window_ms=100.0,
+                            names=[f"upsample {row_name} {k}" for k in ("no list", "list")])
+                tm = measure([chain], args.rounds, window_ms=100.0, min_reps=1,
+                             names=[f"upsample {row_name} torch chain"])[0]
+                listed()
+                torch.cuda.synchronize()
+                holes = int(cnt.cpu().numpy().view(np.uint32)[0])
+                ref, ref_holes = chain()
+                ref = torch.stack(ref, -1).reshape(n, C)
+                nan = torch.isnan(ref)
+                same = bool(((dst.view(torch.int32) == ref.view(torch.int32)) | nan).all()) and \
+                    bool((torch.isnan(dst) == nan).all())
+                same_list = holes == ref_holes.numel() and \
+                    bool((lst[:holes].to(torch.int64) == ref_holes).all())
+                ok = ok and same and same_list
+                floor = (n * (32 + 4 * C) + nl * (32 + (2 if kind == R.FILTER_COUNT else 12))) / 6.0e12 * 1e3
+                out["call"][row_name] = {
+                    "W": W, "H": H, "scaleLog2": L, "kind": int(kind), "hit_points": n_hit,
+                    "holes": holes, "hole_share_of_hit_pixels": round(holes / max(n_hit, 1), 5),
+                    "scratch_bytes": nbytes, "floor_ms": round(floor, 5),
+                    "no_list": m[0], "list": m[1],
+                    "no_list_over_floor": round(m[0]["ms_median"] / floor, 2),
+                    "list_over_floor": round(m[1]["ms_median"] / floor, 2),
+                    "torch_chain": tm, "torch_over_list": round(tm["ms_median"] / m[1]["ms_median"], 2),
+                    "words_equal": same, "list_equal": same_list}
+                print(f"upsample {row_name}: {m[0]['ms_median']} / {m[1]['ms_median']} ms (floor "
+                      f"{floor:.4f}), torch {tm['ms_median']} ms, holes {holes}, equal "
+                      f"{same and same_list}", file=sys.stderr, flush=True)
+                del src, val, dst, ref, ref_holes, nan
+            del low, lowp
+        ctx.close()
+        del hits, full, scratch, lst, cnt
+        torch.cuda.empty_cache()
+
+    # ---- the route it exists for ----
+    sph, lg = R.generate_scene(CONFIGS["c5"][2], CONFIGS["c5"][3], 42)
+    scale = float(F(4) / np.abs(sph["radius"]).max())
+    radius = float(F(2.5) * np.abs(sph["radius"]).max())
+    S = CONFIGS["c5"][4] + 1
+    ctx = R.Context(0)
+    ctx.set_scene(sph, lg)
+    gp = R.gather_params(K, 1e-3, 42, R.GATHER_SKIP_NONFINITE)
+    ap = R.ao_params(K, radius, 1e-3, 42, 0)
+    for rname, (W, H), kind, C in (("gather_c5_1080p", (1920, 1080), R.FILTER_RGB, 3),
+                                   ("ao_c5_2160p", (3840, 2160), R.FILTER_COUNT, 1)):
+        n = W * H
+        rgb = kind == R.FILTER_RGB
+        vdtype, vshape = (torch.float32, (3,)) if rgb else (torch.int16, ())
+        _, hits = records(ctx, W, H)
+        n_hit = int((hits[:, 0] >= 0).sum())
+        whole = torch.empty((n,) + vshape, dtype=vdtype, device="cuda")
+
+        def signal(h, m, dst):
+            if rgb:
+                ctx.gather_device(h.data_ptr(), m, gp, table.data_ptr(), wt.data_ptr(), K,
+                                  dst.data_ptr(), stack_size=S, stream=stream)
+            else:
+                ctx.ao_device(h.data_ptr(), m, ap, table.data_ptr(), K, dst.data_ptr(), stream)
+
+        nbytes = R.upsample_scratch(W, H, True)
+        scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device="cuda")
+        lst = torch.empty((n,), dtype=torch.int32, device="cuda")
+        cnt = torch.zeros((1,), dtype=torch.int32, device="cuda")
+        mixed = torch.empty((n, C), dtype=torch.float32, device="cuda")
+        picked = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        own = torch.empty((n,) + vshape, dtype=vdtype, device="cuda")
+        signal(hits, n, whole)
+        torch.cuda.synchronize()
+        ref = whole.to(torch.float32).reshape(n, C) if rgb else \
+            (whole.to(torch.int32) & 0xFFFF).to(torch.float32).reshape(n, C)
+        row = {"W": W, "H": H, "kind": int(kind), "hit_points": n_hit, "stack_size": S}
+        for L in (1, 2):
+            Wl, Hl = W >> L, H >> L
+            nl = Wl * Hl
+            lrays = torch.empty((nl, 6), dtype=torch.float32, device="cuda")
+            low = torch.empty((nl, 8), dtype=torch.int32, device="cuda")
+            lsig = torch.empty((nl,) + vshape, dtype=vdtype, device="cuda")
+            p = R.upsample_params(L, kind, flags | (R.UPSAMPLE_SKIP_NONFINITE if rgb else 0), scale, nlog)
+
+            def low_records():
+                ctx.camera_rays(cam, Wl, Hl, lrays.data_ptr(), alias_factor=1.0, stream=stream)
+                ctx.intersect_device(lrays.data_ptr(), nl, low.data_ptr(), stream)
+
+            def up():
+                ctx.upsample_device(hits.data_ptr(), W, H, p, low.data_ptr(), Wl, Hl, lsig.data_ptr(),
+                                    mixed.data_ptr(), lst.data_ptr(), n, cnt.data_ptr(),
+                                    scratch.data_ptr(), nbytes, stream=stream)
+
+            low_records()
+            signal(low, nl, lsig)
+            up()
+            torch.cuda.synchronize()
+            m_holes = int(cnt.cpu().numpy().view(np.uint32)[0])
+            fns = [lambda: signal(hits, n, whole), low_records, lambda: signal(low, nl, lsig), up,
+                   lambda: ctx.hits_pick_device(hits.data_ptr(), n, lst.data_ptr(), m_holes,
+                                                picked.data_ptr(), stream=stream),
+                   lambda: signal(picked, m_holes, own),
+                   lambda: ctx.values_place_device(kind, own.data_ptr(), lst.data_ptr(), m_holes, n,
+                                                   mixed.data_ptr(), stream=stream)]
+            names = ["full", "low_records", "low_signal", "upsample_list", "pick", "holes_signal", "place"]
+            if rgb:  # the low frame through the unfused chain too
+                prays = torch.empty((nl * K, 6), dtype=torch.float32, device="cuda")
+                pcols = torch.empty((nl * K, 3), dtype=torch.float32, device="cuda")
+                fns += [lambda: ctx.gather_rays_device(low.data_ptr(), nl, gp, table.data_ptr(), K,
+                                                       prays.data_ptr(), stream),
+                        lambda: ctx.raytrace_device(prays.data_ptr(), nl * K, pcols.data_ptr(), S, stream),
+                        lambda: (pcols.view(nl, K, 3) * wt.view(1, K, 1)).sum(1),
+                        # (and the holes: a few dozen points leave the fused call's lanes idle)
+                        lambda: ctx.gather_rays_device(picked.data_ptr(), m_holes, gp, table.data_ptr(),
+                                                       K, prays.data_ptr(), stream),
+                        lambda: ctx.raytrace_device(prays.data_ptr(), m_holes * K, pcols.data_ptr(), S,
+                                                    stream),
+                        lambda: (pcols[:m_holes * K].view(m_holes, K, 3) * wt.view(1, K, 1)).sum(1)]
+                names += ["low_rays", "low_raytrace", "low_fold", "holes_rays", "holes_raytrace",
+                          "holes_fold"]
+            raw = []
+            m = measure(fns, args.rounds, raw=raw, min_reps=2,
+                        names=[f"route {rname} L{L} {k}" for k in names])
+            torch.cuda.synchronize()
+            sums = {"mixed": [sum(v) for v in zip(*raw[1:7])]}
+            if rgb:
+                sums["mixed_low_unfused"] = [sum(v) for v in zip(raw[1], raw[7], raw[8], raw[9], *raw[3:7])]
+                sums["mixed_unfused"] = [sum(v) for v in zip(raw[1], *raw[7:10], raw[3], raw[4],
+                                                             *raw[10:13], raw[6])]
+            rows = _spread_rows(sums)
+            diff = (mixed - ref).abs()[hits[:, 0] >= 0]
+            diff = diff[torch.isfinite(diff)]
+            row[f"L{L}"] = {
+                **dict(zip(names, m)), **rows,
+                "holes": m_holes, "hole_share_of_hit_pixels": round(m_holes / max(n_hit, 1), 5),
+                "full_over_mixed": round(m[0]["ms_median"] / rows["mixed"]["ms_median"], 3),
+                **({"low_fused_over_low_unfused": round(
+                    m[2]["ms_median"] / (m[7]["ms_median"] + m[8]["ms_median"] + m[9]["ms_median"]), 3),
+                    "full_over_mixed_unfused": round(
+                        m[0]["ms_median"] / rows["mixed_unfused"]["ms_median"], 3)}
+                   if rgb else {}),
+                "mean_abs_difference_from_full": float(diff.mean()) if diff.numel() else 0.0,
+                "largest_abs_difference_from_full": float(diff.max()) if diff.numel() else 0.0,
+                "mean_of_full_signal": float(ref[hits[:, 0] >= 0][torch.isfinite(ref[hits[:, 0] >= 0])].mean())}
+            print(f"route {rname} L{L}: full {m[0]['ms_median']} ms, mixed "
+                  f"{rows['mixed']['ms_median']} ms, holes {m_holes} of {n_hit}", file=sys.stderr,
+                  flush=True)
+            del lrays, low, lsig
+            if rgb:
+                del prays, pcols
+        out["route"][rname] = row
+        del hits, whole, scratch, lst, cnt, mixed, picked, own, ref
+        torch.cuda.empty_cache()
+    ctx.close()
+    return out, ok
+
+
 def matte_rows(args, W, H, rays, stream):
     """Direct light (csrc/rtg_matte.hip) of the frame's 8.3 M aa = 1 primary
     hits on C3 (3 lights) and C5 (4 lights).  Round by round in one process: the
@@ -1592,6 +1880,9 @@ def main():
     ap.add_argument("--only-svgf", action="store_true",
                     help="the variance estimate's and the variance-guided passes' rows alone, put into "
                          "FILE next to what it holds")
+    ap.add_argument("--only-upsample", action="store_true",
+                    help="the guided upsampling's rows and the mixed-resolution route alone, put into "
+                         "FILE next to what it holds")
     ap.add_argument("--only-irradiance", action="store_true",
                     help="the probe grid's lookup rows alone, put into FILE next to what it holds")
     ap.add_argument("--parent-commit", default="",
@@ -1661,6 +1952,15 @@ def main():
         res["svgf_commit"], res["svgf_parent_commit"] = args.commit, args.parent_commit
         res["svgf"], ok = svgf_rows(args, torch.cuda.current_stream().cuda_stream)
         res["svgf"]["rounds"] = args.rounds
+        finish(args, res, ok)
+    if args.only_upsample:  # (the same: it makes the low and the full frames of its own)
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["upsample_commit"], res["upsample_parent_commit"] = args.commit, args.parent_commit
+        res["upsample"], ok = upsample_rows(args, torch.cuda.current_stream().cuda_stream)
+        res["upsample"]["rounds"] = args.rounds
         finish(args, res, ok)
     if args.only_irradiance:  # (the same: it makes the hits and the grid of its own frames)
         res = {}
